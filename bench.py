@@ -1,15 +1,23 @@
 #!/usr/bin/env python
 """Headline benchmark: g-SpMM copy_u+sum on an ogbn-products-shaped CSR.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (dgla_spmm_csr: split-row copy of X when the graph's
 locality probe wants it, merge kernel, fix-up kernel) over the whole synthetic graph:
 N = 2,449,029 rows, E = 61,859,140 edges, F = 100, fp32, int32 ids, column ids uniform
 ("variant U") with inputs resident in HBM; X is treated as a NEW tensor on
 every step (nothing about it is cached between steps).  Rank 0 prints ONE JSON line with
-edges/s, the HBM roofline of the dominant kernel and the CPU baseline; `variants` adds the
-locality variant L and the static-feature mode, timed outside the K steps.
+edges/s, ms_per_step and the HBM roofline of the dominant kernel.
+
+A plain run only sets up, warms up and times the K steps.  `--full` adds everything measured
+outside the K steps: the CPU baseline and the full-size parity check against the oracle, the
+measured streaming peaks, `variants` (the locality variant L, the static-feature mode, int64
+ids, the other hot-path operators) and, with N > 1, the per-kernel and exchange profiles, the
+parity check against one launch over the whole graph and the other partition / exchange lines.
+
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs()) as .npy
+files; the inputs are generated from fixed seeds, so two builds can be compared file by file.
 
 With N > 1 (launched by torch.distributed.run, one rank per GPU) the SAME graph is partitioned
 over the ranks (strong scaling): node partition -> per-rank shard (own-column block +
@@ -449,6 +457,43 @@ def multi_gpu(args, dev, n, e, f, rank, world, dist, spmm=None):
     return step, ctx
 
 
+DUMP_SAMPLE_ROWS = 65536  # 26 MB of fp32 rows at F = 100
+
+
+def dump_outputs(path, out, rows, n, rank=0, dist=None):
+    """Write what the last timed step computed to `path`: the destination-row features a caller of the hot path
+    receives (N x F fp32, 980 MB at full size) as a fixed, seeded sample of DUMP_SAMPLE_ROWS rows in ascending row
+    order (out_rows_sample.npy), the global ids of those rows (out_row_ids.npy) and the float64 column sums of the
+    WHOLE output (out_column_sums.npy).  N > 1: `rows` = the global ids of this rank's rows; rank 0 assembles the same
+    three arrays from every rank's share, so the files do not depend on the number of GPUs."""
+    f = out.shape[1]
+    ids = np.sort(np.random.default_rng(20250824).choice(n, size=min(n, DUMP_SAMPLE_ROWS), replace=False))
+    ids_t = torch.from_numpy(ids).to(out.device)
+    if rows is None:
+        sample = out[ids_t].cpu().numpy()
+        colsum = out.sum(0, dtype=torch.float64).cpu().numpy()
+    else:
+        where = torch.full((n,), -1, dtype=torch.int64, device=out.device)
+        where[rows.to(out.device).long()] = torch.arange(rows.shape[0], device=out.device)
+        local = where[ids_t]
+        mine = local >= 0
+        part = (torch.nonzero(mine).flatten().cpu().numpy(), out[local[mine]].cpu().numpy(),
+                out.sum(0, dtype=torch.float64).cpu().numpy())
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+        sample = np.full((ids.shape[0], f), np.nan, dtype=np.float32)
+        colsum = np.zeros(f, dtype=np.float64)
+        for pos, vals, cs in parts:
+            sample[pos] = vals
+            colsum += cs
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "out_rows_sample.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(path, "out_row_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, "out_column_sums.npy"), colsum.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -468,11 +513,18 @@ def main():
     ap.add_argument("--exchange", default="peer", choices=["peer", "alltoall"],
                     help="N > 1: halo exchange — peer = the pack kernel writes into the peers' IPC-mapped halo buffers "
                          "and flags (no collective); alltoall = pack + all_to_all_single over RCCL")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-peak", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what lies outside the K steps: CPU baseline + oracle parity, streaming "
+                         "peaks, variants, N > 1 profiles / parity / other partitions (--no-cpu, --no-peak, "
+                         "--no-variants trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (a fixed sample of its rows and its column sums) to "
+                         "DIR/*.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the oracle parity check")
+    ap.add_argument("--no-peak", action="store_true", help="--full: skip the measured streaming peaks")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the extra variant-L / static-feature timings of the N=1 line")
-    ap.add_argument("--extra", action="store_true", help="also time int64 ids")
+                    help="--full: skip the extra variant-L / static-feature timings of the N=1 line")
+    ap.add_argument("--extra", action="store_true", help="--full: also time int64 ids")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -550,11 +602,17 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx["out"], None if world == 1 else ctx["shard"]["rows"], n, rank, dist)
+
     # ---- dominant-kernel duration (HIP events on the launch stream) -------------------
+    kernel_name = "spmm_csr_merge_kernel<int,float,VEC=4,copy_lhs,sum>"
     if world == 1:
         kern_ms = [a.elapsed_time(b) for a, b in k_ev]
         kern_avg, kern_min = float(np.mean(kern_ms)), float(np.min(kern_ms))
-        kernel_name = "spmm_csr_merge_kernel<int,float,VEC=4,copy_lhs,sum>"
+    elif not args.full:
+        kern_avg = kern_min = None  # N > 1: the launches are timed alone only under --full
+        kernel_name += " x2 (own-column + halo-column block)"
     else:
         # a step has two launches of the merge kernel (own-column block, halo-column block):
         # time each alone, outside the timed region; the roofline is quoted on their sum
@@ -570,7 +628,7 @@ def main():
         kernel_name = "spmm_csr_merge_kernel<int,float,VEC=4,copy_lhs,sum> x2 (own-column + halo-column block)"
 
     profs = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = exchange_profile(ctx["op"], ctx["x_loc"], ctx["out"], dist, dev)
         mine["rank"] = rank
         mine["halo_MB"] = round(ctx["shard"]["n_halo"] * f * 4 / 1e6, 3)
@@ -579,7 +637,7 @@ def main():
 
     result = None
     if rank == 0:
-        achieved = ctx["alg_bytes"] / (kern_avg * 1e-3) / 1e9
+        achieved = ctx["alg_bytes"] / (kern_avg * 1e-3) / 1e9 if kern_avg is not None else None
         kernel_only = achieved
         if world > 1:
             # N > 1: the roofline of the WHOLE STEP — exchange included: the job's algorithmic bytes over the
@@ -640,7 +698,7 @@ def main():
             # what the exchange costs and how much of it hides (measured after the timed region, same shards):
             # exchange_ms = the exchange with nothing to overlap (max over ranks); wait_ms = what a step still waits
             # for halo rows (max over ranks); overlap_frac = 1 - wait / exchange (min over ranks)
-            result["exchange_profile"] = {
+            result["exchange_profile"] = None if profs is None else {
                 "exchange_ms": max(p["exchange_alone_ms"] for p in profs),
                 "push_ms": max((p.get("push_ms") or 0.0) for p in profs) or None,
                 "wait_ms": max(p.get("wait_ms", 0.0) for p in profs),
@@ -658,7 +716,7 @@ def main():
             result["roofline"]["note"] = ("whole step, exchange included: the job's algorithmic bytes / max-over-ranks "
                                           "step time / n_gpus; `kernel` fields = rank 0's two merge launches timed alone")
             result["roofline"]["kernel_only_achieved_rank0"] = kernel_only
-            result["roofline"]["kernel_only_frac_rank0"] = kernel_only / HBM_PEAK_GBPS
+            result["roofline"]["kernel_only_frac_rank0"] = kernel_only / HBM_PEAK_GBPS if kernel_only is not None else None
             result["roofline"]["algorithmic_bytes_per_launch"] = algorithmic_bytes(n, e, f)
 
     if rank == 0 and world == 1 and args.scale == 1 and args.variant == "U":
@@ -666,8 +724,8 @@ def main():
         result["roofline"]["traffic"] = t
         result["roofline"]["traffic_source"] = src
 
-    # ---- N > 1: every rank checks its rows against the one-launch result on the whole graph
-    if world > 1:
+    # ---- N > 1 (--full): every rank checks its rows against the one-launch result on the whole graph
+    if world > 1 and args.full:
         sh = ctx["shard"]
         g, xf = ctx["g"], ctx["x"]
         full = torch.empty(n, f, device=dev)
@@ -852,8 +910,8 @@ def main():
             close_exchange(ctx_c, dist)
             del ctx_c, step_c
 
-    # ---- extras on rank 0, outside the timed region ----------------------------------
-    if rank == 0 and world == 1:
+    # ---- extras on rank 0, outside the timed region (--full) -------------------------
+    if rank == 0 and world == 1 and args.full:
         if not args.no_peak:
             try:
                 peak, rpeak, which = measure_copy_peak(dev, nbytes=(4 << 30) // max(1, args.scale))

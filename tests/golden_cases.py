@@ -14,6 +14,13 @@ from tests.graphgen import coo_to_csc, coo_to_csr
 SPMM_OPS = ["add", "sub", "mul", "div", "copy_lhs", "copy_rhs"]
 SDDMM_OPS = SPMM_OPS + ["dot"]
 REDUCES = ["sum", "max", "min"]
+# (op, lhs shape, rhs shape) of the broadcast-table checks against CalcBcastOff
+BCAST_CASES = [
+    ("mul", (5, 4, 8), (9, 4, 1)), ("add", (5, 3, 1), (9, 1, 4)), ("dot", (5, 3, 1, 4), (9, 1, 5, 4)),
+    ("dot", (5, 2, 16), (5, 2, 16)), ("copy_lhs", (5, 7), (9, 3)), ("copy_rhs", (5, 7), (9, 3)),
+    ("sub", (1, 2, 1, 3, 1), (1, 4, 1, 3, 1, 1)), ("div", (2, 5, 3, 1, 7), (2, 1, 3, 7, 1)),
+    ("mul", (4, 1), (4, 1)), ("add", (4, 3), (4, 1)),
+]
 
 
 def _graph(kind, seed):
@@ -156,6 +163,17 @@ def all_cases(full=False):
     names = [c["name"] for c in cases]
     assert len(set(names)) == len(names), "duplicate case names"
     return cases
+
+
+def c2_shaped_input():
+    """A 1/64-scale ogbn-products-shaped CSR (heavy-tailed rows) and fp32 features: (indptr, indices, x)."""
+    from tests.graphgen import C2_EDGES, C2_NODES, synth_csr
+
+    n, e = C2_NODES // 64, C2_EDGES // 64
+    g = synth_csr(n, n, e, "U")
+    rng = np.random.default_rng(5)
+    x = (rng.random((n, 100)) + 1).astype(np.float32)
+    return g["indptr"].numpy(), g["indices"].numpy(), x
 
 
 def run_case(backend, c):

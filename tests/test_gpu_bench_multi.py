@@ -16,13 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_on_one_gpu():
-    """`python bench.py --gpus 2` with NO launcher environment: bench.py starts its own ranks
+    """`python bench.py --gpus 2 --full` with NO launcher environment: bench.py starts its own ranks
     (VERDICT r2 Missing #1)."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DGLA_BENCH_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "1", "--scale", "32"], env=env, stdout=subprocess.PIPE,
+                        "--warmup", "1", "--scale", "32", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, cwd=ROOT, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
     outs = [(p.stdout, p.stderr)]
@@ -62,7 +62,7 @@ def test_bench_falls_back_to_all_to_all_when_the_peer_setup_fails_on_one_rank():
     env["DGLA_BENCH_BACKEND"] = "gloo"
     env["DGLA_PEER_FAIL_RANK"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--scale", "64"], env=env, stdout=subprocess.PIPE,
+                        "--warmup", "1", "--scale", "64", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, cwd=ROOT, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

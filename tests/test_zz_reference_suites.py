@@ -1,7 +1,7 @@
 """The REFERENCE'S OWN test suites, unmodified, inside `pytest -m gpu` (VERDICT r5 Next #1b).
 
-`__graft_entry__.build()` (in the container that has /root/reference) copies the suites' files into scratch/ref_tests/
-(git-ignored, travels with the snapshot) and writes their test ids; here every reference test id is one pytest test:
+`tools/ref_suite/run.py --prepare --src <reference checkout>/tests` copies the suites' files into scratch/ref_tests/
+(git-ignored) and `--collect --suite S --device cpu` writes their test ids; here every reference test id is one pytest test:
 a session fixture runs each suite ONCE in a subprocess (`tools/ref_suite/run.py`: `import dgl` -> dgl_amd, the
 reference's files executed as they are, DGLTESTDEV=gpu) and each id asserts its own outcome.  Suites:
 
@@ -12,8 +12,8 @@ reference's files executed as they are, DGLTESTDEV=gpu) and each id asserts its 
             the reference's own LAYER files imported unmodified over the alias (dgl_amd ships no layer code)
   sampling, sparse   the callers either side of the path
 
-Named test_zz_* so that it runs after the package's own parity tests.  Skips with a reason when scratch/ref_tests is
-absent (a checkout on which build() never ran next to /root/reference)."""
+Named test_zz_* so that it runs after the package's own parity tests.  The reference's files are not part of this
+repository, so on a checkout where they were never prepared it skips with a reason."""
 import json
 import os
 import subprocess
@@ -55,8 +55,8 @@ def _run(suite):
 
 def _need():
     if not os.path.isdir(DEST):
-        pytest.skip("scratch/ref_tests is absent: __graft_entry__.build() copies the reference's suites there when "
-                    "/root/reference exists (tools/ref_suite/run.py --prepare)")
+        pytest.skip("scratch/ref_tests is absent: the reference's suites are prepared there by hand "
+                    "(tools/ref_suite/run.py --prepare, then --collect per suite)")
 
 
 @pytest.mark.parametrize("suite", SUITES)
@@ -75,7 +75,7 @@ def pytest_generate_tests(metafunc):
     if "ref_id" in metafunc.fixturenames:
         ids = [(s, i) for s in SUITES for i in _ids(s)]
         metafunc.parametrize("suite_of_id,ref_id", ids or [pytest.param("", "", marks=pytest.mark.skip(
-            reason="scratch/ref_tests is absent (build() next to /root/reference makes it)"))],
+            reason="scratch/ref_tests is absent (tools/ref_suite/run.py --prepare / --collect make it)"))],
             ids=[i for _, i in ids] or None)
 
 
