@@ -200,6 +200,18 @@ def edge_softmax_backward(csr, out, sds, back, workspace=None, plan_valid=False,
                                               ctypes.byref(tb), wp, wn, fl, _stream(back)))
 
 
+def gat_attention_supported(dtype, heads, dim):
+    """Whether the one-pass GAT attention kernels take (dtype, H, D) (dgla_gat_attention_supported; needs no GPU)."""
+    code = _DTYPES.get(dtype)
+    return code is not None and bool(LIB.dgla_gat_attention_supported(code, int(heads), int(dim)))
+
+
+def _gat_same_dtype(ft, *others):
+    for t in others:
+        if t.dtype != ft.dtype:
+            raise _lib.DGLAMDError("gat_attention: every tensor carries the operands' dtype (%s), got %s" % (ft.dtype, t.dtype))
+
+
 def gat_attention_workspace_bytes(csc, heads, dim):
     return int(LIB.dgla_gat_attention_workspace_bytes(ctypes.byref(csc), int(heads), int(dim)))
 
@@ -208,8 +220,11 @@ def gat_attention_forward(csc, ft, el, er, slope, out, mz, workspace):
     """out[v] = sum_u softmax_v(leaky_relu(el[u] + er[v])) ft[u] per head in one pass (dgla_gat_attention_forward);
     `mz` (N_dst, H, 2) fp32 receives each row's softmax maximum and normaliser for the backward."""
     keep = []
+    _gat_same_dtype(ft, el, er, out)
     tf, tl, tr, to = (_tensor(t, keep) for t in (ft, el, er, out))
     _require_gpu(mz)
+    if mz.dtype != torch.float32:
+        raise _lib.DGLAMDError("gat_attention: mz is fp32 whatever the operands' dtype")
     check_call(LIB.dgla_gat_attention_forward(ctypes.byref(csc), _DTYPES[ft.dtype], ctypes.byref(tf), ctypes.byref(tl),
                                               ctypes.byref(tr), float(slope), ctypes.byref(to), mz.data_ptr(),
                                               _ptr(workspace), 0 if workspace is None else workspace.numel(),
@@ -219,6 +234,7 @@ def gat_attention_forward(csc, ft, el, er, slope, out, mz, workspace):
 def gat_attention_backward(csc, csr, ft, el, er, out, mz, dout, slope, d_ft, d_el, d_er, workspace):
     """Gradients of dgla_gat_attention_forward; `csr` = the out-edge CSR (rows = source nodes) of the same graph."""
     keep = []
+    _gat_same_dtype(ft, el, er, out, dout, d_ft, d_el, d_er)
     ts = [_tensor(t, keep) for t in (ft, el, er, out, dout, d_ft, d_el, d_er)]
     check_call(LIB.dgla_gat_attention_backward(ctypes.byref(csc), ctypes.byref(csr), _DTYPES[ft.dtype],
                                                ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),

@@ -92,6 +92,8 @@ LIB.dgla_edge_softmax_workspace_bytes.argtypes = [P(CSR), c_int, c_int64]
 LIB.dgla_edge_softmax_backward.restype = c_int
 LIB.dgla_edge_softmax_backward.argtypes = [P(CSR), c_int, P(Tensor), P(Tensor), P(Tensor),
                                            c_void_p, c_size_t, c_uint32, c_void_p]
+LIB.dgla_gat_attention_supported.restype = c_int
+LIB.dgla_gat_attention_supported.argtypes = [c_int, c_int64, c_int64]
 LIB.dgla_gat_attention_workspace_bytes.restype = c_size_t
 LIB.dgla_gat_attention_workspace_bytes.argtypes = [P(CSR), c_int64, c_int64]
 LIB.dgla_gat_attention_forward.restype = c_int

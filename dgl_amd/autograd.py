@@ -8,6 +8,7 @@ difference: edge softmax uses the fused forward / backward kernels on the GPU (t
 runs max-SpMM, sub-SDDMM, exp, sum-SpMM, div-SDDMM there, sparse.py:709-713).
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import edge_order as _eo
 from ._lib import DGLAMDError
@@ -333,7 +334,8 @@ class EdgeSoftmax(torch.autograd.Function):
 class GATAttention(torch.autograd.Function):
     """``out[v] = sum_{u->v} softmax_v(leaky_relu(el[u] + er[v])) ft[u]`` per head as one operator
     (csrc/gat_attention.hip).  Saved for the backward: the operands, ``out`` and the rows' softmax (max, normaliser) —
-    2 floats per (node, head); the attention weights are recomputed, no (E, H) tensor is kept."""
+    2 floats per (node, head), fp32 whatever the operands' dtype; the attention weights are recomputed, no (E, H) tensor
+    is kept.  Output and gradients carry the operands' dtype (fp32 / fp16 / bf16)."""
 
     @staticmethod
     def forward(ctx, gidx, ft, el, er, slope):
@@ -350,11 +352,12 @@ class GATAttention(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         gidx, slope = ctx.meta
         ft, el, er, out, mz = ctx.saved_tensors
         rel = gidx.relations[0]
-        dout = _eo.plain(dout).contiguous()
+        dout = _eo.plain(dout).to(ft.dtype).contiguous()
         d_ft, d_el, d_er = torch.empty_like(ft), torch.empty_like(el), torch.empty_like(er)
         ws = _gat_workspace(rel, ft.shape[1], ft.shape[2])
         _call_unit("dgl_amd._CAPI_GATAttentionBackward", rel, ("csc", "csr"), _nd(ft), _nd(el), _nd(er), _nd(out), _nd(mz),

@@ -980,6 +980,28 @@ static int seg_arrays_ok_fwd(std::initializer_list<const DGLArray*> arrs) {  // 
   }
   return 0;
 }
+// a required array that was not given (an EMPTY array — a block side without nodes — is given: it has a shape)
+static bool gat_missing(const DGLArray* t) {
+  if (!t || t->ndim == 0) return true;
+  if (t->data) return false;
+  for (int i = 0; i < t->ndim; ++i)
+    if (t->shape[i] == 0) return false;
+  return true;
+}
+static void gat_tensor(const DGLArray* a, TensorArg* out) {  // to_tensor that keeps the shape of an empty array
+  out->shape.assign(a->shape, a->shape + a->ndim);
+  out->t.data = a->data ? data_ptr(a) : nullptr;
+  out->t.ndim = a->ndim;
+  out->t.shape = out->shape.data();
+}
+// every array of a call carries the operands' element type; mz is fp32 always
+static int gat_same_dtype(const DGLArray* ft, std::initializer_list<const DGLArray*> arrs, const DGLArray* mz) {
+  for (const DGLArray* t : arrs)
+    if (t->dtype.code != ft->dtype.code || t->dtype.bits != ft->dtype.bits || t->dtype.lanes != ft->dtype.lanes)
+      return ffi_fail("gat_attention: mixed dtypes (ft, el, er, out, dout and the gradients share one element type)");
+  if (mz->dtype.code != 2 || mz->dtype.bits != 32) return ffi_fail("gat_attention: mz must be float32");
+  return 0;
+}
 // (g, heads, dim) -> bytes of scratch
 static Registrar r_gatw("dgl_amd._CAPI_GATAttentionWorkspaceBytes", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   void* h;
@@ -1004,18 +1026,18 @@ static Registrar r_gatf("dgl_amd._CAPI_GATAttentionForward", [](const FfiArgs& a
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
   if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
-  if (null_array(ft) || null_array(el) || null_array(er) || null_array(out) || null_array(mz))
+  if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
     return ffi_fail("gat_attention: ft / el / er / out / mz are required");
   if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
   dgla_dtype dt;
-  if (float_dtype(ft, &dt)) return -1;
+  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
   const dgla_csr csc = csr_of(g, g->csc, true);
   TensorArg tf, tl, tr, to;
-  to_tensor(ft, &tf);
-  to_tensor(el, &tl);
-  to_tensor(er, &tr);
-  to_tensor(out, &to);
-  return dgla_gat_attention_forward(&csc, dt, &tf.t, &tl.t, &tr.t, static_cast<float>(slope), &to.t, data_ptr(mz),
+  gat_tensor(ft, &tf);
+  gat_tensor(el, &tl);
+  gat_tensor(er, &tr);
+  gat_tensor(out, &to);
+  return dgla_gat_attention_forward(&csc, dt, &tf.t, &tl.t, &tr.t, static_cast<float>(slope), &to.t, mz->data ? data_ptr(mz) : nullptr,
                                     null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0], tls_stream);
 });
 // (g, ft, el, er, out, mz, dout, slope, d_ft, d_el, d_er, workspace)
@@ -1031,15 +1053,15 @@ static Registrar r_gatb("dgl_amd._CAPI_GATAttentionBackward", [](const FfiArgs& 
   UnitGraph* g = static_cast<UnitGraph*>(h);
   if (!g->csc.present || !g->csr.present) return ffi_fail("gat_attention backward needs the CSC and the CSR format");
   for (DGLArray* t : {ft, el, er, out, mz, dout, dft, del_, der})
-    if (null_array(t)) return ffi_fail("gat_attention backward: every tensor is required");
+    if (gat_missing(t)) return ffi_fail("gat_attention backward: every tensor is required");
   if (seg_arrays_ok_fwd({ft, el, er, out, mz, dout, dft, del_, der, ws})) return -1;
   dgla_dtype dt;
-  if (float_dtype(ft, &dt)) return -1;
+  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out, dout, dft, del_, der}, mz)) return -1;
   const dgla_csr csc = csr_of(g, g->csc, true), csr = csr_of(g, g->csr, false);
   TensorArg t[8];
   DGLArray* arrs[8] = {ft, el, er, out, dout, dft, del_, der};
-  for (int i = 0; i < 8; ++i) to_tensor(arrs[i], &t[i]);
-  return dgla_gat_attention_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, &t[3].t, data_ptr(mz), &t[4].t,
+  for (int i = 0; i < 8; ++i) gat_tensor(arrs[i], &t[i]);
+  return dgla_gat_attention_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, &t[3].t, mz->data ? data_ptr(mz) : nullptr, &t[4].t,
                                      static_cast<float>(slope), &t[5].t, &t[6].t, &t[7].t,
                                      null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0], tls_stream);
 });

@@ -24,6 +24,12 @@
 // all of one head since D is a power of two >= 4), the 64 / LPR groups take consecutive edges of the row, each with
 // U edges in flight, and merge their states by xor-shuffles at the end of the row.
 //
+// The paragraph above describes the fp32 kernels for D a power of two >= 4 (first half of this file, kept as they
+// were).  Every other accepted call — fp16 / bf16 operands, any head width whose row fits one wavefront, see
+// dgla_gat_attention_supported — runs the "wide" kernels of the second half: same decomposition, a lane owns V
+// elements of one head, a head is padded to a power-of-two number of lanes, all state is fp32 and 16-bit results are
+// rounded once, at the final store.
+//
 // HBM-bound: per edge one ft (or dout) row of H * D * 4 bytes + 4 * H bytes of el (or 16 * H of aux) + one index;
 // algorithmic bytes of the forward  E * (H*D*4 + H*4 + i) + N * (H*D*4 + 3*H*4) + (N + 1) * i.
 #include "../../include/dgl_amd.h"
@@ -99,16 +105,24 @@ __global__ __launch_bounds__(256) void gat_chunk_rows_kernel(const Idx* __restri
 }
 
 // rows without edges: zero their output rows (two outputs of widths wa / wb; either may be null)
-template <typename Idx>
+template <typename Idx, typename TA, typename TB>
 __global__ __launch_bounds__(256) void gat_zero_rows_kernel(const Idx* __restrict__ indptr, int64_t num_rows,
-                                                           float* __restrict__ a, int wa, float* __restrict__ b, int wb,
+                                                           TA* __restrict__ a, int wa, TB* __restrict__ b, int wb,
                                                            float fill_b0, float fill_b1) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= num_rows || indptr[r] != indptr[r + 1]) return;
   if (a)
-    for (int i = 0; i < wa; ++i) a[r * wa + i] = 0.f;
+    for (int i = 0; i < wa; ++i) a[r * wa + i] = from_acc<TA>(0.f);
   if (b)
-    for (int i = 0; i < wb; ++i) b[r * wb + i] = (i & 1) ? fill_b1 : fill_b0;
+    for (int i = 0; i < wb; ++i) b[r * wb + i] = from_acc<TB>((i & 1) ? fill_b1 : fill_b0);
+}
+
+// (an empty side launches nothing: a grid of 0 blocks is an error)
+template <typename Idx, typename TA, typename TB>
+void zero_rows(hipStream_t s, const Idx* indptr, int64_t n, TA* a, int wa, TB* b, int wb, float fill_b0, float fill_b1) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL((gat_zero_rows_kernel<Idx, TA, TB>), dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s,
+                     indptr, n, a, wa, b, wb, fill_b0, fill_b1);
 }
 
 template <int LOG2_LPR>
@@ -483,6 +497,464 @@ __global__ __launch_bounds__(64) void gat_sum_fixup_kernel(const int64_t* __rest
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// wide kernels: element type T in {float, f16_t, bf16_t} and any head width (dgla_gat_attention_supported)
+// ---------------------------------------------------------------------------------------------------------------
+// A lane owns V consecutive elements of one head (one naturally aligned load of V * sizeof(T) bytes), a head is
+// LPH = 1 << lph_log2 lanes of which ceil(D / V) are active, a row LPR = next_pow2(H * LPH) lanes:
+//     h = l >> lph_log2,  j = l & (LPH - 1),  col = h * D + j * V,  active = h < H && j * V < D.
+// Idle lanes hold zeros, so the xor butterfly over the LPH lanes of a head (head_sum) is the one of the fp32 kernels
+// above.  16-bit values are widened on load; m, z, the accumulators, every partial state, mz and aux are fp32, and the
+// only roundings to 16 bits are the stores of out, d_ft, d_el and d_er.
+template <typename T, typename Idx>
+struct WideArgs {
+  const Idx* indptr;
+  const Idx* indices;
+  int64_t num_rows, nnz, nchunks;
+  const int64_t* chunk_row;
+  int64_t* prow;
+  float* pval;
+  int ns;                      // floats per partial state
+  int H, D, HD, HDp, lph_log2;  // heads, width, H * D, H * D padded to 4, log2(LPH)
+  float slope;
+  const T* ft;
+  const T* el;
+  const T* er;
+  const T* dout;
+  T* out;
+  float* mz;
+  float* aux;
+  T* d_ft;
+  T* d_el;
+  T* d_er;
+};
+
+template <typename T, int V>
+__device__ __forceinline__ void load_slab(const T* __restrict__ src, float (&f)[V]) {
+  const VecT<T, V> v = *reinterpret_cast<const VecT<T, V>*>(src);
+#pragma unroll
+  for (int i = 0; i < V; ++i) f[i] = to_acc<T>(v.v[i]);
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_slab(T* __restrict__ dst, const float (&f)[V], float scale) {
+  VecT<T, V> v;
+#pragma unroll
+  for (int i = 0; i < V; ++i) v.v[i] = from_acc<T>(f[i] * scale);
+  *reinterpret_cast<VecT<T, V>*>(dst) = v;
+}
+
+// V floats of a partial state (16-byte pieces: states start on 16-byte boundaries and col is a multiple of V)
+template <int V>
+__device__ __forceinline__ void load_part(const float* __restrict__ src, float (&f)[V]) {
+  constexpr int W = V < 4 ? V : 4;
+#pragma unroll
+  for (int c = 0; c < V / W; ++c) {
+    const VecT<float, W> v = *reinterpret_cast<const VecT<float, W>*>(src + c * W);
+#pragma unroll
+    for (int i = 0; i < W; ++i) f[c * W + i] = v.v[i];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void store_part(float* __restrict__ dst, const float (&f)[V]) {
+  constexpr int W = V < 4 ? V : 4;
+#pragma unroll
+  for (int c = 0; c < V / W; ++c) {
+    VecT<float, W> v;
+#pragma unroll
+    for (int i = 0; i < W; ++i) v.v[i] = f[c * W + i];
+    *reinterpret_cast<VecT<float, W>*>(dst + c * W) = v;
+  }
+}
+
+template <int V>
+__device__ __forceinline__ float dotv(const float (&a)[V], const float (&b)[V]) {
+  float r = a[0] * b[0];
+#pragma unroll
+  for (int i = 1; i < V; ++i) r = __builtin_fmaf(a[i], b[i], r);
+  return r;
+}
+
+template <int V>
+__device__ __forceinline__ void wide_merge(float& m, float& z, float (&acc)[V], float m_o, float z_o, const float (&a_o)[V]) {
+  const float mn = m > m_o ? m : m_o;
+  const float a = m == mn ? 1.f : gat_exp(m - mn);
+  const float b = m_o == mn ? 1.f : gat_exp(m_o - mn);
+  z = z * a + z_o * b;
+#pragma unroll
+  for (int i = 0; i < V; ++i) acc[i] = acc[i] * a + a_o[i] * b;
+  m = mn;
+}
+
+// the lane map of one row group (see above)
+struct WideLane {
+  int h, col;
+  bool active, head_lane;
+};
+
+template <typename A>
+__device__ __forceinline__ WideLane wide_lane(const A& p, int l, int V) {
+  WideLane w;
+  const int h = l >> p.lph_log2, j = l & ((1 << p.lph_log2) - 1);
+  w.active = h < p.H && j * V < p.D;
+  w.h = w.active ? h : 0;
+  w.col = w.active ? h * p.D + j * V : 0;
+  w.head_lane = j == 0;
+  return w;
+}
+
+template <typename T, int V, typename Idx, int LOG2_LPR>
+__global__ __launch_bounds__(256) void gat_fwd_wide_kernel(const WideArgs<T, Idx> p) {
+  using GE = Geo<LOG2_LPR>;
+  constexpr int LPR = GE::LPR, G = GE::G, U = GE::U;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  if (c >= p.nchunks) return;
+  const int l = lane & (LPR - 1), g = lane >> LOG2_LPR;
+  const WideLane w = wide_lane(p, l, V);
+  const bool active = w.active;
+  const int h = w.h, col = w.col;
+  const int H = p.H, HD = p.HD;
+  const float ninf = -__builtin_huge_valf();
+  const int64_t p0 = c * kGatChunk;
+  const int64_t p1 = p0 + kGatChunk < p.nnz ? p0 + kGatChunk : p.nnz;
+  int64_t row = p.chunk_row[c];
+  int64_t rs = static_cast<int64_t>(p.indptr[row]), re = static_cast<int64_t>(p.indptr[row + 1]);
+  int64_t pos = p0;
+  while (pos < p1) {
+    while (re <= pos) {
+      ++row;
+      rs = re;
+      re = static_cast<int64_t>(p.indptr[row + 1]);
+    }
+    const int64_t b = re < p1 ? re : p1;
+    const float er_h = active ? to_acc<T>(p.er[row * H + h]) : 0.f;
+    float m = ninf, z = 0.f, acc[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[i] = 0.f;
+    for (int64_t base = pos; base < b; base += G * U) {
+      int64_t src[U];
+      bool ok[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int64_t j = base + k * G + g;
+        ok[k] = j < b && active;
+        src[k] = ok[k] ? static_cast<int64_t>(p.indices[j]) : 0;
+      }
+      float sv[U], f[U][V];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        sv[k] = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) f[k][i] = 0.f;
+        if (ok[k]) {
+          sv[k] = to_acc<T>(p.el[src[k] * H + h]);
+          load_slab<T, V>(p.ft + src[k] * HD + col, f[k]);
+        }
+      }
+      float bm = ninf;
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        float s = sv[k] + er_h;
+        s = s > 0.f ? s : s * p.slope;
+        sv[k] = ok[k] ? s : ninf;
+        bm = bm > sv[k] ? bm : sv[k];
+      }
+      const float mn = m > bm ? m : bm;
+      const float sc = m == mn ? 1.f : gat_exp(m - mn);
+      z *= sc;
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc[i] *= sc;
+      m = mn;
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const float pk = ok[k] ? gat_exp(sv[k] - mn) : 0.f;
+        z += pk;
+#pragma unroll
+        for (int i = 0; i < V; ++i) acc[i] = __builtin_fmaf(pk, f[k][i], acc[i]);
+      }
+    }
+#pragma unroll
+    for (int mk = LPR; mk < 64; mk <<= 1) {
+      const float m_o = __shfl_xor(m, mk, 64), z_o = __shfl_xor(z, mk, 64);
+      float a_o[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) a_o[i] = __shfl_xor(acc[i], mk, 64);
+      wide_merge<V>(m, z, acc, m_o, z_o, a_o);
+    }
+    const bool head_partial = pos > rs, tail_partial = re > p1;
+    if (head_partial || tail_partial) {
+      const int64_t slot = 2 * c + (head_partial ? 0 : 1);
+      float* pv = p.pval + slot * p.ns;
+      if (g == 0 && active) {
+        store_part<V>(pv + col, acc);
+        if (w.head_lane) {
+          pv[p.HDp + 2 * h] = m;
+          pv[p.HDp + 2 * h + 1] = z;
+        }
+      }
+      if (lane == 0) p.prow[slot] = row;
+    } else if (g == 0 && active) {
+      store_slab<T, V>(p.out + row * HD + col, acc, 1.f / z);
+      if (w.head_lane) {
+        p.mz[(row * H + h) * 2] = m;
+        p.mz[(row * H + h) * 2 + 1] = z;
+      }
+    }
+    pos = b;
+  }
+}
+
+template <typename T, int V, typename Idx>
+__global__ __launch_bounds__(64) void gat_fwd_wide_fixup_kernel(const WideArgs<T, Idx> p) {
+  const int64_t c = blockIdx.x;
+  const int64_t r = p.prow[2 * c + 1];
+  if (r < 0) return;
+  const WideLane w = wide_lane(p, static_cast<int>(threadIdx.x), V);
+  if (!w.active) return;  // no cross-lane operation below
+  const int h = w.h, col = w.col;
+  const float* pv = p.pval + (2 * c + 1) * p.ns;
+  float acc[V];
+  load_part<V>(pv + col, acc);
+  float m = pv[p.HDp + 2 * h], z = pv[p.HDp + 2 * h + 1];
+  for (int64_t cc = c + 1; cc < p.nchunks && p.prow[2 * cc] == r; ++cc) {
+    const float* qv = p.pval + (2 * cc) * p.ns;
+    float a_o[V];
+    load_part<V>(qv + col, a_o);
+    wide_merge<V>(m, z, acc, qv[p.HDp + 2 * h], qv[p.HDp + 2 * h + 1], a_o);
+  }
+  store_slab<T, V>(p.out + r * p.HD + col, acc, 1.f / z);
+  if (w.head_lane) {
+    p.mz[(r * p.H + h) * 2] = m;
+    p.mz[(r * p.H + h) * 2 + 1] = z;
+  }
+}
+
+// backward pass 1, wide: with x_e = <dout_v, ft_u>_h and l'_e = leaky_relu'(el_u + er_v) a row accumulates
+//     S1 = sum a_e x_e (= t),  S2 = sum l'_e a_e x_e,  S3 = sum l'_e a_e      (three plain sums, all fp32)
+// and d_er = S2 - S1 * S3.  t is NOT taken from the stored `out`: rounded to 16 bits it is off by up to one unit of
+// round-off of |out| while a (x - t) cancels, which put d_er 12-14 units off the fp64 gradient on hub rows.  The
+// record aux[v, h] = (er, m, 1/z, t) is published when the row is complete: here, or in the fix-up for crossing rows.
+template <typename T, int V, typename Idx, int LOG2_LPR>
+__global__ __launch_bounds__(256) void gat_bwd_dst_wide_kernel(const WideArgs<T, Idx> p) {
+  using GE = Geo<LOG2_LPR>;
+  constexpr int LPR = GE::LPR, G = GE::G, U = GE::U;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  if (c >= p.nchunks) return;
+  const int l = lane & (LPR - 1), g = lane >> LOG2_LPR;
+  const WideLane w = wide_lane(p, l, V);
+  const bool active = w.active;
+  const int h = w.h, col = w.col;
+  const int H = p.H, HD = p.HD;
+  const int64_t p0 = c * kGatChunk;
+  const int64_t p1 = p0 + kGatChunk < p.nnz ? p0 + kGatChunk : p.nnz;
+  int64_t row = p.chunk_row[c];
+  int64_t rs = static_cast<int64_t>(p.indptr[row]), re = static_cast<int64_t>(p.indptr[row + 1]);
+  int64_t pos = p0;
+  while (pos < p1) {
+    while (re <= pos) {
+      ++row;
+      rs = re;
+      re = static_cast<int64_t>(p.indptr[row + 1]);
+    }
+    const int64_t b = re < p1 ? re : p1;
+    float er_h = 0.f, m_h = 0.f, rz = 0.f, dO[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) dO[i] = 0.f;
+    if (active) {
+      er_h = to_acc<T>(p.er[row * H + h]);
+      m_h = p.mz[(row * H + h) * 2];
+      rz = 1.f / p.mz[(row * H + h) * 2 + 1];
+      load_slab<T, V>(p.dout + row * HD + col, dO);
+    }
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int64_t base = pos; base < b; base += G * U) {
+      int64_t src[U];
+      bool ok[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int64_t j = base + k * G + g;
+        ok[k] = j < b && active;
+        src[k] = ok[k] ? static_cast<int64_t>(p.indices[j]) : 0;
+      }
+      float sv[U], f[U][V];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        sv[k] = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) f[k][i] = 0.f;
+        if (ok[k]) {
+          sv[k] = to_acc<T>(p.el[src[k] * H + h]);
+          load_slab<T, V>(p.ft + src[k] * HD + col, f[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const float x = head_sum(dotv<V>(dO, f[k]), p.lph_log2);
+        const float pre = sv[k] + er_h;
+        const float s = pre > 0.f ? pre : pre * p.slope;
+        const float a = ok[k] ? gat_exp(s - m_h) * rz : 0.f;
+        const float la = a * (pre > 0.f ? 1.f : p.slope);
+        s1 = __builtin_fmaf(a, x, s1);
+        s2 = __builtin_fmaf(la, x, s2);
+        s3 += la;
+      }
+    }
+#pragma unroll
+    for (int mk = LPR; mk < 64; mk <<= 1) {
+      s1 += __shfl_xor(s1, mk, 64);
+      s2 += __shfl_xor(s2, mk, 64);
+      s3 += __shfl_xor(s3, mk, 64);
+    }
+    const bool head_partial = pos > rs, tail_partial = re > p1;
+    if (head_partial || tail_partial) {
+      const int64_t slot = 2 * c + (head_partial ? 0 : 1);
+      if (g == 0 && active && w.head_lane) {
+        float* pv = p.pval + slot * p.ns;
+        pv[h] = s1;
+        pv[H + h] = s2;
+        pv[2 * H + h] = s3;
+      }
+      if (lane == 0) p.prow[slot] = row;
+    } else if (g == 0 && active && w.head_lane) {
+      p.d_er[row * H + h] = from_acc<T>(s2 - s1 * s3);
+      *reinterpret_cast<F4*>(p.aux + (row * H + h) * 4) = F4{er_h, m_h, rz, s1};
+    }
+    pos = b;
+  }
+}
+
+template <typename T, typename Idx>
+__global__ __launch_bounds__(64) void gat_bwd_dst_wide_fixup_kernel(const WideArgs<T, Idx> p) {
+  const int64_t c = blockIdx.x;
+  const int64_t r = p.prow[2 * c + 1];
+  if (r < 0) return;
+  const int H = p.H;
+  for (int h = threadIdx.x; h < H; h += 64) {
+    const float* pv = p.pval + (2 * c + 1) * static_cast<int64_t>(p.ns);
+    float s1 = pv[h], s2 = pv[H + h], s3 = pv[2 * H + h];
+    for (int64_t cc = c + 1; cc < p.nchunks && p.prow[2 * cc] == r; ++cc) {
+      const float* qv = p.pval + (2 * cc) * static_cast<int64_t>(p.ns);
+      s1 += qv[h];
+      s2 += qv[H + h];
+      s3 += qv[2 * H + h];
+    }
+    p.d_er[r * H + h] = from_acc<T>(s2 - s1 * s3);
+    *reinterpret_cast<F4*>(p.aux + (r * H + h) * 4) =
+        F4{to_acc<T>(p.er[r * H + h]), p.mz[(r * H + h) * 2], 1.f / p.mz[(r * H + h) * 2 + 1], s1};
+  }
+}
+
+template <typename T, int V, typename Idx, int LOG2_LPR>
+__global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(const WideArgs<T, Idx> p) {
+  using GE = Geo<LOG2_LPR>;
+  constexpr int LPR = GE::LPR, G = GE::G, U = GE::U;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  if (c >= p.nchunks) return;
+  const int l = lane & (LPR - 1), g = lane >> LOG2_LPR;
+  const WideLane w = wide_lane(p, l, V);
+  const bool active = w.active;
+  const int h = w.h, col = w.col;
+  const int H = p.H, HD = p.HD;
+  const int64_t p0 = c * kGatChunk;
+  const int64_t p1 = p0 + kGatChunk < p.nnz ? p0 + kGatChunk : p.nnz;
+  int64_t row = p.chunk_row[c];
+  int64_t rs = static_cast<int64_t>(p.indptr[row]), re = static_cast<int64_t>(p.indptr[row + 1]);
+  int64_t pos = p0;
+  while (pos < p1) {
+    while (re <= pos) {
+      ++row;
+      rs = re;
+      re = static_cast<int64_t>(p.indptr[row + 1]);
+    }
+    const int64_t b = re < p1 ? re : p1;
+    float el_h = 0.f, f[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) f[i] = 0.f;
+    if (active) {
+      el_h = to_acc<T>(p.el[row * H + h]);
+      load_slab<T, V>(p.ft + row * HD + col, f);
+    }
+    float acc_el = 0.f, acc[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[i] = 0.f;
+    for (int64_t base = pos; base < b; base += G * U) {
+      int64_t dst[U];
+      bool ok[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const int64_t j = base + k * G + g;
+        ok[k] = j < b && active;
+        dst[k] = ok[k] ? static_cast<int64_t>(p.indices[j]) : 0;
+      }
+      F4 ax[U];
+      float dO[U][V];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        ax[k] = F4{0.f, 0.f, 1.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < V; ++i) dO[k][i] = 0.f;
+        if (ok[k]) {
+          ax[k] = *reinterpret_cast<const F4*>(p.aux + (dst[k] * H + h) * 4);
+          load_slab<T, V>(p.dout + dst[k] * HD + col, dO[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const float dA = head_sum(dotv<V>(dO[k], f), p.lph_log2);
+        const float pre = el_h + ax[k].x;
+        const float s = pre > 0.f ? pre : pre * p.slope;
+        const float a = ok[k] ? gat_exp(s - ax[k].y) * ax[k].z : 0.f;
+        acc_el += a * (dA - ax[k].w) * (pre > 0.f ? 1.f : p.slope);
+#pragma unroll
+        for (int i = 0; i < V; ++i) acc[i] = __builtin_fmaf(a, dO[k][i], acc[i]);
+      }
+    }
+#pragma unroll
+    for (int mk = LPR; mk < 64; mk <<= 1) {
+      acc_el += __shfl_xor(acc_el, mk, 64);
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc[i] += __shfl_xor(acc[i], mk, 64);
+    }
+    const bool head_partial = pos > rs, tail_partial = re > p1;
+    if (head_partial || tail_partial) {
+      const int64_t slot = 2 * c + (head_partial ? 0 : 1);
+      float* pv = p.pval + slot * p.ns;
+      if (g == 0 && active) {
+        store_part<V>(pv + col, acc);
+        if (w.head_lane) pv[p.HDp + h] = acc_el;
+      }
+      if (lane == 0) p.prow[slot] = row;
+    } else if (g == 0 && active) {
+      store_slab<T, V>(p.d_ft + row * HD + col, acc, 1.f);
+      if (w.head_lane) p.d_el[row * H + h] = from_acc<T>(acc_el);
+    }
+    pos = b;
+  }
+}
+
+// fix-up of pass 2, wide: elements [0, wa) of a state go to a[row, :], elements [off_b, off_b + wb) to b[row, :]
+template <typename T>
+__global__ __launch_bounds__(64) void gat_sum_wide_fixup_kernel(const int64_t* __restrict__ prow, const float* __restrict__ pval,
+                                                               int ns, int64_t nchunks, T* __restrict__ a, int wa, int off_b,
+                                                               T* __restrict__ b, int wb) {
+  const int64_t c = blockIdx.x;
+  const int64_t r = prow[2 * c + 1];
+  if (r < 0) return;
+  for (int i = threadIdx.x; i < wa + wb; i += 64) {
+    const int e = i < wa ? i : off_b + (i - wa);
+    float v = pval[(2 * c + 1) * static_cast<int64_t>(ns) + e];
+    for (int64_t cc = c + 1; cc < nchunks && prow[2 * cc] == r; ++cc) v += pval[(2 * cc) * static_cast<int64_t>(ns) + e];
+    if (i < wa)
+      a[r * wa + i] = from_acc<T>(v);
+    else
+      b[r * wb + (i - wa)] = from_acc<T>(v);
+  }
+}
+
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 int pad4(int x) { return (x + 3) & ~3; }  // partial states start on 16-byte boundaries
@@ -491,26 +963,56 @@ int64_t num_chunks(int64_t nnz) { return (nnz + kGatChunk - 1) / kGatChunk; }
 
 struct Shape {
   int H, D, HD, lph_log2, log2_lpr;
+  int V;        // elements per lane
+  bool legacy;  // fp32 with D a power of two >= 4: the 16-byte-slab kernels of the first half of this file
 };
 
-// heads H, per-head width D: D a power of two >= 4 and H * D <= 256 (one 16-byte slab per lane, <= 64 lanes per row)
-int shape_of(const dgla_tensor* ft, const dgla_tensor* el, const dgla_tensor* er, Shape* s) {
-  if (!ft || !el || !er || !ft->data || !el->data || !er->data) return gfail("gat_attention: ft / el / er are required");
+int next_pow2_log2(int64_t x) {
+  int lg = 0;
+  while ((int64_t{1} << lg) < x) ++lg;
+  return lg;
+}
+
+// The accepted set, stated once (include/dgl_amd.h): V = min(16 / s, largest power of two dividing D) elements per lane,
+// LPH = next_pow2(ceil(D / V)) lanes per head, and a row must fit one wavefront: H * LPH <= 64.
+bool accepted(dgla_dtype dtype, int64_t H, int64_t D, int* v_out, int* lph_log2_out) {
+  const int s = dtype == DGLA_F32 ? 4 : (dtype == DGLA_F16 || dtype == DGLA_BF16) ? 2 : 0;
+  if (s == 0 || H < 1 || D < 1 || H > 64 || D > 64 * 8) return false;
+  int V = 16 / s;
+  while (D % V) V >>= 1;
+  const int lg = next_pow2_log2((D + V - 1) / V);
+  if ((H << lg) > 64) return false;
+  if (v_out) *v_out = V;
+  if (lph_log2_out) *lph_log2_out = lg;
+  return true;
+}
+
+// a tensor argument that was given: empty tensors (a side without nodes) carry no data pointer
+bool present(const dgla_tensor* t) {
+  if (!t || t->ndim <= 0) return false;
+  if (t->data) return true;
+  for (int i = 0; i < t->ndim; ++i)
+    if (t->shape[i] == 0) return true;
+  return false;
+}
+
+int shape_of(dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el, const dgla_tensor* er, Shape* s) {
+  if (!present(ft) || !present(el) || !present(er)) return gfail("gat_attention: ft / el / er are required");
   if (ft->ndim != 3 || el->ndim != 3 || er->ndim != 3 || el->shape[2] != 1 || er->shape[2] != 1)
     return gfail("gat_attention: ft must be (N_src, H, D), el (N_src, H, 1), er (N_dst, H, 1)");
   const int64_t H = ft->shape[1], D = ft->shape[2];
   if (el->shape[1] != H || er->shape[1] != H || el->shape[0] != ft->shape[0])
     return gfail("gat_attention: head counts / node counts of ft, el, er differ");
-  if (D < 4 || (D & (D - 1)) != 0 || H < 1 || H * D > 256)
-    return gfail("gat_attention: needs D a power of two >= 4 and H * D <= 256 (use the composed operators otherwise)");
+  if (!accepted(dtype, H, D, &s->V, &s->lph_log2))
+    return gfail("gat_attention: needs fp32 / fp16 / bf16 operands with H * next_pow2(ceil(D / V)) <= 64, V = min(16 / "
+                 "sizeof(element), largest power of two dividing D) (dgla_gat_attention_supported; use the composed "
+                 "operators otherwise)");
   s->H = static_cast<int>(H);
   s->D = static_cast<int>(D);
   s->HD = static_cast<int>(H * D);
-  s->lph_log2 = 0;
-  while ((4 << s->lph_log2) < D) ++s->lph_log2;
-  int lanes = s->HD / 4, lg = 2;
-  while ((1 << lg) < lanes) ++lg;
-  s->log2_lpr = lg;
+  s->log2_lpr = next_pow2_log2(H << s->lph_log2);
+  if (s->log2_lpr < 2) s->log2_lpr = 2;  // narrowest instantiation: 4 lanes per row (lanes past the last head idle)
+  s->legacy = dtype == DGLA_F32 && D >= 4 && (D & (D - 1)) == 0;
   return 0;
 }
 
@@ -524,7 +1026,7 @@ struct Scratch {
 
 size_t scratch_bytes(int64_t nnz, int64_t num_dst, int H, int HD) {
   const int64_t nc = num_chunks(nnz);
-  return align256(8 * nc) + align256(16 * nc) + align256(sizeof(float) * 2 * nc * (HD + pad4(2 * H))) +
+  return align256(8 * nc) + align256(16 * nc) + align256(sizeof(float) * 2 * nc * (pad4(HD) + pad4(2 * H))) +
          align256(sizeof(float) * 4 * num_dst * H);
 }
 
@@ -537,7 +1039,7 @@ Scratch<Idx> carve(char* ws, int64_t nnz, int H, int HD) {
   s.prow = reinterpret_cast<int64_t*>(ws);
   ws += align256(16 * nc);
   s.pval = reinterpret_cast<float*>(ws);
-  ws += align256(sizeof(float) * 2 * nc * (HD + pad4(2 * H)));
+  ws += align256(sizeof(float) * 2 * nc * (pad4(HD) + pad4(2 * H)));
   s.aux = reinterpret_cast<float*>(ws);
   return s;
 }
@@ -558,7 +1060,7 @@ int forward_typed(const dgla_csr* csc, const Shape& sh, const float* ft, const f
                   float* out, float* mz, char* ws, hipStream_t s) {
   const int64_t nnz = csc->nnz, n = csc->num_rows;
   const Idx* indptr = static_cast<const Idx*>(csc->indptr);
-  hipLaunchKernelGGL(gat_zero_rows_kernel<Idx>, dim3(grid1(n)), dim3(256), 0, s, indptr, n, out, sh.HD, mz, 2 * sh.H, 0.f, 1.f);
+  zero_rows(s, indptr, n, out, sh.HD, mz, 2 * sh.H, 0.f, 1.f);
   if (nnz > 0) {
     const Scratch<Idx> sc = carve<Idx>(ws, nnz, sh.H, sh.HD);
     GatArgs<Idx> a{};
@@ -596,10 +1098,8 @@ int backward_typed(const dgla_csr* csc, const dgla_csr* csr, const Shape& sh, co
   const int64_t nnz = csc->nnz, n_dst = csc->num_rows, n_src = csr->num_rows;
   const Idx* ip_in = static_cast<const Idx*>(csc->indptr);
   const Idx* ip_out = static_cast<const Idx*>(csr->indptr);
-  hipLaunchKernelGGL(gat_zero_rows_kernel<Idx>, dim3(grid1(n_dst)), dim3(256), 0, s, ip_in, n_dst, d_er, sh.H,
-                     static_cast<float*>(nullptr), 0, 0.f, 0.f);
-  hipLaunchKernelGGL(gat_zero_rows_kernel<Idx>, dim3(grid1(n_src)), dim3(256), 0, s, ip_out, n_src, d_ft, sh.HD, d_el, sh.H,
-                     0.f, 0.f);
+  zero_rows(s, ip_in, n_dst, d_er, sh.H, static_cast<float*>(nullptr), 0, 0.f, 0.f);
+  zero_rows(s, ip_out, n_src, d_ft, sh.HD, d_el, sh.H, 0.f, 0.f);
   if (nnz > 0) {
     const Scratch<Idx> sc = carve<Idx>(ws, nnz, sh.H, sh.HD);
     GatArgs<Idx> a{};
@@ -647,12 +1147,148 @@ int backward_typed(const dgla_csr* csc, const dgla_csr* csr, const Shape& sh, co
   return 0;
 }
 
+// ---- wide kernels: host side ------------------------------------------------------------------------------------
+#define DGLA_GATW_DISPATCH(KERNEL, LG, ...)                                              \
+  switch (LG) {                                                                          \
+    case 2: hipLaunchKernelGGL((KERNEL<T, V, Idx, 2>), __VA_ARGS__); break;               \
+    case 3: hipLaunchKernelGGL((KERNEL<T, V, Idx, 3>), __VA_ARGS__); break;               \
+    case 4: hipLaunchKernelGGL((KERNEL<T, V, Idx, 4>), __VA_ARGS__); break;               \
+    case 5: hipLaunchKernelGGL((KERNEL<T, V, Idx, 5>), __VA_ARGS__); break;               \
+    default: hipLaunchKernelGGL((KERNEL<T, V, Idx, 6>), __VA_ARGS__); break;              \
+  }
+
+struct WidePtrs {
+  const void *ft, *el, *er, *dout;
+  void *out, *d_ft, *d_el, *d_er;
+  float* mz;
+};
+
+template <typename T, typename Idx>
+WideArgs<T, Idx> wide_args(const Shape& sh, const WidePtrs& q, int64_t nnz, const Scratch<Idx>& sc, float slope) {
+  WideArgs<T, Idx> a{};
+  a.nnz = nnz;
+  a.nchunks = num_chunks(nnz);
+  a.chunk_row = sc.chunk_row;
+  a.prow = sc.prow;
+  a.pval = sc.pval;
+  a.H = sh.H;
+  a.D = sh.D;
+  a.HD = sh.HD;
+  a.HDp = pad4(sh.HD);
+  a.lph_log2 = sh.lph_log2;
+  a.slope = slope;
+  a.ft = static_cast<const T*>(q.ft);
+  a.el = static_cast<const T*>(q.el);
+  a.er = static_cast<const T*>(q.er);
+  a.dout = static_cast<const T*>(q.dout);
+  a.out = static_cast<T*>(q.out);
+  a.mz = q.mz;
+  a.aux = sc.aux;
+  a.d_ft = static_cast<T*>(q.d_ft);
+  a.d_el = static_cast<T*>(q.d_el);
+  a.d_er = static_cast<T*>(q.d_er);
+  return a;
+}
+
+template <typename T, int V, typename Idx>
+int forward_wide_v(const dgla_csr* csc, const Shape& sh, const WidePtrs& q, float slope, char* ws, hipStream_t s) {
+  const int64_t nnz = csc->nnz, n = csc->num_rows;
+  const Idx* indptr = static_cast<const Idx*>(csc->indptr);
+  zero_rows(s, indptr, n, static_cast<T*>(q.out), sh.HD, q.mz, 2 * sh.H, 0.f, 1.f);
+  if (nnz > 0) {
+    const Scratch<Idx> sc = carve<Idx>(ws, nnz, sh.H, sh.HD);
+    WideArgs<T, Idx> a = wide_args<T, Idx>(sh, q, nnz, sc, slope);
+    a.indptr = indptr;
+    a.indices = static_cast<const Idx*>(csc->indices);
+    a.num_rows = n;
+    a.ns = a.HDp + pad4(2 * sh.H);
+    hipLaunchKernelGGL(gat_chunk_rows_kernel<Idx>, dim3(grid1(a.nchunks)), dim3(256), 0, s, indptr, n, a.nchunks,
+                       sc.chunk_row, sc.prow);
+    DGLA_GATW_DISPATCH(gat_fwd_wide_kernel, sh.log2_lpr, dim3(grid1(a.nchunks, 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gat_fwd_wide_fixup_kernel<T, V, Idx>), dim3(static_cast<unsigned>(a.nchunks)), dim3(64), 0, s, a);
+  }
+  DGLA_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T, int V, typename Idx>
+int backward_wide_v(const dgla_csr* csc, const dgla_csr* csr, const Shape& sh, const WidePtrs& q, float slope, char* ws,
+                    hipStream_t s) {
+  const int64_t nnz = csc->nnz, n_dst = csc->num_rows, n_src = csr->num_rows;
+  const Idx* ip_in = static_cast<const Idx*>(csc->indptr);
+  const Idx* ip_out = static_cast<const Idx*>(csr->indptr);
+  zero_rows(s, ip_in, n_dst, static_cast<T*>(q.d_er), sh.H, static_cast<T*>(nullptr), 0, 0.f, 0.f);
+  zero_rows(s, ip_out, n_src, static_cast<T*>(q.d_ft), sh.HD, static_cast<T*>(q.d_el), sh.H, 0.f, 0.f);
+  if (nnz > 0) {
+    const Scratch<Idx> sc = carve<Idx>(ws, nnz, sh.H, sh.HD);
+    WideArgs<T, Idx> a = wide_args<T, Idx>(sh, q, nnz, sc, slope);
+    // pass 1: rows = destination nodes; three sums per (row, head)
+    a.indptr = ip_in;
+    a.indices = static_cast<const Idx*>(csc->indices);
+    a.num_rows = n_dst;
+    a.ns = pad4(3 * sh.H);
+    hipLaunchKernelGGL(gat_chunk_rows_kernel<Idx>, dim3(grid1(a.nchunks)), dim3(256), 0, s, ip_in, n_dst, a.nchunks,
+                       sc.chunk_row, sc.prow);
+    DGLA_GATW_DISPATCH(gat_bwd_dst_wide_kernel, sh.log2_lpr, dim3(grid1(a.nchunks, 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gat_bwd_dst_wide_fixup_kernel<T, Idx>), dim3(static_cast<unsigned>(a.nchunks)), dim3(64), 0, s, a);
+    // pass 2: rows = source nodes
+    a.indptr = ip_out;
+    a.indices = static_cast<const Idx*>(csr->indices);
+    a.num_rows = n_src;
+    a.ns = a.HDp + pad4(sh.H);
+    hipLaunchKernelGGL(gat_chunk_rows_kernel<Idx>, dim3(grid1(a.nchunks)), dim3(256), 0, s, ip_out, n_src, a.nchunks,
+                       sc.chunk_row, sc.prow);
+    DGLA_GATW_DISPATCH(gat_bwd_src_wide_kernel, sh.log2_lpr, dim3(grid1(a.nchunks, 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gat_sum_wide_fixup_kernel<T>, dim3(static_cast<unsigned>(a.nchunks)), dim3(64), 0, s, sc.prow, sc.pval,
+                       a.ns, a.nchunks, a.d_ft, sh.HD, a.HDp, a.d_el, sh.H);
+  }
+  DGLA_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// V = 8 exists only for 16-bit elements (16-byte slabs)
+template <typename T, typename Idx>
+int wide_typed(bool backward, const dgla_csr* csc, const dgla_csr* csr, const Shape& sh, const WidePtrs& q, float slope,
+               char* ws, hipStream_t s) {
+#define DGLA_GATW_V(VV) \
+  return backward ? backward_wide_v<T, VV, Idx>(csc, csr, sh, q, slope, ws, s) : forward_wide_v<T, VV, Idx>(csc, sh, q, slope, ws, s)
+  if constexpr (sizeof(T) == 2) {
+    if (sh.V == 8) DGLA_GATW_V(8);
+  }
+  switch (sh.V) {
+    case 4: DGLA_GATW_V(4);
+    case 2: DGLA_GATW_V(2);
+    default: DGLA_GATW_V(1);
+  }
+#undef DGLA_GATW_V
+}
+
+int wide(bool backward, dgla_dtype dtype, const dgla_csr* csc, const dgla_csr* csr, const Shape& sh, const WidePtrs& q,
+         float slope, char* ws, hipStream_t s) {
+  const bool i32 = csc->idtype_bits == 32;
+  switch (dtype) {
+    case DGLA_F16:
+      return i32 ? wide_typed<f16_t, int32_t>(backward, csc, csr, sh, q, slope, ws, s)
+                 : wide_typed<f16_t, int64_t>(backward, csc, csr, sh, q, slope, ws, s);
+    case DGLA_BF16:
+      return i32 ? wide_typed<bf16_t, int32_t>(backward, csc, csr, sh, q, slope, ws, s)
+                 : wide_typed<bf16_t, int64_t>(backward, csc, csr, sh, q, slope, ws, s);
+    default:
+      return i32 ? wide_typed<float, int32_t>(backward, csc, csr, sh, q, slope, ws, s)
+                 : wide_typed<float, int64_t>(backward, csc, csr, sh, q, slope, ws, s);
+  }
+}
+
 }  // namespace
 }  // namespace dgla
 
 using namespace dgla;
 
 extern "C" {
+
+int dgla_gat_attention_supported(dgla_dtype dtype, int64_t heads, int64_t dim) {
+  return accepted(dtype, heads, dim, nullptr, nullptr) ? 1 : 0;
+}
 
 size_t dgla_gat_attention_workspace_bytes(const dgla_csr* csc, int64_t heads, int64_t dim) {
   if (!csc || csc->nnz <= 0 || heads <= 0 || dim <= 0) return 0;
@@ -662,10 +1298,9 @@ size_t dgla_gat_attention_workspace_bytes(const dgla_csr* csc, int64_t heads, in
 int dgla_gat_attention_forward(const dgla_csr* csc, dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el,
                                const dgla_tensor* er, float negative_slope, const dgla_tensor* out, void* mz,
                                void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !out || !out->data || !mz) return gfail("gat_attention_forward: csc / out / mz are required");
-  if (dtype != DGLA_F32) return gfail("gat_attention: fp32 operands only (use the composed operators otherwise)");
+  if (!csc || !present(out) || (!mz && csc->num_rows > 0)) return gfail("gat_attention_forward: csc / out / mz are required");
   Shape sh;
-  if (shape_of(ft, el, er, &sh)) return -1;
+  if (shape_of(dtype, ft, el, er, &sh)) return -1;
   if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return gfail("idtype must be int32 or int64");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows || out->ndim != 3 ||
       out->shape[0] != csc->num_rows || out->shape[1] != sh.H || out->shape[2] != sh.D)
@@ -674,6 +1309,15 @@ int dgla_gat_attention_forward(const dgla_csr* csc, dgla_dtype dtype, const dgla
     return gfail("gat_attention_forward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
+  if (!sh.legacy) {
+    WidePtrs q{};
+    q.ft = ft->data;
+    q.el = el->data;
+    q.er = er->data;
+    q.out = out->data;
+    q.mz = static_cast<float*>(mz);
+    return wide(false, dtype, csc, nullptr, sh, q, negative_slope, static_cast<char*>(workspace), s);
+  }
   const float *f = static_cast<const float*>(ft->data), *l = static_cast<const float*>(el->data),
               *r = static_cast<const float*>(er->data);
   return csc->idtype_bits == 32
@@ -688,22 +1332,41 @@ int dgla_gat_attention_backward(const dgla_csr* csc, const dgla_csr* csr, dgla_d
                                 const dgla_tensor* dout, float negative_slope, const dgla_tensor* d_ft,
                                 const dgla_tensor* d_el, const dgla_tensor* d_er, void* workspace, size_t workspace_bytes,
                                 void* hip_stream) {
-  if (!csc || !csr || !out || !dout || !d_ft || !d_el || !d_er || !mz || !out->data || !dout->data || !d_ft->data ||
-      !d_el->data || !d_er->data)
+  if (!csc || !csr || !present(out) || !present(dout) || !present(d_ft) || !present(d_el) || !present(d_er) ||
+      (!mz && csc->num_rows > 0))
     return gfail("gat_attention_backward: every tensor is required");
-  if (dtype != DGLA_F32) return gfail("gat_attention: fp32 operands only (use the composed operators otherwise)");
   Shape sh;
-  if (shape_of(ft, el, er, &sh)) return -1;
+  if (shape_of(dtype, ft, el, er, &sh)) return -1;
   if (csc->idtype_bits != csr->idtype_bits || (csc->idtype_bits != 32 && csc->idtype_bits != 64))
     return gfail("gat_attention_backward: the two CSRs must share one id type (int32 or int64)");
   if (csc->nnz != csr->nnz || csc->num_rows != csr->num_cols || csc->num_cols != csr->num_rows)
     return gfail("gat_attention_backward: csr is not the out-edge CSR of csc's graph");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows)
     return gfail("gat_attention_backward: tensor shapes do not match the graph");
+  for (const dgla_tensor* t : {out, dout})
+    if (t->ndim != 3 || t->shape[0] != csc->num_rows || t->shape[1] != sh.H || t->shape[2] != sh.D)
+      return gfail("gat_attention_backward: out / dout must be (N_dst, H, D)");
+  if (d_ft->ndim != 3 || d_ft->shape[0] != ft->shape[0] || d_ft->shape[1] != sh.H || d_ft->shape[2] != sh.D ||
+      d_el->ndim != 3 || d_el->shape[0] != el->shape[0] || d_el->shape[1] != sh.H || d_el->shape[2] != 1 ||
+      d_er->ndim != 3 || d_er->shape[0] != er->shape[0] || d_er->shape[1] != sh.H || d_er->shape[2] != 1)
+    return gfail("gat_attention_backward: d_ft / d_el / d_er must have the shapes of ft / el / er");
   if (csc->nnz > 0 && (!workspace || workspace_bytes < dgla_gat_attention_workspace_bytes(csc, sh.H, sh.D)))
     return gfail("gat_attention_backward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, d_ft->data);
+  if (!sh.legacy) {
+    WidePtrs q{};
+    q.ft = ft->data;
+    q.el = el->data;
+    q.er = er->data;
+    q.dout = dout->data;
+    q.out = out->data;
+    q.mz = const_cast<float*>(static_cast<const float*>(mz));
+    q.d_ft = d_ft->data;
+    q.d_el = d_el->data;
+    q.d_er = d_er->data;
+    return wide(true, dtype, csc, csr, sh, q, negative_slope, static_cast<char*>(workspace), s);
+  }
 #define DGLA_GAT_BWD(IDX)                                                                                         \
   backward_typed<IDX>(csc, csr, sh, static_cast<const float*>(ft->data), static_cast<const float*>(el->data),     \
                       static_cast<const float*>(er->data), static_cast<const float*>(out->data),                  \

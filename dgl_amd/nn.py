@@ -25,7 +25,9 @@ def gat_attention(graph, ft, el, er, negative_slope=0.2, fused=None, handoff=Fal
     """``out[v] = sum_{u->v} softmax_v(leaky_relu(el[u] + er[v])) * ft[u]`` per head.
 
     ft: (N_src, H, D); el: (N_src, H, 1); er: (N_dst, H, 1) -> (N_dst, H, D).  ``fused=None`` takes the one-pass kernel
-    (``dgl_amd.ops.gat_attention``) whenever it applies and the composed operators otherwise; ``fused=False`` forces the
+    (``dgl_amd.ops.gat_attention``) whenever it applies — fp32 / fp16 / bf16 operands of one dtype and any head width
+    with ``H * next_pow2(ceil(D / V)) <= 64``, ``V = min(16 / itemsize, largest power of two dividing D)``
+    (``dgl_amd.ops.gat_attention_applies``) — and the composed operators otherwise; ``fused=False`` forces the
     composition (the reference's own sequence, the parity yardstick); ``handoff=True`` runs the composition inside
     ``dgl_amd.edge_order_handoff()`` (opt-in: entering that scope installs edge_order's process-wide shims)."""
     from . import ops

@@ -10,6 +10,7 @@ import sys
 import torch
 
 from . import autograd as _F
+from . import _capi
 from ._lib import DGLAMDError
 
 __all__ = ["gspmm", "gsddmm", "edge_softmax", "copy_u", "copy_v", "copy_e", "gat_attention", "gat_attention_applies"]
@@ -150,9 +151,12 @@ def edge_softmax(graph, logits, eids=None, norm_by="dst"):
 
 # ---- GAT attention block as one operator ------------------------------------------------
 def gat_attention_applies(graph, ft, el, er):
-    """Whether the one-pass kernel takes this call: one relation with an in-edge CSC, fp32 operands on the GPU of
-    shapes (N_src, H, D), (N_src, H, 1), (N_dst, H, 1) with D a power of two >= 4 and H * D <= 256 (one 16-byte slab
-    per lane); anything else runs the composed operators (dgl_amd.nn.gat_attention)."""
+    """Whether the one-pass kernel takes this call: one relation with an in-edge CSC (and, when an operand needs a
+    gradient, an out-edge CSR, which the backward reads), fp32 / fp16 / bf16 operands of ONE dtype on the GPU of shapes
+    (N_src, H, D), (N_src, H, 1), (N_dst, H, 1) with (dtype, H, D) in the set of ``dgla_gat_attention_supported``
+    (include/dgl_amd.h): with V = min(16 / itemsize, largest power of two dividing D) elements per lane and
+    LPH = next_pow2(ceil(D / V)) lanes per head, H * LPH <= 64.  Anything else runs the composed operators
+    (dgl_amd.nn.gat_attention)."""
     gidx = graph._graph
     if gidx.number_of_etypes() != 1 or not gidx.relations[0].allowed("csc"):
         return False
@@ -160,10 +164,13 @@ def gat_attention_applies(graph, ft, el, er):
         return False
     if ft.dim() != 3 or el.dim() != 3 or er.dim() != 3 or el.shape[2] != 1 or er.shape[2] != 1:
         return False
-    if not (ft.dtype == el.dtype == er.dtype == torch.float32) or type(ft) is not torch.Tensor:
+    if not (ft.dtype == el.dtype == er.dtype) or type(ft) is not torch.Tensor:
+        return False
+    if (torch.is_grad_enabled() and (ft.requires_grad or el.requires_grad or er.requires_grad) and
+            not gidx.relations[0].allowed("csr")):
         return False
     h, d = int(ft.shape[1]), int(ft.shape[2])
-    return (ft.is_cuda and el.shape[1] == h and er.shape[1] == h and d >= 4 and d & (d - 1) == 0 and h * d <= 256 and
+    return (ft.is_cuda and el.shape[1] == h and er.shape[1] == h and _capi.gat_attention_supported(ft.dtype, h, d) and
             ft.shape[0] == el.shape[0] == graph.num_src_nodes() and er.shape[0] == graph.num_dst_nodes())
 
 
@@ -181,7 +188,9 @@ def _registered():
 def gat_attention(graph, ft, el, er, negative_slope=0.2):
     """``out[v] = sum_{u->v} softmax_v(leaky_relu(el[u] + er[v])) * ft[u]`` per head in ONE pass over the in-edges
     (csrc/gat_attention.hip): no (E, H) tensor is written or read; the backward recomputes the attention weights from
-    the per-row (max, sum) the forward saved.  The composition it replaces: gatconv.py:330-347."""
+    the per-row (max, sum) the forward saved.  The composition it replaces: gatconv.py:330-347.  Takes fp32 / fp16 /
+    bf16 operands of one dtype and every (H, D) of :func:`gat_attention_applies`; output and gradients carry the
+    operands' dtype, with fp32 state inside and one rounding at the final stores."""
     if not gat_attention_applies(graph, ft, el, er):
         raise DGLAMDError("gat_attention: the fused kernel does not take these operands (dgl_amd.nn.gat_attention "
                           "falls back to the composed operators)")

@@ -228,15 +228,28 @@ int dgla_edge_softmax_backward(const dgla_csr* csr, dgla_dtype dtype, const dgla
  * python/dgl/backend/pytorch/sparse.py:709-713, with a fused version left as a TODO at src/array/kernel.cc:313,331)
  * in one pass over the in-edges: no (E, H) tensor is written or read, so an edge-id map costs nothing.
  *   csc        in-edge CSR (rows = destination nodes); its `data` (edge-id map) is not read
- *   ft         (N_src, H, D) fp32;  el (N_src, H, 1);  er (N_dst, H, 1);  out (N_dst, H, D)
- *              D a power of two >= 4 and H * D <= 256, otherwise -1 (callers compose the four operators instead)
- *   mz         float [N_dst, H, 2]: the row's softmax maximum and normaliser, written by the forward and read by
- *              the backward, which recomputes the attention weights from them
+ *   ft         (N_src, H, D);  el (N_src, H, 1);  er (N_dst, H, 1);  out (N_dst, H, D): all of element type `dtype`
+ *   mz         float [N_dst, H, 2] WHATEVER `dtype` is: the row's softmax maximum and normaliser, written by the forward
+ *              and read by the backward, which recomputes the attention weights from them
+ * Accepted set (dgla_gat_attention_supported; anything else returns -1 and callers compose the four operators): with
+ * s = sizeof(element) (4 for DGLA_F32, 2 for DGLA_F16 / DGLA_BF16; DGLA_F64 is not taken),
+ *     V   = min(16 / s, largest power of two that divides D)      elements a lane owns (one aligned load of V * s bytes)
+ *     LPH = next_pow2(ceil(D / V))                                lanes per head, idle ones included
+ * the call is taken iff H >= 1, D >= 1 and H * LPH <= 64 (a row fits one wavefront).  For fp32 with D a power of two >= 4
+ * that is H * D <= 256; fp32 also takes e.g. D = 1..7, 12, 24, 40, 48, 96, D = 47 with H = 1, D = 100 with H <= 2; 16-bit
+ * operands take H * D up to 512 for D a multiple of 8 (H8 D64, H2 D256).
+ * 16-bit contract: every fp16 / bf16 value is widened on load; the running maximum, the normaliser, the accumulators, the
+ * partial states of rows that cross chunks, `mz` and the backward's per-node record are fp32; the ONLY roundings to 16
+ * bits are the final stores of out, d_ft, d_el and d_er (one round-to-nearest-even each).  The backward does not read
+ * `out`'s values for 16-bit operands (it forms <dout, out> itself, in fp32).  fp32 calls with D a power of two >= 4 run
+ * the same kernels, bit for bit, as before the set was widened.
  *   workspace  dgla_gat_attention_workspace_bytes(csc, H, D) bytes of device scratch (required when nnz > 0)
  * Backward: `csr` is the out-edge CSR (rows = source nodes) of the same graph; d_ft / d_el / d_er get the gradients
  * of ft / el / er for the upstream gradient `dout` (every row is written, rows without edges with zeros).
  * Rows without in-edges: out = 0.  Deterministic: no atomics, partial rows are merged in a fixed order.
  */
+/* 1 when the fused operator takes (dtype, heads, dim) — the rule above —, 0 otherwise.  Host-only: needs no GPU. */
+int dgla_gat_attention_supported(dgla_dtype dtype, int64_t heads, int64_t dim);
 size_t dgla_gat_attention_workspace_bytes(const dgla_csr* csc, int64_t heads, int64_t dim);
 int dgla_gat_attention_forward(const dgla_csr* csc, dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el,
                                const dgla_tensor* er, float negative_slope, const dgla_tensor* out, void* mz,
