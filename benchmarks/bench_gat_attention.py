@@ -13,9 +13,17 @@ hbm_roofline_evidence (the gathered operand exceeds the 256 MiB cache), a SHA-25
 both trees for the fp32 power-of-two controls) and the commit id given with --commit.
 
     python benchmarks/bench_gat_attention.py --commit $(git rev-parse --short HEAD) [--scale 1] [--reps 10]
+
+``--train`` times the TRAINING rows instead (profiles/r8/gat_attention_dropout.jsonl): forward and forward + backward at
+C3 and at C2 size, H8 D8 and H8 D32, fp32 and bf16, attention dropout p = 0.6, each three ways: ``fused_p0`` (the fused
+kernel without dropout, the control: it runs on a tree without the ``attn_drop`` keyword too, so this tree and its parent
+can alternate on one GPU), ``fused_drop`` (the fused kernel with the mask evaluated in registers, a fresh seed per call)
+and ``composed_drop`` (the four operators with ``F.dropout`` on the (E, H) weights).  A
+dropout pass reads the edge-id map once more than the byte model above: + E * i bytes per pass.
 """
 import argparse
 import hashlib
+import inspect
 import json
 import os
 import sys
@@ -134,15 +142,86 @@ def run(args):
         torch.cuda.empty_cache()
 
 
+TRAIN_CASES = [(t, 8, d) for t in ("fp32", "bf16") for d in (8, 32)]
+TRAIN_P = 0.6
+
+
+class _Seeds:
+    """A fresh seed per call without a generator draw inside the timed region: ``int(seed)`` counts up."""
+
+    def __init__(self):
+        self.n = 0
+
+    def __int__(self):
+        self.n += 1
+        return self.n
+
+
+def run_train(args):
+    import dgl_amd as dgl
+    from tests.graphgen import C2_EDGES, C2_NODES, synth_csr
+
+    dev = torch.device("cuda:0")
+    i = 4
+    routes = [("fused_p0", dict(fused=True), 0.0)]
+    if "attn_drop" in inspect.signature(dgl.nn.gat_attention).parameters:
+        routes += [("fused_drop", dict(fused=True, attn_drop=TRAIN_P, seed=_Seeds()), TRAIN_P),
+                   ("composed_drop", dict(fused=False, attn_drop=TRAIN_P), TRAIN_P)]
+    for size in ("C3", "C2size"):
+        if size == "C3":
+            n, e = C3_NODES, C3_EDGES
+            g = synth_csr(n, n, e, "U", seed=3, device=dev, with_eids=True)
+        else:
+            n, e = C2_NODES // args.scale, C2_EDGES // args.scale
+            g = synth_csr(n, n, e, "U", seed=20250824, device=dev)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(7)
+            g["eids"] = torch.randperm(e, device=dev, generator=gen).to(torch.int32)
+        dg = _dgl_graph(g, dev)
+        for tname, h, d in TRAIN_CASES:
+            dt = DTYPES[tname]
+            s = torch.finfo(dt).bits // 8
+            torch.manual_seed(h * 100 + d)
+            ps = [(torch.rand(n, h, d, device=dev) + 1).to(dt), torch.randn(n, h, 1, device=dev).to(dt),
+                  torch.randn(n, h, 1, device=dev).to(dt)]
+            up = torch.randn(n, h, d, device=dev).to(dt)
+            for route, kw, p in routes:
+                nb = e * (h * d * s + h * s + i + (i if p else 0)) + n * (h * d * s + 2 * h * 4) + (n + 1) * i
+                tag = "%s_H%d_D%d_eid_map_%s" % (tname, h, d, route)
+                common = dict(dtype=tname, heads=h, dim=d, route=route, p=p, fused=route != "composed_drop")
+                with torch.no_grad():
+                    out = dgl.nn.gat_attention(dg, ps[0], ps[1], ps[2], 0.2, **kw)
+                    t = _time(lambda: dgl.nn.gat_attention(dg, ps[0], ps[1], ps[2], 0.2, **kw), args.reps)
+                _emit(args, "gat_attention_train_fwd_%s_%s" % (size, tag), t, nb, e, n * h * d * s,
+                      sha256=None if p else _sha(out), **common)
+                del out
+                qs = [q.clone().requires_grad_(True) for q in ps]
+
+                def train():
+                    for q in qs:
+                        q.grad = None
+                    dgl.nn.gat_attention(dg, qs[0], qs[1], qs[2], 0.2, **kw).backward(up)
+
+                train()
+                sha = None if p else _sha(*[q.grad for q in qs])
+                t = _time(train, args.reps)
+                _emit(args, "gat_attention_train_fwd_bwd_%s_%s" % (size, tag), t, 3 * nb, e, n * h * d * s, sha256=sha, **common)
+                del qs
+            del ps, up
+        del dg, g
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--commit", default="unknown", help="commit id of the tree, copied into every line")
     ap.add_argument("--reps", type=int, default=10, help="timed calls per case (>= 10)")
     ap.add_argument("--scale", type=int, default=1, help="divide the C2-size graph by this")
     ap.add_argument("--composed", action="store_true", help="also time fused=False")
+    ap.add_argument("--train", action="store_true", help="time the training rows (attention dropout) instead")
     args = ap.parse_args()
     args.reps = max(10, args.reps)
-    run(args)
+    (run_train if args.train else run)(args)
     return 0
 
 

@@ -244,6 +244,57 @@ def gat_attention_backward(csc, csr, ft, el, er, out, mz, dout, slope, d_ft, d_e
                                                _stream(d_ft)))
 
 
+def gat_attention_train_forward(csc, ft, el, er, slope, p, seed, out, mz, workspace):
+    """dgla_gat_attention_train_forward: the forward above with dropout of probability `p` on the attention weights,
+    the mask a function of (seed, edge id, head) that is never stored; `mz` is the (max, normaliser) of the softmax
+    WITHOUT dropout, as gat_attention_forward writes it."""
+    keep = []
+    _gat_same_dtype(ft, el, er, out)
+    tf, tl, tr, to = (_tensor(t, keep) for t in (ft, el, er, out))
+    _require_gpu(mz)
+    if mz.dtype != torch.float32:
+        raise _lib.DGLAMDError("gat_attention: mz is fp32 whatever the operands' dtype")
+    check_call(LIB.dgla_gat_attention_train_forward(ctypes.byref(csc), _DTYPES[ft.dtype], ctypes.byref(tf), ctypes.byref(tl),
+                                                    ctypes.byref(tr), float(slope), float(p), int(seed), ctypes.byref(to),
+                                                    mz.data_ptr(), _ptr(workspace),
+                                                    0 if workspace is None else workspace.numel(), _stream(out)))
+
+
+def gat_attention_train_backward(csc, csr, ft, el, er, mz, dout, slope, p, seed, d_ft, d_el, d_er, workspace):
+    """Gradients of dgla_gat_attention_train_forward for the same (p, seed): the mask is evaluated again, from the
+    edge-id map of each CSR."""
+    keep = []
+    _gat_same_dtype(ft, el, er, dout, d_ft, d_el, d_er)
+    ts = [_tensor(t, keep) for t in (ft, el, er, dout, d_ft, d_el, d_er)]
+    check_call(LIB.dgla_gat_attention_train_backward(ctypes.byref(csc), ctypes.byref(csr), _DTYPES[ft.dtype],
+                                                     ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
+                                                     mz.data_ptr(), ctypes.byref(ts[3]), float(slope), float(p), int(seed),
+                                                     ctypes.byref(ts[4]), ctypes.byref(ts[5]), ctypes.byref(ts[6]),
+                                                     _ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                                     _stream(d_ft)))
+
+
+def gat_attention_weights(csc, el, er, mz, slope, p, seed, attn):
+    """attn[eid, h] = the post-dropout attention weight of every edge, (E, H, 1) in edge-id order, from the `mz` of a
+    forward on the same operands (dgla_gat_attention_weights)."""
+    keep = []
+    _gat_same_dtype(el, er, attn)
+    tl, tr, ta = (_tensor(t, keep) for t in (el, er, attn))
+    check_call(LIB.dgla_gat_attention_weights(ctypes.byref(csc), _DTYPES[el.dtype], ctypes.byref(tl), ctypes.byref(tr),
+                                              mz.data_ptr(), float(slope), float(p), int(seed), ctypes.byref(ta),
+                                              _stream(attn)))
+
+
+def gat_dropout_mask_host(seed, p, eids, heads):
+    """The keep mask of attention dropout for edge ids `eids` (a CPU int64 tensor) as a (len(eids), heads) uint8 CPU
+    tensor — the same gat_keep the kernels evaluate (dgla_gat_dropout_mask_host; needs no GPU)."""
+    eids = eids.to(device="cpu", dtype=torch.int64).contiguous()
+    keep = torch.empty((eids.numel(), int(heads)), dtype=torch.uint8)
+    check_call(LIB.dgla_gat_dropout_mask_host(int(seed), float(p), eids.data_ptr(), eids.numel(), int(heads),
+                                              keep.data_ptr()))
+    return keep
+
+
 def stream_copy(dst, src):
     _require_gpu(dst)
     check_call(LIB.dgla_stream_copy(dst.data_ptr(), src.data_ptr(),

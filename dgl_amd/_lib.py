@@ -103,6 +103,19 @@ LIB.dgla_gat_attention_backward.restype = c_int
 LIB.dgla_gat_attention_backward.argtypes = [P(CSR), P(CSR), c_int, P(Tensor), P(Tensor), P(Tensor), P(Tensor), c_void_p,
                                             P(Tensor), ctypes.c_float, P(Tensor), P(Tensor), P(Tensor), c_void_p,
                                             c_size_t, c_void_p]
+LIB.dgla_gat_attention_train_forward.restype = c_int
+LIB.dgla_gat_attention_train_forward.argtypes = [P(CSR), c_int, P(Tensor), P(Tensor), P(Tensor), ctypes.c_float,
+                                                 ctypes.c_float, ctypes.c_uint64, P(Tensor), c_void_p, c_void_p, c_size_t,
+                                                 c_void_p]
+LIB.dgla_gat_attention_train_backward.restype = c_int
+LIB.dgla_gat_attention_train_backward.argtypes = [P(CSR), P(CSR), c_int, P(Tensor), P(Tensor), P(Tensor), c_void_p,
+                                                  P(Tensor), ctypes.c_float, ctypes.c_float, ctypes.c_uint64, P(Tensor),
+                                                  P(Tensor), P(Tensor), c_void_p, c_size_t, c_void_p]
+LIB.dgla_gat_attention_weights.restype = c_int
+LIB.dgla_gat_attention_weights.argtypes = [P(CSR), c_int, P(Tensor), P(Tensor), c_void_p, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_uint64, P(Tensor), c_void_p]
+LIB.dgla_gat_dropout_mask_host.restype = c_int
+LIB.dgla_gat_dropout_mask_host.argtypes = [ctypes.c_uint64, ctypes.c_float, c_void_p, c_int64, c_int, c_void_p]
 LIB.dgla_spmm_set_profile_events.restype = c_int
 LIB.dgla_spmm_set_profile_events.argtypes = [c_void_p, c_void_p]
 LIB.dgla_segment_reduce_workspace_bytes.restype = c_size_t

@@ -365,6 +365,47 @@ class GATAttention(torch.autograd.Function):
         return None, d_ft, d_el, d_er, None
 
 
+class GATAttentionTrain(torch.autograd.Function):
+    """The training form of :class:`GATAttention` (csrc/gat_attention_train.hip): dropout with probability ``p`` on the
+    attention weights, the keep bit a function of (seed, edge id, head) that the forward evaluates in registers and the
+    backward evaluates again, so no mask and no (E, H) tensor is kept.  Saved: the operands, the rows' softmax (max,
+    normaliser) and the seed.  With ``want_attn`` the post-dropout weights come back as a second, non-differentiable
+    output, (E, H, 1) in edge-id order."""
+
+    @staticmethod
+    def forward(ctx, gidx, ft, el, er, slope, p, seed, want_attn):
+        rel = gidx.relations[0]
+        ft, el, er = ft.contiguous(), el.contiguous(), er.contiguous()
+        n_dst, (h, d) = rel.num_dst, ft.shape[1:]
+        out = torch.empty((n_dst, h, d), dtype=ft.dtype, device=ft.device)
+        mz = torch.empty((n_dst, h, 2), dtype=torch.float32, device=ft.device)
+        ws = _gat_workspace(rel, h, d)
+        _call_unit("dgl_amd._CAPI_GATAttentionTrainForward", rel, ("csc",), _nd(ft), _nd(el), _nd(er), float(slope), float(p),
+                   int(seed), _nd(out), _nd(mz), _nd(ws))
+        ctx.meta = (gidx, float(slope), float(p), int(seed))
+        ctx.save_for_backward(ft, el, er, mz)
+        if not want_attn:
+            return out
+        attn = torch.empty((rel.num_edges, h, 1), dtype=ft.dtype, device=ft.device)
+        _call_unit("dgl_amd._CAPI_GATAttentionWeights", rel, ("csc",), _nd(el), _nd(er), _nd(mz), float(slope), float(p),
+                   int(seed), _nd(attn))
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, *_):
+        gidx, slope, p, seed = ctx.meta
+        ft, el, er, mz = ctx.saved_tensors
+        rel = gidx.relations[0]
+        dout = _eo.plain(dout).to(ft.dtype).contiguous()
+        d_ft, d_el, d_er = torch.empty_like(ft), torch.empty_like(el), torch.empty_like(er)
+        ws = _gat_workspace(rel, ft.shape[1], ft.shape[2])
+        _call_unit("dgl_amd._CAPI_GATAttentionTrainBackward", rel, ("csc", "csr"), _nd(ft), _nd(el), _nd(er), _nd(mz),
+                   _nd(dout), slope, p, seed, _nd(d_ft), _nd(d_el), _nd(d_er), _nd(ws))
+        return None, d_ft, d_el, d_er, None, None, None, None
+
+
 def _nd(t):
     from . import _ffi
     return None if t is None else _ffi.NDArray(t)
@@ -393,10 +434,12 @@ def _gat_workspace(rel, heads, dim):
     return ws
 
 
-def gat_attention(gidx, ft, el, er, slope):
+def gat_attention(gidx, ft, el, er, slope, p=0.0, seed=0, want_attn=False):
     ft, el, er = _eo.plain(ft), _eo.plain(el), _eo.plain(er)
     with torch.autocast("cuda", enabled=False):
-        return GATAttention.apply(gidx, ft, el, er, slope)
+        if p == 0.0 and not want_attn:
+            return GATAttention.apply(gidx, ft, el, er, slope)
+        return GATAttentionTrain.apply(gidx, ft, el, er, slope, p, seed, want_attn)
 
 
 def _autocast(*tensors):

@@ -1065,6 +1065,90 @@ static Registrar r_gatb("dgl_amd._CAPI_GATAttentionBackward", [](const FfiArgs& 
                                      static_cast<float>(slope), &t[5].t, &t[6].t, &t[7].t,
                                      null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0], tls_stream);
 });
+// Training form (csrc/gat_attention_train.hip): attention dropout with probability p, mask keyed by (seed, edge id, head)
+// (g, ft, el, er, slope, p, seed, out, mz, workspace)
+static Registrar r_gattf("dgl_amd._CAPI_GATAttentionTrainForward", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  void* h;
+  DGLArray *ft, *el, *er, *out, *mz, *ws;
+  double slope, p;
+  int64_t seed;
+  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
+      get_float(a, 4, &slope) || get_float(a, 5, &p) || get_int(a, 6, &seed) || get_array(a, 7, &out) ||
+      get_array(a, 8, &mz) || get_array(a, 9, &ws))
+    return -1;
+  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
+    return ffi_fail("gat_attention: ft / el / er / out / mz are required");
+  if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
+  dgla_dtype dt;
+  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
+  const dgla_csr csc = csr_of(g, g->csc, true);
+  TensorArg tf, tl, tr, to;
+  gat_tensor(ft, &tf);
+  gat_tensor(el, &tl);
+  gat_tensor(er, &tr);
+  gat_tensor(out, &to);
+  return dgla_gat_attention_train_forward(&csc, dt, &tf.t, &tl.t, &tr.t, static_cast<float>(slope), static_cast<float>(p),
+                                          static_cast<uint64_t>(seed), &to.t, mz->data ? data_ptr(mz) : nullptr,
+                                          null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0],
+                                          tls_stream);
+});
+// (g, ft, el, er, mz, dout, slope, p, seed, d_ft, d_el, d_er, workspace)
+static Registrar r_gattb("dgl_amd._CAPI_GATAttentionTrainBackward", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  void* h;
+  DGLArray *ft, *el, *er, *mz, *dout, *dft, *del_, *der, *ws;
+  double slope, p;
+  int64_t seed;
+  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
+      get_array(a, 4, &mz) || get_array(a, 5, &dout) || get_float(a, 6, &slope) || get_float(a, 7, &p) ||
+      get_int(a, 8, &seed) || get_array(a, 9, &dft) || get_array(a, 10, &del_) || get_array(a, 11, &der) ||
+      get_array(a, 12, &ws))
+    return -1;
+  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (!g->csc.present || !g->csr.present) return ffi_fail("gat_attention backward needs the CSC and the CSR format");
+  for (DGLArray* t : {ft, el, er, mz, dout, dft, del_, der})
+    if (gat_missing(t)) return ffi_fail("gat_attention backward: every tensor is required");
+  if (seg_arrays_ok_fwd({ft, el, er, mz, dout, dft, del_, der, ws})) return -1;
+  dgla_dtype dt;
+  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, dout, dft, del_, der}, mz)) return -1;
+  const dgla_csr csc = csr_of(g, g->csc, true), csr = csr_of(g, g->csr, false);
+  TensorArg t[7];
+  DGLArray* arrs[7] = {ft, el, er, dout, dft, del_, der};
+  for (int i = 0; i < 7; ++i) gat_tensor(arrs[i], &t[i]);
+  return dgla_gat_attention_train_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, mz->data ? data_ptr(mz) : nullptr,
+                                           &t[3].t, static_cast<float>(slope), static_cast<float>(p),
+                                           static_cast<uint64_t>(seed), &t[4].t, &t[5].t, &t[6].t,
+                                           null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0],
+                                           tls_stream);
+});
+// (g, el, er, mz, slope, p, seed, attn): the post-dropout attention weights, (E, H, 1) in edge-id order
+static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  void* h;
+  DGLArray *el, *er, *mz, *attn;
+  double slope, p;
+  int64_t seed;
+  if (get_handle(a, 0, &h) || get_array(a, 1, &el) || get_array(a, 2, &er) || get_array(a, 3, &mz) ||
+      get_float(a, 4, &slope) || get_float(a, 5, &p) || get_int(a, 6, &seed) || get_array(a, 7, &attn))
+    return -1;
+  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (gat_missing(el) || gat_missing(er) || gat_missing(mz) || gat_missing(attn))
+    return ffi_fail("gat_attention_weights: el / er / mz / attn are required");
+  if (seg_arrays_ok_fwd({el, er, mz, attn})) return -1;
+  dgla_dtype dt;
+  if (float_dtype(el, &dt) || gat_same_dtype(el, {er, attn}, mz)) return -1;
+  const dgla_csr csc = csr_of(g, g->csc, true);
+  TensorArg tl, tr, ta;
+  gat_tensor(el, &tl);
+  gat_tensor(er, &tr);
+  gat_tensor(attn, &ta);
+  return dgla_gat_attention_weights(&csc, dt, &tl.t, &tr.t, mz->data ? data_ptr(mz) : nullptr, static_cast<float>(slope),
+                                    static_cast<float>(p), static_cast<uint64_t>(seed), &ta.t, tls_stream);
+});
 
 // ---- segment reduce family (src/array/kernel.cc:658-708) -------------------------------------
 static int seg_arrays_ok(std::initializer_list<const DGLArray*> arrs) {

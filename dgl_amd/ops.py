@@ -185,16 +185,47 @@ def _registered():
     return _registry_names[0]
 
 
-def gat_attention(graph, ft, el, er, negative_slope=0.2):
+def gat_attention(graph, ft, el, er, negative_slope=0.2, attn_drop=0.0, training=True, seed=None, get_attention=False):
     """``out[v] = sum_{u->v} softmax_v(leaky_relu(el[u] + er[v])) * ft[u]`` per head in ONE pass over the in-edges
     (csrc/gat_attention.hip): no (E, H) tensor is written or read; the backward recomputes the attention weights from
     the per-row (max, sum) the forward saved.  The composition it replaces: gatconv.py:330-347.  Takes fp32 / fp16 /
     bf16 operands of one dtype and every (H, D) of :func:`gat_attention_applies`; output and gradients carry the
-    operands' dtype, with fp32 state inside and one rounding at the final stores."""
+    operands' dtype, with fp32 state inside and one rounding at the final stores.
+
+    ``attn_drop`` (in [0, 1)) with ``training=True`` is GATConv's dropout on the attention weights
+    (``attn_drop(edge_softmax(graph, e))``, gatconv.py:337), inside the kernel (csrc/gat_attention_train.hip): the keep
+    bit is a function of (seed, edge id, head), evaluated in registers by the forward and again by the backward, so no
+    mask is stored.  ``seed=None`` draws one 63-bit integer from torch's default CPU generator — ``torch.manual_seed``
+    makes a run reproducible —, an explicit ``seed`` is used as given.  A call captured into a graph would replay ONE
+    mask, so under stream capture ``attn_drop > 0`` needs an explicit seed.  With ``attn_drop == 0`` or
+    ``training=False``, and ``get_attention=False``, this is the call without dropout: same kernels, same bits.
+    ``attn_drop`` outside [0, 1) raises ``DGLAMDError`` whatever ``training`` says: a layer configured with an
+    impossible rate is wrong in evaluation mode too.
+
+    ``get_attention=True`` returns ``(out, attn)``: ``attn`` is (E, H, 1), in edge-id order, AFTER dropout, as the
+    reference's ``get_attention`` returns it.  It is NOT differentiable (``requires_grad`` is False): gradients
+    through the attention tensor need the composed route, ``dgl_amd.nn.gat_attention(..., fused=False)``."""
+    p = float(attn_drop)
+    if not 0.0 <= p < 1.0:
+        raise DGLAMDError("gat_attention: attn_drop must lie in [0, 1), got %r" % (attn_drop,))
     if not gat_attention_applies(graph, ft, el, er):
         raise DGLAMDError("gat_attention: the fused kernel does not take these operands (dgl_amd.nn.gat_attention "
                           "falls back to the composed operators)")
-    return _F.gat_attention(graph._graph, ft, el, er, float(negative_slope))
+    if not training:
+        p = 0.0
+    if p == 0.0 and not get_attention:
+        return _F.gat_attention(graph._graph, ft, el, er, float(negative_slope))
+    if p == 0.0:
+        seed = 0
+    elif seed is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise DGLAMDError("gat_attention: attn_drop > 0 under stream capture needs an explicit seed — a captured "
+                              "call would replay one mask on every launch of the graph")
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 63:
+        raise DGLAMDError("gat_attention: seed must be an integer in [0, 2**63)")
+    return _F.gat_attention(graph._graph, ft, el, er, float(negative_slope), p, seed, bool(get_attention))
 
 
 # ---- generated aliases -----------------------------------------------------------------

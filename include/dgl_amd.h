@@ -260,6 +260,46 @@ int dgla_gat_attention_backward(const dgla_csr* csc, const dgla_csr* csr, dgla_d
                                 const dgla_tensor* d_el, const dgla_tensor* d_er, void* workspace,
                                 size_t workspace_bytes, void* hip_stream);
 
+/*
+ * Training form of the block above (csrc/gat_attention_train.hip): dropout on the attention weights, as GATConv's
+ *     a = attn_drop(edge_softmax(graph, e));   out[v, h, :] = sum_{u -> v} a_e,h * ft[u, h, :]
+ * (python/dgl/nn/pytorch/conv/gatconv.py:337-347), and the weights themselves on request.  No mask is stored:
+ * Keep rule (csrc/gat_dropout.h, gat_keep — ONE definition, compiled for the host and the device):
+ *     w    = Philox4x32-10(key = the 64-bit seed, counter = (eid low 32, eid high 32, head / 4, 0))[head % 4]
+ *     keep = (w >> 8) >= threshold,   threshold = (uint32_t)(p * 16777216.0),   kept weights are scaled by 1 / (1 - p)
+ *   threshold and the fp32 scale are computed once on the host from the float `p`, 0 <= p < 1 (anything else is an
+ *   error), and handed to the kernels as they are, so host and device agree bit for bit.
+ * Edge-id keying: eid = data ? data[pos] : pos of WHICHEVER CSR a kernel walks (csc in the forward, in pass 1 of the
+ *   backward and in dgla_gat_attention_weights, csr in pass 2 of the backward).  An edge therefore gets the same bit in
+ *   every pass and the mask does not depend on the sparse format; csc and csr must carry the edge-id maps of ONE graph
+ *   (a NULL `data` means edge id == position, as everywhere in this header).
+ * mz: exactly the mz of dgla_gat_attention_forward — the maximum and the normaliser of the softmax WITHOUT dropout —
+ *   so a row whose edges are all dropped gives out = 0, and the backward and the weights kernel recompute a from it.
+ * With c = keep / (1 - p), x_e = <dout_v, ft_u>_h and l'_e = leaky_relu'(el_u + er_v):
+ *     d_ft[u] = sum_e a c dout_v,   d_er[v] = S2 - S1 S3,   d_el[u] = sum_e l' a (c x - t_v),
+ *     S1 = t_v = sum a c x,  S2 = sum l' a c x,  S3 = sum l' a      (fp32 sums over the in-edges of v)
+ * Every accepted shape (dgla_gat_attention_supported, same workspace) runs the V-elements-per-lane scheme of the wide
+ * kernels — fp32 with D a power of two too, with V = 4 — with fp32 state and one rounding at the final store.  p = 0
+ * evaluates no Philox round.  No atomics; same chunk and fix-up order as above: deterministic for a given seed.
+ * dgla_gat_attention_weights writes attn[eid, h] = exp(leaky_relu(el[u, h] + er[v, h]) - m_v,h) / z_v,h * c_e,h for every
+ * edge, in EDGE-ID order, rounded once to `dtype`: attn is (E, H, 1) (or (E, H)); it needs mz of a forward on the same
+ * operands and no workspace.
+ * dgla_gat_dropout_mask_host: keep[i * heads + h] = gat_keep(seed, eids[i], h) as 0 / 1 bytes.  Host-only: needs no GPU.
+ */
+int dgla_gat_attention_train_forward(const dgla_csr* csc, dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el,
+                                     const dgla_tensor* er, float negative_slope, float p, uint64_t seed,
+                                     const dgla_tensor* out, void* mz, void* workspace, size_t workspace_bytes,
+                                     void* hip_stream);
+int dgla_gat_attention_train_backward(const dgla_csr* csc, const dgla_csr* csr, dgla_dtype dtype, const dgla_tensor* ft,
+                                      const dgla_tensor* el, const dgla_tensor* er, const void* mz, const dgla_tensor* dout,
+                                      float negative_slope, float p, uint64_t seed, const dgla_tensor* d_ft,
+                                      const dgla_tensor* d_el, const dgla_tensor* d_er, void* workspace,
+                                      size_t workspace_bytes, void* hip_stream);
+int dgla_gat_attention_weights(const dgla_csr* csc, dgla_dtype dtype, const dgla_tensor* el, const dgla_tensor* er,
+                               const void* mz, float negative_slope, float p, uint64_t seed, const dgla_tensor* attn,
+                               void* hip_stream);
+int dgla_gat_dropout_mask_host(uint64_t seed, float p, const int64_t* eids, int64_t n, int heads, uint8_t* keep);
+
 /* ---- segment reduce / scatter add ----------------------------------------
  * Replace SegmentReduce / ScatterAdd / BackwardSegmentCmp<kDGLCUDA,…>
  * (src/array/kernel_decl.h, kernels src/array/cuda/segment_reduce.cuh:30-113; registered as
