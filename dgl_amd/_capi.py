@@ -508,6 +508,70 @@ def coo_to_csr(row, col, eids, num_rows, num_minor=0):
     return indptr, indices, eids_out
 
 
+def csr_mm_row_classes():
+    """Term-count thresholds between the row classes of the sparse x sparse kernels, ascending (host query)."""
+    buf = (ctypes.c_int64 * 8)()
+    n = LIB.dgla_csr_mm_row_classes(buf, 8)
+    return [int(buf[i]) for i in range(n)]
+
+
+def csr_mm_workspace_bytes(a, b):
+    return LIB.dgla_csr_mm_workspace_bytes(ctypes.byref(a), ctypes.byref(b))
+
+
+def _ws(workspace):
+    return _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+
+
+def csr_mm(a, a_w, b, b_w, workspace=None):
+    """(indptr, indices, weights) of a . b (dgla_csr_mm_count + dgla_csr_mm_fill) on the current stream; `a` / `b` from
+    make_csr, weights 1-D per edge id.  The result's columns ascend in every row and it has no edge-id map."""
+    _require_gpu(a_w)
+    _require_gpu(b_w)
+    if a_w.dtype != b_w.dtype:
+        raise _lib.DGLAMDError("csr_mm: the weights must share one dtype")
+    idt = torch.int32 if a.idtype_bits == 32 else torch.int64
+    indptr = torch.empty(a.num_rows + 1, dtype=idt, device=a_w.device)
+    nnz = ctypes.c_int64(0)
+    wp, wb = _ws(workspace)
+    check_call(LIB.dgla_csr_mm_count(ctypes.byref(a), ctypes.byref(b), indptr.data_ptr(), ctypes.byref(nnz), wp, wb,
+                                     _stream(a_w)))
+    indices = torch.empty(nnz.value, dtype=idt, device=a_w.device)
+    w = torch.empty(nnz.value, dtype=a_w.dtype, device=a_w.device)
+    check_call(LIB.dgla_csr_mm_fill(ctypes.byref(a), _DTYPES[a_w.dtype], _ptr(a_w), ctypes.byref(b), _ptr(b_w),
+                                    indptr.data_ptr(), _ptr(indices), _ptr(w), wp, wb, _stream(a_w)))
+    return indptr, indices, w
+
+
+def csr_sum(ops, weights, workspace=None):
+    """(indptr, indices, weights) of the sum of the CSR operands `ops` (dgla_csr_sum_count + dgla_csr_sum_fill)."""
+    n = len(ops)
+    for t in weights:
+        _require_gpu(t)
+    arr = (ctypes.POINTER(_lib.CSR) * n)(*[ctypes.pointer(o) for o in ops])
+    wts = (ctypes.c_void_p * n)(*[_ptr(t) for t in weights])
+    idt = torch.int32 if ops[0].idtype_bits == 32 else torch.int64
+    dev = weights[0].device
+    indptr = torch.empty(ops[0].num_rows + 1, dtype=idt, device=dev)
+    nnz = ctypes.c_int64(0)
+    wp, wb = _ws(workspace)
+    check_call(LIB.dgla_csr_sum_count(arr, n, indptr.data_ptr(), ctypes.byref(nnz), wp, wb, _stream(weights[0])))
+    indices = torch.empty(nnz.value, dtype=idt, device=dev)
+    w = torch.empty(nnz.value, dtype=weights[0].dtype, device=dev)
+    check_call(LIB.dgla_csr_sum_fill(arr, n, _DTYPES[weights[0].dtype], wts, indptr.data_ptr(), _ptr(indices), _ptr(w),
+                                     wp, wb, _stream(weights[0])))
+    return indptr, indices, w
+
+
+def csr_mask(a, a_w, b_coo):
+    """out[e] = a[row_b[e], col_b[e]] or 0 (dgla_csr_mask); `a` from make_csr, `b_coo` from make_coo."""
+    _require_gpu(a_w)
+    out = torch.empty(b_coo.nnz, dtype=a_w.dtype, device=a_w.device)
+    check_call(LIB.dgla_csr_mask(ctypes.byref(a), _DTYPES[a_w.dtype], _ptr(a_w), ctypes.byref(b_coo), _ptr(out),
+                                 _stream(a_w)))
+    return out
+
+
 def sample_neighbors(csr, seeds, fanout, replace=False, rng_seed=0):
     """Uniform in-neighbour sampling over the in-edge CSR `csr` (dgla_sample_neighbors):
     returns ``(indptr, src, eids)`` — a CSR over the seeds with GLOBAL source / edge ids."""

@@ -181,6 +181,24 @@ LIB.dgla_coo_to_csr.argtypes = [c_int, c_int64, c_int64, c_void_p, c_void_p, c_v
 LIB.dgla_coo_to_csr_bounded.restype = c_int
 LIB.dgla_coo_to_csr_bounded.argtypes = [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_csr_mm_workspace_bytes.restype = c_size_t
+LIB.dgla_csr_mm_workspace_bytes.argtypes = [P(CSR), P(CSR)]
+LIB.dgla_csr_mm_count.restype = c_int
+LIB.dgla_csr_mm_count.argtypes = [P(CSR), P(CSR), c_void_p, P(c_int64), c_void_p, c_size_t, c_void_p]
+LIB.dgla_csr_mm_fill.restype = c_int
+LIB.dgla_csr_mm_fill.argtypes = [P(CSR), c_int, c_void_p, P(CSR), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]
+LIB.dgla_csr_mm_row_classes.restype = c_int
+LIB.dgla_csr_mm_row_classes.argtypes = [P(c_int64), c_int]
+LIB.dgla_csr_sum_workspace_bytes.restype = c_size_t
+LIB.dgla_csr_sum_workspace_bytes.argtypes = [P(P(CSR)), c_int]
+LIB.dgla_csr_sum_count.restype = c_int
+LIB.dgla_csr_sum_count.argtypes = [P(P(CSR)), c_int, c_void_p, P(c_int64), c_void_p, c_size_t, c_void_p]
+LIB.dgla_csr_sum_fill.restype = c_int
+LIB.dgla_csr_sum_fill.argtypes = [P(P(CSR)), c_int, c_int, P(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]
+LIB.dgla_csr_mask.restype = c_int
+LIB.dgla_csr_mask.argtypes = [P(CSR), c_int, c_void_p, P(COO), c_void_p, c_void_p]
 LIB.dgla_sample_neighbors_workspace_bytes.restype = c_size_t
 LIB.dgla_sample_neighbors_workspace_bytes.argtypes = [c_int, c_int64]
 LIB.dgla_sample_neighbors.restype = c_int

@@ -764,3 +764,94 @@ def edge_softmax_hetero(gidx, eids=None, norm_by="dst", *score):
     score = _autocast(*[None if t is None else _eo.plain(t) for t in score])
     with torch.autocast("cuda", enabled=False):
         return EdgeSoftmax_hetero.apply(gidx, eids, norm_by, *score)
+
+
+# ---------------------------------------------------------------------------------------
+# Sparse x sparse: CSRMM / CSRSum / CSRMask (python/dgl/backend/pytorch/sparse.py:869-966, wrappers :1137-1180).
+# The graph a forward returns is an ordinary Python object among the outputs; only the weights carry a gradient.
+# The two gradients of the product each form a full product and then mask it, like the reference; direct
+# masked-product kernels are listed in DESIGN.md §8.
+# ---------------------------------------------------------------------------------------
+def _grad_or_zeros(g, n, dtype, device):
+    return torch.zeros(n, dtype=dtype, device=device) if g is None else g.contiguous()
+
+
+class CSRMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gidxA, A_weights, gidxB, B_weights, num_vtypes):
+        from .sparse_kernels import _csrmm
+        gidxC, C_weights = _csrmm(gidxA, A_weights, gidxB, B_weights, num_vtypes)
+        ctx.backward_cache = gidxA, gidxB, gidxC
+        ctx.save_for_backward(A_weights, B_weights)
+        ctx.set_materialize_grads(False)
+        return gidxC, C_weights
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _dgidx, dC_weights):
+        from .sparse_kernels import _csrmask, _csrmm
+        gidxA, gidxB, gidxC = ctx.backward_cache
+        A_weights, B_weights = ctx.saved_tensors
+        dC = _grad_or_zeros(dC_weights, gidxC.num_edges(0), A_weights.dtype, A_weights.device)
+        dA = dB = None
+        if ctx.needs_input_grad[1]:   # dA = (dC . B^T) masked by A
+            g, w = _csrmm(gidxC, dC, gidxB.reverse(), B_weights.detach(), gidxA.number_of_ntypes())
+            dA = _csrmask(g, w, gidxA)
+        if ctx.needs_input_grad[3]:   # dB = (A^T . dC) masked by B
+            g, w = _csrmm(gidxA.reverse(), A_weights.detach(), gidxC, dC, gidxB.number_of_ntypes())
+            dB = _csrmask(g, w, gidxB)
+        return None, dA, None, dB, None
+
+
+class CSRSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gidxs, *weights):
+        from .sparse_kernels import _csrsum
+        gidxC, C_weights = _csrsum(gidxs, weights)
+        ctx.backward_cache = gidxs, gidxC
+        ctx.set_materialize_grads(False)
+        ctx.like = (weights[0].dtype, weights[0].device)
+        return gidxC, C_weights
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _dgidx, dC_weights):
+        from .sparse_kernels import _csrmask
+        gidxs, gidxC = ctx.backward_cache
+        dC = _grad_or_zeros(dC_weights, gidxC.num_edges(0), *ctx.like)
+        return (None,) + tuple(_csrmask(gidxC, dC, g) if need else None
+                               for g, need in zip(gidxs, ctx.needs_input_grad[1:]))
+
+
+class CSRMask(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gidxA, A_weights, gidxB):
+        from .sparse_kernels import _csrmask
+        ctx.backward_cache = gidxA, gidxB
+        return _csrmask(gidxA, A_weights, gidxB)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dB_weights):
+        from .sparse_kernels import _csrmask
+        gidxA, gidxB = ctx.backward_cache
+        return None, _csrmask(gidxB, dB_weights.contiguous(), gidxA), None
+
+
+def csrmm(gidxA, A_weights, gidxB, B_weights, num_vtypes):
+    """``(graph index of adj(A) . adj(B), its edge weights)``; differentiable in both weight tensors.  Simple graphs only."""
+    with torch.autocast("cuda", enabled=False):
+        return CSRMM.apply(gidxA, A_weights, gidxB, B_weights, num_vtypes)
+
+
+def csrsum(gidxs, weights):
+    """``(graph index of the sum of the adjacency matrices, its edge weights)``; differentiable in every weight tensor.
+    Simple graphs only."""
+    with torch.autocast("cuda", enabled=False):
+        return CSRSum.apply(list(gidxs), *weights)
+
+
+def csrmask(gidxA, A_weights, gidxB):
+    """Weights of A at the entries of B (0 where A has none), in B's edge-id order; differentiable in ``A_weights``."""
+    with torch.autocast("cuda", enabled=False):
+        return CSRMask.apply(gidxA, A_weights, gidxB)

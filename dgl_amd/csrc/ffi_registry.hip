@@ -1150,6 +1150,156 @@ static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& 
                                     static_cast<float>(p), static_cast<uint64_t>(seed), &ta.t, tls_stream);
 });
 
+// ---- sparse x sparse (csrc/csr_mm.hip; the reference's _CAPI_DGLCSRMM / CSRSum / CSRMask, src/array/kernel.cc:725-800) ----
+// The reference's three names return a graph object and an array the library owns; this registry allocates nothing, so
+// the product and the sum are a Count and a Fill over caller-allocated arrays.  Operands are unit-graph handles with
+// their CSR (rows = source nodes) registered — A->GetCSRMatrix(0) of kernel.cc:739-740 —, CSRMask's second operand
+// with its COO (kernel.cc:788).
+static int spgemm_csr(const FfiArgs& a, int i, dgla_csr* out) {
+  void* h;
+  if (get_handle(a, i, &h)) return -1;
+  if (!h || *static_cast<const uint32_t*>(h) != kMagicUnit) return ffi_fail("argument " + std::to_string(i) + ": not a unit graph");
+  const UnitGraph* g = static_cast<const UnitGraph*>(h);
+  if (!g->csr.present) return ffi_fail("csr_mm / csr_sum / csr_mask need the CSR format of their operands");
+  *out = csr_of(g, g->csr, false);
+  return 0;
+}
+static int spgemm_ids(const DGLArray* t, int bits, const char* name) {
+  if (!t || t->ndim == 0) return ffi_fail(std::string(name) + " is required");
+  if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+  if (check_contiguous(t, name)) return -1;
+  int b;
+  if (idbits_of(t, &b)) return -1;
+  if (b != bits) return ffi_fail(std::string(name) + " must have the id type of the operands");
+  return 0;
+}
+// weights: 1-D (or (n, 1)), one per edge
+static int spgemm_weights(const DGLArray* t, int64_t nnz, dgla_dtype* dt, const char* name) {
+  if (!t || t->ndim == 0) return ffi_fail(std::string(name) + " is required");
+  if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+  if (check_contiguous(t, name) || float_dtype(t, dt)) return -1;
+  if (t->ndim > 2 || (t->ndim == 2 && t->shape[1] != 1)) return ffi_fail(std::string(name) + " must be one scalar per edge (1-D)");
+  if (t->shape[0] != nnz)
+    return ffi_fail(std::string(name) + " has " + std::to_string(t->shape[0]) + " entries for " + std::to_string(nnz) + " edges");
+  return 0;
+}
+static void spgemm_ws(const DGLArray* ws, void** p, size_t* bytes) {
+  *p = null_array(ws) ? nullptr : data_ptr(ws);
+  *bytes = null_array(ws) ? 0 : static_cast<size_t>(ws->shape[0]);
+}
+// (gA, gB, c_indptr, workspace | null) -> nnz(C)
+static Registrar r_csrmmc("dgl_amd._CAPI_CSRMMCount", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
+  dgla_csr A, B;
+  DGLArray *ip, *ws;
+  if (spgemm_csr(a, 0, &A) || spgemm_csr(a, 1, &B) || get_array(a, 2, &ip) || get_array(a, 3, &ws)) return -1;
+  if (spgemm_ids(ip, A.idtype_bits, "c_indptr")) return -1;
+  if (ip->shape[0] != A.num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  void* w;
+  size_t wb;
+  spgemm_ws(ws, &w, &wb);
+  int64_t nnz = 0;
+  if (dgla_csr_mm_count(&A, &B, data_ptr(ip), &nnz, w, wb, tls_stream)) return -1;
+  *rtc = kObjectInt;
+  ret->v_int64 = nnz;
+  return 0;
+});
+// (gA, a_w, gB, b_w, c_indptr, c_indices, c_w, workspace | null)
+static Registrar r_csrmmf("dgl_amd._CAPI_CSRMMFill", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  dgla_csr A, B;
+  DGLArray *aw, *bw, *ip, *ix, *cw, *ws;
+  if (spgemm_csr(a, 0, &A) || get_array(a, 1, &aw) || spgemm_csr(a, 2, &B) || get_array(a, 3, &bw) || get_array(a, 4, &ip) ||
+      get_array(a, 5, &ix) || get_array(a, 6, &cw) || get_array(a, 7, &ws))
+    return -1;
+  dgla_dtype dt, dtb, dtc;
+  if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(bw, B.nnz, &dtb, "b_weights")) return -1;
+  if (spgemm_ids(ip, A.idtype_bits, "c_indptr") || spgemm_ids(ix, A.idtype_bits, "c_indices")) return -1;
+  if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
+  if (dt != dtb || dt != dtc) return ffi_fail("csr_mm: the weights of a, b and c must share one element type");
+  if (ip->shape[0] != A.num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  void* w;
+  size_t wb;
+  spgemm_ws(ws, &w, &wb);
+  return dgla_csr_mm_fill(&A, dt, aw->data ? data_ptr(aw) : nullptr, &B, bw->data ? data_ptr(bw) : nullptr, data_ptr(ip),
+                          ix->data ? data_ptr(ix) : nullptr, cw->data ? data_ptr(cw) : nullptr, w, wb, tls_stream);
+});
+// (n, g_0 .. g_{n-1}, c_indptr, workspace | null) -> nnz(C)
+static Registrar r_csrsumc("dgl_amd._CAPI_CSRSumCount", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
+  int64_t n;
+  if (get_int(a, 0, &n)) return -1;
+  if (n < 1 || n > 4096) return ffi_fail("csr_sum: the number of operands must be in [1, 4096]");
+  std::vector<dgla_csr> ops(n);
+  std::vector<const dgla_csr*> ptrs(n);
+  for (int k = 0; k < n; ++k) {
+    if (spgemm_csr(a, 1 + k, &ops[k])) return -1;
+    ptrs[k] = &ops[k];
+  }
+  DGLArray *ip, *ws;
+  if (get_array(a, 1 + n, &ip) || get_array(a, 2 + n, &ws)) return -1;
+  if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr")) return -1;
+  if (ip->shape[0] != ops[0].num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  void* w;
+  size_t wb;
+  spgemm_ws(ws, &w, &wb);
+  int64_t nnz = 0;
+  if (dgla_csr_sum_count(ptrs.data(), static_cast<int>(n), data_ptr(ip), &nnz, w, wb, tls_stream)) return -1;
+  *rtc = kObjectInt;
+  ret->v_int64 = nnz;
+  return 0;
+});
+// (n, g_0 .. g_{n-1}, w_0 .. w_{n-1}, c_indptr, c_indices, c_w, workspace | null)
+static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  int64_t n;
+  if (get_int(a, 0, &n)) return -1;
+  if (n < 1 || n > 4096) return ffi_fail("csr_sum: the number of operands must be in [1, 4096]");
+  std::vector<dgla_csr> ops(n);
+  std::vector<const dgla_csr*> ptrs(n);
+  std::vector<const void*> wts(n);
+  dgla_dtype dt = DGLA_F32;
+  for (int k = 0; k < n; ++k) {
+    if (spgemm_csr(a, 1 + k, &ops[k])) return -1;
+    ptrs[k] = &ops[k];
+  }
+  for (int k = 0; k < n; ++k) {
+    DGLArray* t;
+    dgla_dtype dk;
+    if (get_array(a, 1 + n + k, &t) || spgemm_weights(t, ops[k].nnz, &dk, "weights")) return -1;
+    if (k > 0 && dk != dt) return ffi_fail("csr_sum: the weights must share one element type");
+    dt = dk;
+    wts[k] = t->data ? data_ptr(t) : nullptr;
+  }
+  DGLArray *ip, *ix, *cw, *ws;
+  if (get_array(a, 1 + 2 * n, &ip) || get_array(a, 2 + 2 * n, &ix) || get_array(a, 3 + 2 * n, &cw) || get_array(a, 4 + 2 * n, &ws))
+    return -1;
+  dgla_dtype dtc;
+  if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr") || spgemm_ids(ix, ops[0].idtype_bits, "c_indices")) return -1;
+  if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
+  if (dtc != dt) return ffi_fail("csr_sum: the weights must share one element type");
+  if (ip->shape[0] != ops[0].num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  void* w;
+  size_t wb;
+  spgemm_ws(ws, &w, &wb);
+  return dgla_csr_sum_fill(ptrs.data(), static_cast<int>(n), dt, wts.data(), data_ptr(ip), ix->data ? data_ptr(ix) : nullptr,
+                           cw->data ? data_ptr(cw) : nullptr, w, wb, tls_stream);
+});
+// (gA, a_w, gB, out): out[e] = A[row_B[e], col_B[e]] or 0, e over B's edge ids
+static Registrar r_csrmask("dgl_amd._CAPI_CSRMask", [](const FfiArgs& a, DGLValue*, int* rtc) {
+  *rtc = kNull;
+  dgla_csr A;
+  void* hb;
+  DGLArray *aw, *out;
+  if (spgemm_csr(a, 0, &A) || get_array(a, 1, &aw) || get_handle(a, 2, &hb) || get_array(a, 3, &out)) return -1;
+  if (!hb || *static_cast<const uint32_t*>(hb) != kMagicUnit) return ffi_fail("argument 2: not a unit graph");
+  const UnitGraph* gb = static_cast<const UnitGraph*>(hb);
+  if (!gb->coo.present) return ffi_fail("csr_mask needs the COO format of its second operand");
+  const dgla_coo B = coo_of(gb);
+  dgla_dtype dt, dto;
+  if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(out, B.nnz, &dto, "out")) return -1;
+  if (dt != dto) return ffi_fail("csr_mask: a_weights and out must share one element type");
+  return dgla_csr_mask(&A, dt, aw->data ? data_ptr(aw) : nullptr, &B, out->data ? data_ptr(out) : nullptr, tls_stream);
+});
+
 // ---- segment reduce family (src/array/kernel.cc:658-708) -------------------------------------
 static int seg_arrays_ok(std::initializer_list<const DGLArray*> arrs) {
   for (const DGLArray* t : arrs) {

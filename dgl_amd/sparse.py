@@ -455,9 +455,12 @@ def bspmm(A, X):
 
 
 def spspmm(A, B):
-    """Sparse x sparse (matmul.py:88-129 -> spspmm.cc, cuSPARSE SpGEMM behind aten::CSRMM there).  Here: the rows of B
-    are gathered per nonzero of A (expand), the products keyed by (row, col), one stable sort, equal keys added
-    (compress).  Differentiable w.r.t. both value tensors; the result is coalesced."""
+    """Sparse x sparse (matmul.py:88-129 -> spspmm.cc, cuSPARSE SpGEMM behind aten::CSRMM there).  On the GPU with
+    float16 / bfloat16 / float32 / float64 values of one dtype and one id dtype: the library's CSRMM kernels
+    (csrc/csr_mm.hip — no host-side expansion, no vendor sort, a fixed order of additions) and their autograd.  Anything
+    else (CPU matrices, other value dtypes, mixed dtypes): the rows of B are gathered per nonzero of A (expand), the
+    products keyed by (row, col), one sort, equal keys added (compress).  Differentiable w.r.t. both value tensors; the
+    result is coalesced."""
     _is_sp(A, "arg1")
     _is_sp(B, "arg2")
     if A.shape[1] != B.shape[0]:
@@ -466,6 +469,16 @@ def spspmm(A, B):
         raise DGLAMDError("spspmm only supports scalar nonzero values")
     if A.has_duplicate() or B.has_duplicate():
         raise DGLAMDError("SpSpMM does not support sparse matrices with duplicate entries; call coalesce() first.")
+    if (A.device.type == "cuda" and B.device.type == "cuda" and A.val.dtype == B.val.dtype and
+            A.val.dtype in (torch.float32, torch.float64, torch.float16, torch.bfloat16) and
+            A._rel.idtype == B._rel.idtype):
+        from .autograd import csrmm
+        # the matrix' CSR is the in-edge CSR of its relation (column -> row): the reversed relation has it as out-edge CSR
+        ga = GraphIndex([A.shape[0], A.shape[1]], [(0, 1)], [A._rel.reverse()])
+        gb = GraphIndex([B.shape[0], B.shape[1]], [(0, 1)], [B._rel.reverse()])
+        gc, val = csrmm(ga, A.val, gb, B.val, 2)
+        indptr, indices, _ = gc.relations[0].csr()
+        return from_csr(indptr, indices, val, (A.shape[0], B.shape[1]))
     a_row, a_col = A.coo()
     b_ptr, b_col, b_vidx = B.csr()
     starts = b_ptr[a_col.long()].long()

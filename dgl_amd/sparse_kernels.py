@@ -538,3 +538,121 @@ def _update_grad_minmax_hetero(gidx, op, list_x, list_idx, list_idx_etype, list_
                  ["coo" if r.allowed("coo") else r.formats[0] for r in gidx.relations], op, nd(list_x),
                  nd(list_idx), nd(list_idx_etype), nd(list_out))
     return tuple(list_out)
+
+
+# ---------------------------------------------------------------------------------------
+# Sparse x sparse (python/dgl/_sparse_ops.py:802-886 ``_csrmm`` / ``_csrsum`` / ``_csrmask``) over
+# csrc/csr_mm.hip: count -> allocate -> fill, every array allocated here.
+# ---------------------------------------------------------------------------------------
+_SPGEMM_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def _spgemm_operand(gidx, weights, what, fmt="csr"):
+    """The one relation of ``gidx`` and its weights, checked: one edge type, on the GPU, ``fmt`` allowed, one scalar
+    weight per edge."""
+    if gidx.number_of_etypes() != 1:
+        raise DGLAMDError("{}: the graph must have only one edge type.".format(what))
+    rel = gidx.relations[0]
+    if rel.device.type != "cuda" or (weights is not None and not weights.is_cuda):
+        raise DGLAMDError("dgl_amd: tensors must live on a ROCm GPU (no CPU fallback)")
+    if not rel.allowed(fmt):
+        raise DGLAMDError("{}: the graph's formats are restricted and do not allow {}".format(what, fmt.upper()))
+    if weights is not None:
+        if weights.dim() != 1:
+            raise DGLAMDError("{}: edge weights must be scalar, i.e. a 1D tensor".format(what))
+        if weights.shape[0] != rel.num_edges:
+            raise DGLAMDError("{}: got {} weights for {} edges".format(what, weights.shape[0], rel.num_edges))
+        if weights.dtype not in _SPGEMM_DTYPES:
+            raise DGLAMDError("{}: edge weights must be float16 / bfloat16 / float32 / float64".format(what))
+        weights = weights.contiguous()
+    return rel, weights
+
+
+def _ws_nd(workspace):
+    return None if workspace is None else _ffi.NDArray(workspace)
+
+
+def _graph_from_csr(num_rows, num_cols, indptr, indices, num_vtypes, idtype, device):
+    """One-relation GraphIndex over a CSR without an edge-id map (edge id = CSR position)."""
+    from .graph_index import GraphIndex, Relation
+
+    if num_vtypes not in (1, 2):
+        raise DGLAMDError("num_vtypes must be either 1 or 2.")
+    rel = Relation(num_rows, num_cols, csr=(indptr, indices, None), idtype=idtype, device=device)
+    if num_vtypes == 1:
+        return GraphIndex([num_rows], [(0, 0)], [rel])
+    return GraphIndex([num_rows, num_cols], [(0, 1)], [rel])
+
+
+def _csrmm(A, A_weights, B, B_weights, num_vtypes, workspace=None):
+    """Graph whose adjacency matrix is adj(A) . adj(B), and its edge weights (python/dgl/_sparse_ops.py:802-832).
+
+    Both graphs must be simple graphs with one edge type on the GPU and share one id dtype; the weights are 1-D, one per
+    edge.  Returns ``(GraphIndex, weights)``: the result's CSR has no edge-id map (edge id = CSR position), its columns
+    ascend in every row, and an entry whose products cancel is kept with weight 0.  ``workspace``: optional uint8 device
+    tensor of ``dgla_csr_mm_workspace_bytes`` bytes; without it the library takes stream-ordered scratch."""
+    ra, wa = _spgemm_operand(A, A_weights, "csrmm")
+    rb, wb = _spgemm_operand(B, B_weights, "csrmm")
+    if ra.idtype != rb.idtype:
+        raise DGLAMDError("csrmm: the two graphs must have the same id dtype")
+    if wa.dtype != wb.dtype:
+        raise DGLAMDError("csrmm: the two weight tensors must have the same dtype")
+    if ra.num_dst != rb.num_src:
+        raise DGLAMDError("csrmm: the number of destination nodes of A ({}) must equal the number of source nodes of B "
+                          "({})".format(ra.num_dst, rb.num_src))
+    dev = ra.device
+    _ffi.use_current_stream(dev)
+    ha, hb = ra.handle("csr"), rb.handle("csr")
+    indptr = torch.empty(ra.num_src + 1, dtype=ra.idtype, device=dev)
+    nnz = _ffi.get_global_func("dgl_amd._CAPI_CSRMMCount")(ha, hb, _ffi.NDArray(indptr), _ws_nd(workspace))
+    indices = torch.empty(nnz, dtype=ra.idtype, device=dev)
+    w = torch.empty(nnz, dtype=wa.dtype, device=dev)
+    _ffi.get_global_func("dgl_amd._CAPI_CSRMMFill")(ha, _ffi.NDArray(wa), hb, _ffi.NDArray(wb), _ffi.NDArray(indptr),
+                                                  _ffi.NDArray(indices), _ffi.NDArray(w), _ws_nd(workspace))
+    return _graph_from_csr(ra.num_src, rb.num_dst, indptr, indices, num_vtypes, ra.idtype, dev), w
+
+
+def _csrsum(As, A_weights, workspace=None):
+    """Graph whose adjacency matrix is the sum of those of ``As``, and its edge weights
+    (python/dgl/_sparse_ops.py:835-857).  Simple graphs of one shape, one edge type, one id dtype, on the GPU; 1-D
+    weights.  One operand gives that operand with sorted columns and its weights permuted accordingly."""
+    if len(As) == 0:
+        raise DGLAMDError("csrsum: the list of graphs must not be empty")
+    if len(As) != len(A_weights):
+        raise DGLAMDError("csrsum: one weight tensor per graph is required")
+    ops = [_spgemm_operand(g, w, "csrsum") for g, w in zip(As, A_weights)]
+    r0, w0 = ops[0]
+    for r, w in ops[1:]:
+        if r.idtype != r0.idtype:
+            raise DGLAMDError("csrsum: the graphs must have the same id dtype")
+        if w.dtype != w0.dtype:
+            raise DGLAMDError("csrsum: the weight tensors must have the same dtype")
+        if (r.num_src, r.num_dst) != (r0.num_src, r0.num_dst):
+            raise DGLAMDError("csrsum: the graphs must have the same number of nodes")
+    dev = r0.device
+    _ffi.use_current_stream(dev)
+    handles = [r.handle("csr") for r, _ in ops]
+    n = len(ops)
+    indptr = torch.empty(r0.num_src + 1, dtype=r0.idtype, device=dev)
+    nnz = _ffi.get_global_func("dgl_amd._CAPI_CSRSumCount")(n, *handles, _ffi.NDArray(indptr), _ws_nd(workspace))
+    indices = torch.empty(nnz, dtype=r0.idtype, device=dev)
+    w = torch.empty(nnz, dtype=w0.dtype, device=dev)
+    _ffi.get_global_func("dgl_amd._CAPI_CSRSumFill")(n, *handles, *[_ffi.NDArray(x) for _, x in ops], _ffi.NDArray(indptr),
+                                                   _ffi.NDArray(indices), _ffi.NDArray(w), _ws_nd(workspace))
+    return _graph_from_csr(r0.num_src, r0.num_dst, indptr, indices, As[0].number_of_ntypes(), r0.idtype, dev), w
+
+
+def _csrmask(A, A_weights, B):
+    """Weights of A at the entries of B, in B's edge-id order; 0 where A has no such entry
+    (python/dgl/_sparse_ops.py:860-886).  A copy: no arithmetic.  A must be a simple graph."""
+    ra, wa = _spgemm_operand(A, A_weights, "csrmask")
+    rb, _ = _spgemm_operand(B, None, "csrmask", "coo")
+    if ra.idtype != rb.idtype:
+        raise DGLAMDError("csrmask: the two graphs must have the same id dtype")
+    if (ra.num_src, ra.num_dst) != (rb.num_src, rb.num_dst):
+        raise DGLAMDError("csrmask: both graphs must have the same number of nodes")
+    dev = ra.device
+    _ffi.use_current_stream(dev)
+    out = torch.empty(rb.num_edges, dtype=wa.dtype, device=dev)
+    _ffi.get_global_func("dgl_amd._CAPI_CSRMask")(ra.handle("csr"), _ffi.NDArray(wa), rb.handle("coo"), _ffi.NDArray(out))
+    return out

@@ -416,6 +416,47 @@ def in_subgraph(g, nodes, relabel_nodes=False, store_ids=True, output_device=Non
     return out.to(output_device) if output_device is not None else out
 
 
-__all__ = ["add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
+
+def adj_product_graph(A, B, weight_name, etype="_E"):
+    """Weighted graph whose adjacency matrix is ``adj(A) x adj(B)`` (rows = source nodes, columns = destination nodes;
+    transforms/functional.py:2564-2714).  Both graphs must be simple graphs (call :func:`to_simple` first otherwise) with
+    one edge type, on the GPU; the number of destination nodes of ``A`` must equal the number of source nodes of ``B``;
+    ``edata[weight_name]`` of both is one scalar per edge.  The result goes from ``A``'s source node type to ``B``'s
+    destination node type and is homogeneous when the two are the same; its edge type is ``etype`` and its weights are
+    in ``edata[weight_name]``, differentiable w.r.t. both inputs.  Unlike scipy, an edge whose weight sums to zero is
+    kept.  Edges are listed row by row with ascending destination ids.  If the formats are restricted both graphs must
+    allow CSR.  No int32 size limit applies (the reference's cuSPARSE restriction)."""
+    from .autograd import csrmm
+
+    _single(A, "adj_product_graph")
+    _single(B, "adj_product_graph")
+    srctype, _, _ = A.canonical_etypes[0]
+    _, _, dsttype = B.canonical_etypes[0]
+    num_vtypes = 1 if srctype == dsttype else 2
+    ntypes = [srctype] if num_vtypes == 1 else [srctype, dsttype]
+    C_gidx, C_weights = csrmm(A._graph, A.edata[weight_name], B._graph, B.edata[weight_name], num_vtypes)
+    C = DGLGraph(C_gidx, ntypes, [(srctype, etype, dsttype)])
+    C.edata[weight_name] = C_weights
+    return C
+
+
+def adj_sum_graph(graphs, weight_name):
+    """Weighted graph whose adjacency matrix is the sum of those of ``graphs`` (transforms/functional.py:2717-2821): simple
+    graphs with one edge type, the same node types and the same numbers of nodes, on the GPU.  The result has the
+    metagraph of the inputs and its weights in ``edata[weight_name]``, differentiable w.r.t. every input; an edge whose
+    weight sums to zero is kept.  If the formats are restricted every graph must allow CSR."""
+    from .autograd import csrsum
+
+    if len(graphs) == 0:
+        raise ValueError("The list of graphs must not be empty.")
+    for g in graphs:
+        _single(g, "adj_sum_graph")
+    C_gidx, C_weights = csrsum([g._graph for g in graphs], [g.edata[weight_name] for g in graphs])
+    C = DGLGraph(C_gidx, graphs[0].ntypes, graphs[0].canonical_etypes)
+    C.edata[weight_name] = C_weights
+    return C
+
+
+__all__ = ["adj_product_graph", "adj_sum_graph", "add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
            "node_subgraph", "edge_subgraph", "in_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
            "adj_external"]

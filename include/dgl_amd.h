@@ -446,6 +446,47 @@ int dgla_coo_to_csr_bounded(int idtype_bits, int64_t num_rows, int64_t num_minor
                             const void* col, const void* eids, void* indptr, void* indices, void* eids_out,
                             void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- sparse x sparse: CSRMM, CSRSum, CSRMask (csrc/csr_mm.hip) ------------------------------
+ * Replace aten::CSRMM / CSRSum / CSRGetData<kDGLCUDA> behind _CAPI_DGLCSRMM / _CAPI_DGLCSRSum /
+ * _CAPI_DGLCSRMask (src/array/kernel.cc:725-800; CPU kernels src/array/cpu/csr_mm.cc:20-130, csr_sum.cc; GPU kernels
+ * src/array/cuda/csr_mm.cu, csr_sum.cu over cusparseSpGEMM / csrgeam2).  Operands are CSR matrices of SIMPLE graphs (no
+ * duplicate column in a row, as the reference requires) with optional edge-id maps; weights are one scalar per edge,
+ * read as w[data ? data[pos] : pos] (csr_mm.cc:67-70).
+ *   C = A . B  (A: M x K, B: K x P)   /   C = A_0 + ... + A_{n-1}  (n >= 1 operands of one shape)
+ * Structure of C: the structural product / union — an entry exists wherever at least one term exists, also when the
+ * terms cancel to 0.0 ("Unlike scipy", python/dgl/transforms/functional.py:2583); C carries no edge-id map; the columns of a row ascend
+ * strictly; the same structure on every run.  Values: fp32 / fp64 in their own arithmetic; fp16 / bf16 are widened on
+ * load, multiplied and added in fp32 and rounded once at the store of c_w.  The terms of an entry are added in a fixed
+ * order (product: position order of A's row; sum: operand order): no floating-point atomics, same bits on every run.
+ * Term counts and nnz(C) are int64 inside; with int32 ids an nnz(C) above 2^31 - 1 is an error, with int64 ids there
+ * is no limit of the reference's 2^31 kind.  Zero sizes (M, K, P, nnz(A), nnz(B) == 0) are valid calls.
+ * Two calls around one workspace, every output allocated by the caller:
+ *   *_count  writes c_indptr [M + 1] and *nnz_out (HOST memory; reading it is the call's one synchronisation);
+ *   *_fill   writes c_indices / c_w [nnz(C)] for the c_indptr of a count on the same operands.
+ * `workspace` may be NULL (stream-ordered scratch for the duration of the call); the bound is a host computation from the
+ * row count alone — no path expands terms into global memory, so there is nothing to chunk.
+ * dgla_csr_mm_row_classes: the term-count thresholds between the row classes (one wavefront per row / one workgroup
+ * per row / dense accumulator over column windows), ascending; returns their number (2) and writes min(max, 2). */
+size_t dgla_csr_mm_workspace_bytes(const dgla_csr* a, const dgla_csr* b);
+int dgla_csr_mm_count(const dgla_csr* a, const dgla_csr* b, void* c_indptr, int64_t* nnz_out, void* workspace,
+                      size_t workspace_bytes, void* hip_stream);
+int dgla_csr_mm_fill(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dgla_csr* b, const void* b_w,
+                     const void* c_indptr, void* c_indices, void* c_w, void* workspace, size_t workspace_bytes,
+                     void* hip_stream);
+int dgla_csr_mm_row_classes(int64_t* bounds, int max);
+/* `ops`: HOST array of n operand descriptors; `weights`: HOST array of n device pointers (dgla_csr_sum_fill). */
+size_t dgla_csr_sum_workspace_bytes(const dgla_csr* const* ops, int n);
+int dgla_csr_sum_count(const dgla_csr* const* ops, int n, void* c_indptr, int64_t* nnz_out, void* workspace,
+                       size_t workspace_bytes, void* hip_stream);
+int dgla_csr_sum_fill(const dgla_csr* const* ops, int n, dgla_dtype dtype, const void* const* weights,
+                      const void* c_indptr, void* c_indices, void* c_w, void* workspace, size_t workspace_bytes,
+                      void* hip_stream);
+/* CSRMask (kernel.cc:775-800, CSRGetData with filler 0): out[eid(e)] = A[row_b[e], col_b[e]], or 0 where A has no such
+ * entry, for every entry e of the COO `b` (eid(e) = b.data ? b.data[e] : e); a copy, no arithmetic.  One group of 8
+ * lanes per query: bisection when the columns of A ascend strictly in every row (checked on the device in the same
+ * call), else a strided scan of the row in which the smallest matching position wins.  A or b without entries is valid. */
+int dgla_csr_mask(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dgla_coo* b, void* out, void* hip_stream);
+
 /* ---- uniform neighbour sampling and block construction -------------------
  * Replace CSRRowWiseSamplingUniform<kDGLCUDA> (src/array/cuda/rowwise_sampling.cu:43-330, behind
  * dgl.sampling.sample_neighbors) and ToBlock<kDGLCUDA> (src/graph/transform/cuda/cuda_to_block.cu,
