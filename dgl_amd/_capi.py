@@ -614,6 +614,86 @@ def sample_neighbors_weighted(csr, prob, seeds, fanout, replace=False, rng_seed=
     return indptr, src, eids
 
 
+def host_csr(indptr, indices, eids, num_cols):
+    """dgla_csr over CPU tensors, for the host-only entry points (dgla_random_walk_host)."""
+    for t in (indptr, indices, eids):
+        if t is not None and (t.is_cuda or not t.is_contiguous()):
+            raise _lib.DGLAMDError("host_csr takes contiguous CPU tensors")
+    c = CSR(indptr.shape[0] - 1, int(num_cols), indices.shape[0], _idbits(indptr), indptr.data_ptr(), _ptr(indices),
+            _ptr(eids))
+    c._keep = (indptr, indices, eids)
+    return c
+
+
+def random_walk_cdf(csr, prob):
+    """The row-wise inclusive sums of the weights of `csr` (dgla_random_walk_cdf): float64 [nnz] in CSR position order,
+    what the weighted step of :func:`random_walk` bisects.  `prob` is float32 / float64, one weight per EDGE ID."""
+    _require_gpu(prob)
+    if prob.dtype not in (torch.float32, torch.float64) or prob.dim() != 1 or not prob.is_contiguous():
+        raise _lib.DGLAMDError("prob must be a contiguous 1-D float32 / float64 tensor")
+    if prob.shape[0] != csr.nnz:
+        raise _lib.DGLAMDError("prob must hold one value per edge (%d), got %d" % (csr.nnz, prob.shape[0]))
+    cdf = torch.empty(csr.nnz, dtype=torch.float64, device=prob.device)
+    need = LIB.dgla_random_walk_cdf_workspace_bytes(ctypes.byref(csr))
+    ws = torch.empty(need, dtype=torch.uint8, device=prob.device) if need else None
+    check_call(LIB.dgla_random_walk_cdf(ctypes.byref(csr), prob.data_ptr(), _DTYPES[prob.dtype], cdf.data_ptr(),
+                                        _ptr(ws), need, _stream(prob)))
+    return cdf
+
+
+def _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, return_eids):
+    """The argument list the device and the host walker share; `rels` = [(dgla_csr, cdf tensor or None), ...]."""
+    table = (_lib.WalkRelation * max(1, len(rels)))()
+    for k, (csr, cdf) in enumerate(rels):
+        if cdf is not None and (cdf.dtype != torch.float64 or cdf.numel() != csr.nnz or not cdf.is_contiguous()):
+            raise _lib.DGLAMDError("a relation's cdf must be a contiguous float64 tensor with one entry per edge")
+        table[k].csr = ctypes.pointer(csr)
+        table[k].cdf = _ptr(cdf)
+    steps = len(metapath)
+    path = (ctypes.c_int32 * max(1, steps))(*[int(m) for m in metapath])
+    if restart_steps is not None:
+        if restart_steps.dtype not in (torch.float32, torch.float64) or restart_steps.dim() != 1 or \
+                restart_steps.shape[0] != steps or not restart_steps.is_contiguous():
+            raise _lib.DGLAMDError("restart_steps must be a contiguous float32 / float64 tensor with one entry per step")
+    n = seeds.shape[0]
+    traces = torch.empty((n, steps + 1), dtype=seeds.dtype, device=seeds.device)
+    eids = torch.empty((n, steps), dtype=seeds.dtype, device=seeds.device) if return_eids else None
+    args = [table if rels else None, len(rels), path, steps, seeds.data_ptr(), n, float(restart_prob or 0.0),
+            _ptr(restart_steps), _DTYPES[restart_steps.dtype] if restart_steps is not None else 0,
+            int(rng_seed) & 0xFFFFFFFFFFFFFFFF, traces.data_ptr(), _ptr(eids)]
+    return args, traces, eids, (table, path, rels)
+
+
+def random_walk(rels, metapath, seeds, restart_prob=0.0, restart_steps=None, rng_seed=0, return_eids=True):
+    """Random walks over the out-edge CSRs `rels` = [(dgla_csr, cdf or None), ...] along `metapath` (relation indices),
+    one walk per entry of `seeds` (dgla_random_walk).  Returns ``(traces [n, steps + 1], eids [n, steps] or None)``;
+    a walk that halts is padded with -1.  Nothing is read back."""
+    _require_gpu(seeds)
+    for t in [restart_steps] + [c for _, c in rels]:
+        if t is not None:
+            _require_gpu(t)
+    if not seeds.is_contiguous() or (rels and _idbits(seeds) != rels[0][0].idtype_bits):
+        raise _lib.DGLAMDError("seeds must be contiguous and of the relations' id type")
+    args, traces, eids, keep = _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, return_eids)
+    need = LIB.dgla_random_walk_workspace_bytes(len(rels), len(metapath))
+    ws = torch.empty(need, dtype=torch.uint8, device=seeds.device) if need else None
+    check_call(LIB.dgla_random_walk(*args, _ptr(ws), need, _stream(seeds)))
+    return traces, eids
+
+
+def random_walk_host(rels, metapath, seeds, restart_prob=0.0, restart_steps=None, rng_seed=0, return_eids=True):
+    """:func:`random_walk` run by the CPU on CPU tensors (dgla_random_walk_host; `rels` built with :func:`host_csr`):
+    the same step rule compiled for the host, bit for bit what the kernel writes.  Needs no GPU."""
+    for t in [seeds, restart_steps] + [c for _, c in rels]:
+        if t is not None and t.is_cuda:
+            raise _lib.DGLAMDError("random_walk_host takes CPU tensors")
+    if not seeds.is_contiguous() or (rels and _idbits(seeds) != rels[0][0].idtype_bits):
+        raise _lib.DGLAMDError("seeds must be contiguous and of the relations' id type")
+    args, traces, eids, keep = _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, return_eids)
+    check_call(LIB.dgla_random_walk_host(*args))
+    return traces, eids
+
+
 def to_block(seeds, src, node_map):
     """Block-local renumbering of `src` (dgla_to_block).  Returns ``(local_src, src_nodes,
     num_src)``; reading ``num_src`` back is the one host synchronisation of block building

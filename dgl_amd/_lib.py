@@ -46,6 +46,10 @@ class COO(ctypes.Structure):  # dgla_coo
                 ("data", c_void_p)]
 
 
+class WalkRelation(ctypes.Structure):  # dgla_walk_relation
+    _fields_ = [("csr", ctypes.POINTER(CSR)), ("cdf", c_void_p)]
+
+
 class Tensor(ctypes.Structure):  # dgla_tensor
     _fields_ = [("data", c_void_p), ("ndim", ctypes.c_int32),
                 ("shape", ctypes.POINTER(c_int64))]
@@ -220,6 +224,18 @@ LIB.dgla_sample_neighbors_padded.argtypes = [c_void_p, c_void_p, c_int, c_void_p
 LIB.dgla_to_block_padded.restype = c_int
 LIB.dgla_to_block_padded.argtypes = [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_random_walk_cdf_workspace_bytes.restype = c_size_t
+LIB.dgla_random_walk_cdf_workspace_bytes.argtypes = [P(CSR)]
+LIB.dgla_random_walk_cdf.restype = c_int
+LIB.dgla_random_walk_cdf.argtypes = [P(CSR), c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_random_walk_workspace_bytes.restype = c_size_t
+LIB.dgla_random_walk_workspace_bytes.argtypes = [c_int, c_int64]
+_WALK_ARGS = [P(WalkRelation), c_int, P(ctypes.c_int32), c_int64, c_void_p, c_int64, ctypes.c_double, c_void_p, c_int,
+              ctypes.c_uint64, c_void_p, c_void_p]
+LIB.dgla_random_walk.restype = c_int
+LIB.dgla_random_walk.argtypes = _WALK_ARGS + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_random_walk_host.restype = c_int
+LIB.dgla_random_walk_host.argtypes = _WALK_ARGS
 LIB.dgla_partition_kway_ex.restype = c_int
 LIB.dgla_partition_kway_ex.argtypes = [c_int, c_int64, c_void_p, c_void_p, c_int, ctypes.c_double, c_int, ctypes.c_uint64,
                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]

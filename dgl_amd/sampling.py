@@ -8,6 +8,9 @@ with their in-edge CSR already built (rows = seeds), i.e. in the format the SpMM
 round trip.  Graphs with several relations (round 5): ``nodes`` / ``fanout`` / ``dst_nodes`` are given per
 node / edge type as in the reference, every relation goes through the same two kernels, and a
 block keeps one source and one destination node set per node type (R-GCN mini-batches).
+
+``random_walk`` / ``pack_traces`` mirror ``dgl.sampling.random_walk`` / ``pack_traces``
+(python/dgl/sampling/randomwalks.py:31-310) over csrc/random_walk.hip: metapath, weighted and restart walks.
 """
 import torch
 
@@ -490,3 +493,109 @@ class NeighborSampler:
             seeds, nv = src_nodes, num_src
         self.counter += 1
         return seeds, nv, output_nodes, blocks
+
+
+# ---- random walks ------------------------------------------------------------------------------
+def _walk_cdf(rel, csr, w):
+    """The CDF of relation ``rel`` under the edge weights ``w``: built on first use and kept in ONE slot on the
+    relation, keyed by the weight tensor's address, ``_version``, shape, dtype and device and checked at every use (as
+    ``static_features`` checks its promise), so an in-place write to the weights rebuilds it."""
+    key = (w.data_ptr(), w._version, tuple(w.shape), w.dtype, w.device)
+    slot = getattr(rel, "_walk_cdf", None)
+    if slot is None or slot[0] != key:
+        p = (w if w.dtype in (torch.float32, torch.float64) else w.float()).contiguous().reshape(-1)
+        slot = rel._walk_cdf = (key, _capi.random_walk_cdf(csr, p))
+    return slot[1]
+
+
+def _walk_plan(g, metapath, length):
+    """``(edge type ids, node type id of every trace column)`` of a walk, with the reference's argument errors
+    (randomwalks.py:170-184); a metapath whose node types do not chain is refused here, before any launch.  Host work."""
+    if metapath is None:
+        if len(g.canonical_etypes) > 1 or len(g.ntypes) > 1:
+            raise _DGLError("metapath not specified and the graph is not homogeneous.")
+        if length is None:
+            raise ValueError("Please specify either the metapath or the random walk length.")
+        metapath = [0] * int(length)
+    else:
+        metapath = [g.get_etype_id(e) for e in metapath]
+    meta = g._graph.metagraph
+    for t in range(1, len(metapath)):
+        if meta.find_edge(metapath[t - 1])[1] != meta.find_edge(metapath[t])[0]:
+            raise _DGLError("metapath does not chain: edge type %s ends in node type '%s', edge type %s starts from '%s'"
+                            % (g.canonical_etypes[metapath[t - 1]], g.canonical_etypes[metapath[t - 1]][2],
+                               g.canonical_etypes[metapath[t]], g.canonical_etypes[metapath[t]][0]))
+    if metapath:
+        types = [meta.find_edge(metapath[0])[0]] + [meta.find_edge(m)[1] for m in metapath]
+    elif len(g.ntypes) == 1:
+        types = [0]
+    else:
+        raise _DGLError("an empty metapath does not say which node type the walks start from")
+    return metapath, types
+
+
+def random_walk(g, nodes, *, metapath=None, length=None, prob=None, restart_prob=None, return_eids=False, seed=None):
+    """``dgl.sampling.random_walk`` (python/dgl/sampling/randomwalks.py:31-226): one walk per entry of ``nodes`` along
+    ``metapath`` (edge types; default ``length`` steps of the only edge type).  ``prob`` names an edge feature of
+    unnormalised weights (relations that lack it walk uniformly; zero, negative and NaN weights are never taken),
+    ``restart_prob`` is a float (the same halting probability before every step) or a tensor with one entry per step.
+    Returns ``(traces, types)`` or ``(traces, eids, types)``: ``traces`` is ``(len(nodes), steps + 1)`` with -1 after a
+    walk halted (no out-edge, or a restart draw), ``eids`` ``(len(nodes), steps)``, ``types`` the node type id of every
+    column.  ``seed=None`` draws the call's seed from torch's generator (``torch.manual_seed`` makes a run
+    reproducible); an integer pins the walks, whatever the launch geometry (the step rule: include/dgl_amd.h)."""
+    metapath, types = _walk_plan(g, metapath, length)
+    restart_steps, restart_scalar = None, 0.0
+    if restart_prob is None:
+        pass
+    elif torch.is_tensor(restart_prob):
+        restart_steps = restart_prob
+        if restart_steps.dim() != 1 or restart_steps.shape[0] != len(metapath):
+            raise _DGLError("restart_prob must hold one entry per step (%d), got shape %s"
+                            % (len(metapath), tuple(restart_steps.shape)))
+    elif isinstance(restart_prob, float):
+        restart_scalar = restart_prob
+    else:
+        raise TypeError("restart_prob should be float or Tensor.")
+    if torch.is_tensor(nodes) and nodes.dtype != g.idtype:
+        raise _DGLError("Expect argument \"nodes\" to have data type %s. But got %s." % (g.idtype, nodes.dtype))
+    dev, idt = g.device, g.idtype
+    # only the relations the metapath uses enter the table (their formats and CDFs are built on first use)
+    used = sorted(set(metapath)) or [0]
+    table = []
+    for etid in used:
+        rel = g._graph.relations[etid]
+        fmt = rel.csr()
+        csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst)    # (refuses a CPU graph: no CPU fallback)
+        cdf = None
+        if prob is not None and prob in g._edge_frames[etid]:
+            w = g._edge_frames[etid][prob]
+            if w.dim() == 0 or w.shape[0] != rel.num_edges or w.numel() != rel.num_edges:
+                raise _DGLError("random_walk: prob must hold one value per edge of the relation (%d), got shape %s"
+                                % (rel.num_edges, tuple(w.shape)))
+            cdf = _walk_cdf(rel, csr, w.to(dev))
+        table.append((csr, cdf))
+    nodes = torch.as_tensor(nodes).reshape(-1).to(device=dev, dtype=idt).contiguous()
+    if restart_steps is not None:
+        restart_steps = restart_steps.to(dev)
+        if restart_steps.dtype not in (torch.float32, torch.float64):
+            restart_steps = restart_steps.float()
+        restart_steps = restart_steps.contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    traces, eids = _capi.random_walk(table, [used.index(m) for m in metapath], nodes, restart_scalar, restart_steps,
+                                     int(seed), return_eids)
+    types = torch.tensor(types, dtype=idt, device=dev)
+    return (traces, eids, types) if return_eids else (traces, types)
+
+
+def pack_traces(traces, types):
+    """``dgl.sampling.pack_traces`` (python/dgl/sampling/randomwalks.py:229-310): the -1 padding of ``traces`` removed
+    and the rest concatenated.  Returns ``(concat_vids, concat_types, lengths, offsets)``: node ids, their node types,
+    the length of every trace and where it starts in ``concat_vids``.  Plain torch, on the inputs' device (the
+    reference takes CPU tensors only)."""
+    if traces.dim() != 2 or types.dim() != 1 or types.shape[0] != traces.shape[1]:
+        raise _DGLError("pack_traces: traces must be (num_traces, len) and types (len,)")
+    keep = traces != -1
+    lengths = keep.sum(1).to(traces.dtype)
+    offsets = torch.cumsum(lengths, 0).to(traces.dtype) - lengths
+    return traces[keep], types.to(traces.device).expand_as(traces)[keep], lengths, offsets

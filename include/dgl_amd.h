@@ -557,6 +557,68 @@ int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, 
                          void* src_nodes, int64_t* num_src_out, void* workspace, size_t workspace_bytes,
                          void* hip_stream);
 
+/* ---- random walks: metapath, weighted and restart forms ------------------------------------------
+ * Replace RandomWalk<kDGLCUDA> and its restart forms (src/graph/sampling/randomwalks/randomwalk_gpu.cu, behind
+ * dgl.sampling.random_walk, python/dgl/sampling/randomwalks.py:31-226).  The reference seeds one curand state per thread
+ * (its picks depend on the launch geometry) and scans a weighted row linearly; here the picks are a pure function of
+ * (rng_seed, walk index, step, draw slot) and the weighted step is a bisection in a CDF built once per relation.
+ * The step rule (ONE definition for device and host, csrc/random_walk_step.h):
+ *
+ * Generator.  mix64 is the function of csrc/sampling.hip (the splitmix64 finaliser including its increment).  For walk
+ * index i (position in `seeds`, not the node id, so a node listed twice gets two independent walks), step t (0-based)
+ * and draw slot k:
+ *     r(seed,i,t,k) = mix64( mix64( mix64(seed ^ (i * 0xD1B54A32D192ED03)) + t ) + k )      (all mod 2^64)
+ *     uniform index in [0,n):  (r * n) >> 64    (multiply-high)
+ *     uniform double in [0,1): (r >> 11) * 2^-53
+ * Slot 0 is the neighbour pick and slot 1 is the restart test.
+ *
+ * One step of walk i at node curr, step t, relation R = rels[metapath[t]].  R is the out-edge CSR: rows are source
+ * nodes, `indices` are successors, and `data` is the edge-id map or NULL.
+ *  1. Restart: if a restart probability p_t is given (scalar, or restart_steps[t] converted to double) and
+ *     u(seed,i,t,1) < p_t, the walk halts.
+ *  2. lo = indptr[curr], hi = indptr[curr+1].  If hi == lo, the walk halts.
+ *  3. Uniform relation (cdf == NULL): pos = lo + index(r(seed,i,t,0), hi - lo).
+ *  4. Weighted relation: total = cdf[hi-1].  If !(total > 0) or total is not finite, the walk halts.  Otherwise
+ *     x = u(seed,i,t,0) * total (one fp64 multiply).  pos is the first position in [lo,hi) with cdf[pos] > x.  If there
+ *     is none (rounding), pos is the first position with cdf[pos] == total.  The search is a bisection, O(log deg).
+ *  5. trace[i][t+1] = indices[pos], eids[i][t] = data ? data[pos] : pos, curr = indices[pos].
+ * A halted walk writes -1 into trace[i][t+1 ..] and eids[i][t ..].  trace[i][0] = seeds[i] always.  A seed outside
+ * [0, num_rows of rels[metapath[0]]) halts at once and touches no memory through that id.
+ *
+ * CDF of a relation, as double[nnz] in CSR position order: cdf[pos] = sum_{q = lo..pos} w'(q), with
+ * w'(q) = max((double)prob[data ? data[q] : q], 0) and NaN -> 0.  `prob` is indexed by EDGE ID.  The order of additions
+ * is free, but cdf never decreases inside a row, and w'(pos) == 0 implies cdf[pos] == cdf[pos-1], so a zero-weight
+ * edge is never picked.
+ *
+ * dgla_random_walk_cdf: builds that CDF (device memory, double[nnz]) from `prob` (float32 / float64 per EDGE ID); no
+ *   floating-point atomics, the same bits on every run.  Its workspace is empty today; pass what
+ *   dgla_random_walk_cdf_workspace_bytes says.
+ * dgla_random_walk: `rels` and `metapath` are HOST arrays (the table holds device pointers), everything else is device
+ *   memory of the table's id type.  Up to 16 relations and 256 steps travel in the kernel arguments; a larger table or
+ *   metapath goes through `workspace` (dgla_random_walk_workspace_bytes, 0 while both fit).  eids may be NULL.
+ *   restart_prob is used when restart_steps == NULL (0 = no restart); restart_steps is float32 / float64 [num_steps].
+ * The calls allocate nothing, read nothing back and do not synchronise.  They fail with -1 and a message for a NULL
+ *   table, relations of mixed id width, metapath[t] out of range, a metapath whose node types do not chain
+ *   (rels[metapath[t]].csr->num_cols != rels[metapath[t+1]].csr->num_rows) and a workspace that is too small.
+ *   num_seeds == 0 and num_steps == 0 are valid.
+ * dgla_random_walk_host: the same arguments with every pointer in HOST memory, no stream and no workspace: the same
+ *   rule run by the CPU, bit for bit what the kernel writes.  Host-only: needs no GPU. */
+typedef struct {
+  const dgla_csr* csr; /* out-edge CSR: rows = source nodes */
+  const double* cdf;   /* [nnz] from dgla_random_walk_cdf, or NULL = uniform */
+} dgla_walk_relation;
+size_t dgla_random_walk_cdf_workspace_bytes(const dgla_csr* csr);
+int dgla_random_walk_cdf(const dgla_csr* csr, const void* prob, dgla_dtype prob_dtype, double* cdf, void* workspace,
+                         size_t workspace_bytes, void* hip_stream);
+size_t dgla_random_walk_workspace_bytes(int num_rels, int64_t num_steps);
+int dgla_random_walk(const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps,
+                     const void* seeds, int64_t num_seeds, double restart_prob, const void* restart_steps,
+                     dgla_dtype restart_dtype, uint64_t rng_seed, void* traces, void* eids, void* workspace,
+                     size_t workspace_bytes, void* hip_stream);
+int dgla_random_walk_host(const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps,
+                          const void* seeds, int64_t num_seeds, double restart_prob, const void* restart_steps,
+                          dgla_dtype restart_dtype, uint64_t rng_seed, void* traces, void* eids);
+
 /* ---- k-way node-cut partitioner (host code) ---------------------------------
  * Stands where METIS stands in the reference: metis_partition_assignment
  * (python/dgl/partition.py:278-397 -> _CAPI_DGLMetisPartition_Hetero).  Multilevel
