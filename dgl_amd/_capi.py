@@ -694,6 +694,84 @@ def random_walk_host(rels, metapath, seeds, restart_prob=0.0, restart_steps=None
     return traces, eids
 
 
+def pinsage_max_samples(idtype=torch.int64):
+    """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
+    return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))
+
+
+def pinsage_size_classes():
+    """The largest ``num_samples_per_node`` of every size class of the selection kernel, ascending (host query)."""
+    buf = (ctypes.c_int64 * 8)()
+    n = LIB.dgla_pinsage_size_classes(buf, 8)
+    return [int(buf[i]) for i in range(n)]
+
+
+def _pinsage_args(who, src, dst, num_samples_per_node, k, device):
+    """The argument errors the three selection entry points share, raised before any launch and before the device check
+    (so they can be met without a GPU).  Returns ``(id width, num_dst, S, k, min(k, S))``."""
+    if src.dtype != dst.dtype or src.dtype not in (torch.int32, torch.int64):
+        raise _lib.DGLAMDError("%s: src and dst must both be int32 or both int64, got %s and %s" % (who, src.dtype, dst.dtype))
+    if src.dim() != 1 or dst.shape != src.shape or not src.is_contiguous() or not dst.is_contiguous():
+        raise _lib.DGLAMDError("%s: src and dst must be contiguous 1-D tensors of one length" % who)
+    S, k = int(num_samples_per_node), int(k)
+    if S < 1:
+        raise _lib.DGLAMDError("%s: num_samples_per_node must be at least 1, got %d" % (who, S))
+    if k < 1:
+        raise _lib.DGLAMDError("%s: k must be at least 1, got %d" % (who, k))
+    if src.shape[0] % S:
+        raise _lib.DGLAMDError("%s: the length of src (%d) is not a multiple of num_samples_per_node (%d)"
+                               % (who, src.shape[0], S))
+    if device and S > pinsage_max_samples(src.dtype):
+        raise _lib.DGLAMDError("%s: num_samples_per_node = %d is above the largest segment the kernel holds in LDS (%d); "
+                               "there is no CPU fallback" % (who, S, pinsage_max_samples(src.dtype)))
+    return _idbits(src), src.shape[0] // S, S, k, min(k, S)
+
+
+def select_pinsage_neighbors_padded(src, dst, num_samples_per_node, k):
+    """The visit-count top-k of every segment of ``num_samples_per_node`` entries of `src` in its static shape
+    (dgla_pinsage_select_padded; the rule: include/dgl_amd.h).  Returns ``(src [n, k'], counts [n, k'], num [n])`` with
+    k' = min(k, num_samples_per_node), -1 / 0 in the unused slots.  Nothing is read back."""
+    bits, n, S, k, kp = _pinsage_args("select_pinsage_neighbors_padded", src, dst, num_samples_per_node, k, True)
+    _require_gpu(src)
+    _require_gpu(dst)
+    out_src = torch.empty((n, kp), dtype=src.dtype, device=src.device)
+    out_cnt = torch.empty((n, kp), dtype=src.dtype, device=src.device)
+    out_num = torch.empty(n, dtype=src.dtype, device=src.device)
+    check_call(LIB.dgla_pinsage_select_padded(bits, _ptr(src), _ptr(dst), n, S, k, _ptr(out_src), _ptr(out_cnt),
+                                              _ptr(out_num), None, _stream(src)))
+    return out_src, out_cnt, out_num
+
+
+def select_pinsage_neighbors(src, dst, num_samples_per_node, k):
+    """``_select_pinsage_neighbors`` of python/dgl/sampling/pinsage.py on the device (dgla_pinsage_select_count + _fill):
+    ``(src, dst, counts)`` of the kept neighbours, segments in input order, ranked by (count, id) descending inside a
+    segment.  Reading the total is the one host synchronisation."""
+    bits, n, S, k, kp = _pinsage_args("select_pinsage_neighbors", src, dst, num_samples_per_node, k, True)
+    _require_gpu(src)
+    _require_gpu(dst)
+    need = LIB.dgla_pinsage_select_workspace_bytes(bits, n, S, k)
+    ws = torch.empty(need, dtype=torch.uint8, device=src.device)
+    total = ctypes.c_int64(0)
+    st = _stream(src)
+    check_call(LIB.dgla_pinsage_select_count(bits, _ptr(src), _ptr(dst), n, S, k, ctypes.byref(total), _ptr(ws), need, st))
+    res = [torch.empty(total.value, dtype=src.dtype, device=src.device) for _ in range(3)]
+    check_call(LIB.dgla_pinsage_select_fill(bits, n, S, k, _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(ws), need, st))
+    return tuple(res)
+
+
+def select_pinsage_neighbors_host(src, dst, num_samples_per_node, k):
+    """:func:`select_pinsage_neighbors` run by the CPU on CPU tensors (dgla_pinsage_select_host): a plain restatement
+    of the rule, what the kernel is tested against.  Needs no GPU and accepts any ``num_samples_per_node``."""
+    bits, n, S, k, kp = _pinsage_args("select_pinsage_neighbors_host", src, dst, num_samples_per_node, k, False)
+    if src.is_cuda or dst.is_cuda:
+        raise _lib.DGLAMDError("select_pinsage_neighbors_host takes CPU tensors")
+    res = [torch.empty(n * kp, dtype=src.dtype) for _ in range(3)]
+    total = ctypes.c_int64(0)
+    check_call(LIB.dgla_pinsage_select_host(bits, _ptr(src), _ptr(dst), n, S, k, _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+                                            ctypes.byref(total)))
+    return tuple(r[:total.value].clone() for r in res)
+
+
 def to_block(seeds, src, node_map):
     """Block-local renumbering of `src` (dgla_to_block).  Returns ``(local_src, src_nodes,
     num_src)``; reading ``num_src`` back is the one host synchronisation of block building

@@ -236,6 +236,22 @@ LIB.dgla_random_walk.restype = c_int
 LIB.dgla_random_walk.argtypes = _WALK_ARGS + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_random_walk_host.restype = c_int
 LIB.dgla_random_walk_host.argtypes = _WALK_ARGS
+LIB.dgla_pinsage_max_samples.restype = c_int64
+LIB.dgla_pinsage_max_samples.argtypes = [c_int]
+LIB.dgla_pinsage_size_classes.restype = c_int
+LIB.dgla_pinsage_size_classes.argtypes = [P(c_int64), c_int]
+_PINSAGE_ARGS = [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64]   # id width, src, dst, num_dst, S, k
+LIB.dgla_pinsage_select_padded.restype = c_int
+LIB.dgla_pinsage_select_padded.argtypes = _PINSAGE_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+LIB.dgla_pinsage_select_workspace_bytes.restype = c_size_t
+LIB.dgla_pinsage_select_workspace_bytes.argtypes = [c_int, c_int64, c_int64, c_int64]
+LIB.dgla_pinsage_select_count.restype = c_int
+LIB.dgla_pinsage_select_count.argtypes = _PINSAGE_ARGS + [P(c_int64), c_void_p, c_size_t, c_void_p]
+LIB.dgla_pinsage_select_fill.restype = c_int
+LIB.dgla_pinsage_select_fill.argtypes = [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]
+LIB.dgla_pinsage_select_host.restype = c_int
+LIB.dgla_pinsage_select_host.argtypes = _PINSAGE_ARGS + [c_void_p, c_void_p, c_void_p, P(c_int64)]
 LIB.dgla_partition_kway_ex.restype = c_int
 LIB.dgla_partition_kway_ex.argtypes = [c_int, c_int64, c_void_p, c_void_p, c_int, ctypes.c_double, c_int, ctypes.c_uint64,
                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]

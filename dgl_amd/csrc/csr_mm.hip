@@ -112,30 +112,6 @@ __global__ __launch_bounds__(256) void bound_kernel(const Src src, int64_t num_r
   if (lane == 0) ub[row] = s;
 }
 
-// exclusive prefix of `v` over the NT threads of the workgroup, *total = the sum; wsum: NT / 64 words of LDS
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total, int* wsum) {
-  const int incl = msd::wave_inclusive_scan32(v);
-  if constexpr (NT == 64) {
-    *total = __shfl(incl, 63, 64);
-    return incl - v;
-  } else {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();   // (wsum may still be read from the previous use)
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-      const int x = wsum[w];
-      if (w < wave) off += x;
-      tot += x;
-    }
-    *total = tot;
-    return off + incl - v;
-  }
-}
-
 // ---- classes 1 and 2: expand -> sort by (column, sequence) -> segmented sum, all in LDS --------------------------------
 // One workgroup of NT threads per row whose term count lies in [lo, hi], hi <= CAP.  FILL = false counts the distinct
 // columns into cnt[row]; FILL = true writes them and their sums at c_indptr[row].
@@ -164,7 +140,7 @@ __global__ __launch_bounds__(NT) void row_sort_kernel(const Src src, const int64
     A scale = A(0);
     if (u < u_end) src.template source<FILL>(row, u, &scale, &p0, &p1);
     int total;
-    const int off = running + block_exclusive_scan<NT>(static_cast<int>(p1 - p0), &total, wsum);
+    const int off = running + msd::block_exclusive_scan<NT>(static_cast<int>(p1 - p0), &total, wsum);
     for (int64_t p = p0; p < p1; ++p) {
       const int slot = off + static_cast<int>(p - p0);
       if (slot < n) {   // (always, for a consistent indptr)
@@ -206,7 +182,7 @@ __global__ __launch_bounds__(NT) void row_sort_kernel(const Src src, const int64
   int heads = 0;
   for (int s = s0; s < s1; ++s) heads += (s == 0 || kc[s] != kc[s - 1]) ? 1 : 0;
   int total;
-  int at = block_exclusive_scan<NT>(heads, &total, wsum);
+  int at = msd::block_exclusive_scan<NT>(heads, &total, wsum);
   if constexpr (!FILL) {
     if (tid == 0) cnt[row] = total;
   } else {
@@ -280,7 +256,7 @@ __global__ __launch_bounds__(64) void row_spa_kernel(const Src src, const int64_
     int have = 0;
     for (int i = 0; i < kPer; ++i) have += flag[lane * kPer + i];
     int total;
-    int at = block_exclusive_scan<64>(have, &total, nullptr);
+    int at = msd::block_exclusive_scan<64>(have, &total, nullptr);
     if constexpr (FILL) {
       for (int i = 0; i < kPer; ++i) {
         const int sl = lane * kPer + i;

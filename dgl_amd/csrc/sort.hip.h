@@ -85,6 +85,30 @@ __device__ __forceinline__ T wave_inclusive_scan(T v) {
   }
 }
 
+// exclusive prefix of `v` over the NT threads of the workgroup, *total = the sum; wsum: NT / 64 words of LDS
+template <int NT>
+__device__ __forceinline__ int block_exclusive_scan(int v, int* total, int* wsum) {
+  const int incl = wave_inclusive_scan32(v);
+  if constexpr (NT == 64) {
+    *total = __shfl(incl, 63, 64);
+    return incl - v;
+  } else {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();   // (wsum may still be read from the previous use)
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+      const int x = wsum[w];
+      if (w < wave) off += x;
+      tot += x;
+    }
+    *total = tot;
+    return off + incl - v;
+  }
+}
+
 template <typename TI, typename TO>
 __global__ __launch_bounds__(kScanBlock) void scan_block_sums_kernel(const TI* __restrict__ in, int64_t n, TO* __restrict__ sums) {
   __shared__ TO part[kScanBlock / 64];

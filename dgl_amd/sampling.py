@@ -11,13 +11,15 @@ block keeps one source and one destination node set per node type (R-GCN mini-ba
 
 ``random_walk`` / ``pack_traces`` mirror ``dgl.sampling.random_walk`` / ``pack_traces``
 (python/dgl/sampling/randomwalks.py:31-310) over csrc/random_walk.hip: metapath, weighted and restart walks.
+``RandomWalkNeighborSampler`` / ``PinSAGESampler`` mirror python/dgl/sampling/pinsage.py:27-272: those walks followed by
+the visit-count top-k of csrc/pinsage.hip.
 """
 import torch
 
 from . import _capi
 from ._lib import DGLAMDError as _DGLError
 from .graph_index import GraphIndex, Relation
-from .heterograph import DGLGraph
+from .heterograph import DGLGraph, heterograph as _heterograph
 
 NID = "_ID"   # dgl.NID / dgl.EID
 EID = "_ID"
@@ -599,3 +601,78 @@ def pack_traces(traces, types):
     lengths = keep.sum(1).to(traces.dtype)
     offsets = torch.cumsum(lengths, 0).to(traces.dtype) - lengths
     return traces[keep], types.to(traces.device).expand_as(traces)[keep], lengths, offsets
+
+
+# ---- PinSAGE neighbourhoods ----------------------------------------------------------------------
+class RandomWalkNeighborSampler:
+    """``dgl.sampling.RandomWalkNeighborSampler`` (python/dgl/sampling/pinsage.py:27-163): the neighbours of a seed are
+    the nodes of its own type that ``num_random_walks`` walks from it visit most often.  A walk is up to
+    ``num_traversals`` passes over ``metapath`` (which must end in the node type it starts from) and halts with
+    ``termination_prob`` in front of every pass but the first.  Calling the sampler returns a graph over ALL nodes of that
+    type with one edge ``neighbour -> seed`` per kept neighbour, at most ``num_neighbors`` per seed, ranked by
+    (visits, id) descending, and the visit counts in ``edata[weight_column]``.  Walks and selection run on the device
+    (csrc/random_walk.hip, csrc/pinsage.hip); ``seed`` pins the walks as in :func:`random_walk`."""
+
+    def __init__(self, G, num_traversals, termination_prob, num_random_walks, num_neighbors, metapath=None,
+                 weight_column="weights"):
+        self.G = G
+        self.weight_column = weight_column
+        self.num_random_walks = int(num_random_walks)
+        self.num_neighbors = int(num_neighbors)
+        self.num_traversals = int(num_traversals)
+        if metapath is None:
+            if len(G.ntypes) > 1 or len(G.etypes) > 1:
+                raise ValueError("Metapath must be specified if the graph is homogeneous.")   # (the reference's wording)
+            metapath = [G.canonical_etypes[0]]
+        metapath = list(metapath)
+        start_ntype = G.to_canonical_etype(metapath[0])[0]
+        end_ntype = G.to_canonical_etype(metapath[-1])[-1]
+        if start_ntype != end_ntype:
+            raise ValueError("The metapath must start and end at the same node type.")
+        self.ntype = start_ntype
+        self.metapath_hops = len(metapath)
+        self.metapath = metapath
+        self.full_metapath = metapath * self.num_traversals
+        # halting is tested in front of the first step of every pass but the first
+        restart_prob = torch.zeros(self.metapath_hops * self.num_traversals, dtype=torch.float32)
+        restart_prob[self.metapath_hops::self.metapath_hops] = termination_prob
+        self.restart_prob = restart_prob.to(G.device)
+
+    def __call__(self, seed_nodes, seed=None):
+        G = self.G
+        if not torch.is_tensor(seed_nodes):
+            seed_nodes = torch.as_tensor(seed_nodes, dtype=G.idtype)
+        if seed_nodes.dtype != G.idtype:
+            raise _DGLError("Expect argument \"seed_nodes\" to have data type %s. But got %s." % (G.idtype, seed_nodes.dtype))
+        seed_nodes = seed_nodes.reshape(-1).to(G.device)
+        walks = seed_nodes.repeat_interleave(self.num_random_walks)
+        paths, _ = random_walk(G, walks, metapath=self.full_metapath, restart_prob=self.restart_prob, seed=seed)
+        src = paths[:, self.metapath_hops::self.metapath_hops].reshape(-1).contiguous()   # (one column stays a strided view)
+        dst = paths[:, 0].repeat_interleave(self.num_traversals)
+        if src.numel():
+            src, dst, counts = _capi.select_pinsage_neighbors(src, dst, self.num_random_walks * self.num_traversals,
+                                                              self.num_neighbors)
+        else:
+            counts = src
+        g = _heterograph({(self.ntype, "_E", self.ntype): (src, dst)}, {self.ntype: G.num_nodes(self.ntype)},
+                         idtype=G.idtype, device=G.device)
+        g.edata[self.weight_column] = counts
+        return g
+
+
+class PinSAGESampler(RandomWalkNeighborSampler):
+    """``dgl.sampling.PinSAGESampler`` (python/dgl/sampling/pinsage.py:166-272): :class:`RandomWalkNeighborSampler` on a
+    bidirectional bipartite graph, along the metapath ``ntype -> other_type -> ntype`` (the first edge type of each
+    direction)."""
+
+    def __init__(self, G, ntype, other_type, num_traversals, termination_prob, num_random_walks, num_neighbors,
+                 weight_column="weights"):
+        def etype_between(a, b):
+            for c in G.canonical_etypes:
+                if c[0] == a and c[2] == b:
+                    return c
+            raise _DGLError("PinSAGESampler: no edge type goes from '%s' to '%s'" % (a, b))
+
+        super().__init__(G, num_traversals, termination_prob, num_random_walks, num_neighbors,
+                         metapath=[etype_between(ntype, other_type), etype_between(other_type, ntype)],
+                         weight_column=weight_column)

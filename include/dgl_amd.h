@@ -619,6 +619,53 @@ int dgla_random_walk_host(const dgla_walk_relation* rels, int num_rels, const in
                           const void* seeds, int64_t num_seeds, double restart_prob, const void* restart_steps,
                           dgla_dtype restart_dtype, uint64_t rng_seed, void* traces, void* eids);
 
+/* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
+ * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
+ * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
+ * atomic inserts and leaves ties between equal visit counts in a run-dependent order; here a segment is selected in LDS
+ * by one workgroup, without atomics, and the result is the one of the reference's CPU form (randomwalk_cpu.cc:41-102).
+ * The rule (ONE statement for device and host):
+ *
+ * Inputs are src[num_dst * S] and dst[num_dst * S], both int32 or both int64; S = num_samples_per_node >= 1, k >= 1.
+ * For segment j take the multiset of src[j*S .. (j+1)*S) with its -1 entries removed.  Rank its distinct ids by
+ * (count descending, id descending) and keep the first min(k, number of distinct ids).  For each kept id emit
+ * (id, dst[j*S], count) with the count in the id dtype; the segments follow each other in the order of j.
+ * Ids cover the full non-negative range of the dtype (an id is never packed into a narrower key); ids are compared as
+ * unsigned words, so an id below -1 is outside the contract but ranks the same way on the device and on the host.
+ *
+ * dgla_pinsage_max_samples: the largest S the kernel accepts (the segment lives in LDS): 4096 for both id widths, 0
+ *   for another width.  A larger S is refused with a message before any launch; there is no CPU fallback.
+ * dgla_pinsage_size_classes: the largest S of each size class, ascending (one wavefront per segment / a 256-thread
+ *   workgroup / a 512-thread workgroup); returns their number.
+ * dgla_pinsage_select_padded: the static-shape result.  With k' = min(k, S): out_src and out_cnt are [num_dst, k'] in
+ *   the id dtype with the kept (id, count) pairs of segment j in rank order and -1 / 0 in the unused slots; out_num
+ *   [num_dst] is the number kept; out_dst (may be NULL, then dst may be NULL) [num_dst] receives dst[j*S], the one
+ *   read of dst per segment.  No workspace, no allocation, nothing read back, no synchronisation.
+ * dgla_pinsage_select_count / _fill: the compact result around one workspace of
+ *   dgla_pinsage_select_workspace_bytes bytes (it holds the padded result: proportional to num_dst * k', not to
+ *   num_dst * S).  `count` selects, scans the kept numbers and returns their total in *total_out — the one host
+ *   synchronisation, which the reference pays too; `fill` then writes res_src / res_dst / res_cnt [total] allocated by
+ *   the caller, from the same workspace on the same stream.
+ * dgla_pinsage_select_host: the rule run by the CPU on HOST pointers, no stream and no workspace; res_* must hold
+ *   num_dst * k' entries, *total_out receives the number written.  Host-only: needs no GPU, accepts any S.
+ * All fail with -1 and a message for an id width other than 32 / 64, S < 1, k < 1, num_dst < 0 and (device forms)
+ * S above the limit or a workspace that is too small.  num_dst == 0 is valid. */
+int64_t dgla_pinsage_max_samples(int idtype_bits);
+int dgla_pinsage_size_classes(int64_t* bounds, int max);
+int dgla_pinsage_select_padded(int idtype_bits, const void* src, const void* dst, int64_t num_dst,
+                               int64_t num_samples_per_node, int64_t k, void* out_src, void* out_cnt, void* out_num,
+                               void* out_dst, void* hip_stream);
+size_t dgla_pinsage_select_workspace_bytes(int idtype_bits, int64_t num_dst, int64_t num_samples_per_node, int64_t k);
+int dgla_pinsage_select_count(int idtype_bits, const void* src, const void* dst, int64_t num_dst,
+                              int64_t num_samples_per_node, int64_t k, int64_t* total_out, void* workspace,
+                              size_t workspace_bytes, void* hip_stream);
+int dgla_pinsage_select_fill(int idtype_bits, int64_t num_dst, int64_t num_samples_per_node, int64_t k, void* res_src,
+                             void* res_dst, void* res_cnt, const void* workspace, size_t workspace_bytes,
+                             void* hip_stream);
+int dgla_pinsage_select_host(int idtype_bits, const void* src, const void* dst, int64_t num_dst,
+                             int64_t num_samples_per_node, int64_t k, void* res_src, void* res_dst, void* res_cnt,
+                             int64_t* total_out);
+
 /* ---- k-way node-cut partitioner (host code) ---------------------------------
  * Stands where METIS stands in the reference: metis_partition_assignment
  * (python/dgl/partition.py:278-397 -> _CAPI_DGLMetisPartition_Hetero).  Multilevel
