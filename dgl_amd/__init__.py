@@ -22,7 +22,8 @@ from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, ad
 from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401
-from .sampling import EID, NID, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler, to_block  # noqa: E402,F401
+from .sampling import (EID, NID, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
+                       node2vec_random_walk, to_block)
 from .mm import gather_mm, segment_mm  # noqa: E402,F401
 from .segment import scatter_add, segment_reduce, segment_softmax  # noqa: E402,F401
 from .sparse_kernels import release_static, set_auto_edge_operand, static_features  # noqa: E402,F401

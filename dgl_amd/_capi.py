@@ -694,6 +694,62 @@ def random_walk_host(rels, metapath, seeds, restart_prob=0.0, restart_steps=None
     return traces, eids
 
 
+def csr_sorted_columns(csr):
+    """The membership list of `csr` (dgla_csr_sorted_columns): every row's column ids in ascending order, duplicates
+    kept, over the same indptr; what the node2vec step bisects to learn whether an edge exists.  `csr` from
+    :func:`make_csr`; nothing is read back."""
+    indptr = csr._keep[0]
+    _require_gpu(indptr)
+    member = torch.empty(csr.nnz, dtype=indptr.dtype, device=indptr.device)
+    need = LIB.dgla_csr_sorted_columns_workspace_bytes(ctypes.byref(csr))
+    ws = torch.empty(need, dtype=torch.uint8, device=indptr.device) if need else None
+    check_call(LIB.dgla_csr_sorted_columns(ctypes.byref(csr), member.data_ptr(), _ptr(ws), need, _stream(indptr)))
+    return member
+
+
+def _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids):
+    """The argument list the device and the host node2vec walker share."""
+    if cdf is not None and (cdf.dtype != torch.float64 or cdf.numel() != csr.nnz or not cdf.is_contiguous()):
+        raise _lib.DGLAMDError("the cdf must be a contiguous float64 tensor with one entry per edge")
+    if member is None or _idbits(member) != csr.idtype_bits or member.numel() != csr.nnz or not member.is_contiguous():
+        raise _lib.DGLAMDError("member must be a contiguous tensor of the csr's id type with one entry per edge")
+    if not seeds.is_contiguous() or _idbits(seeds) != csr.idtype_bits:
+        raise _lib.DGLAMDError("seeds must be contiguous and of the csr's id type")
+    n, steps = seeds.shape[0], int(num_steps)
+    if steps < 0:
+        raise _lib.DGLAMDError("the number of steps must not be negative")
+    traces = torch.empty((n, steps + 1), dtype=seeds.dtype, device=seeds.device)
+    eids = torch.empty((n, steps), dtype=seeds.dtype, device=seeds.device) if return_eids else None
+    args = [ctypes.byref(csr), _ptr(cdf), member.data_ptr(), seeds.data_ptr(), n, steps, float(p), float(q),
+            int(rng_seed) & 0xFFFFFFFFFFFFFFFF, traces.data_ptr(), _ptr(eids)]
+    return args, traces, eids
+
+
+def node2vec_walk(csr, cdf, member, seeds, num_steps, p, q, rng_seed=0, return_eids=True):
+    """node2vec walks over the out-edge CSR `csr` (dgla_node2vec_walk): `cdf` from :func:`random_walk_cdf` or None,
+    `member` from :func:`csr_sorted_columns`.  Returns ``(traces [n, steps + 1], eids [n, steps] or None)``; a walk that
+    halts is padded with -1.  Nothing is read back."""
+    for t in (seeds, member, cdf):
+        if t is not None:
+            _require_gpu(t)
+    args, traces, eids = _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids)
+    check_call(LIB.dgla_node2vec_walk(*args, _stream(seeds)))
+    return traces, eids
+
+
+def node2vec_walk_host(csr, cdf, member, seeds, num_steps, p, q, rng_seed=0, return_eids=True, stats=False):
+    """:func:`node2vec_walk` run by the CPU on CPU tensors (dgla_node2vec_walk_host; `csr` built with :func:`host_csr`):
+    the same step rule compiled for the host, bit for bit what the kernel writes.  Needs no GPU.  With ``stats`` a third
+    result ``[steps t >= 1 that recorded a node, candidates drawn, steps that reached the scan]``."""
+    for t in (seeds, member, cdf):
+        if t is not None and t.is_cuda:
+            raise _lib.DGLAMDError("node2vec_walk_host takes CPU tensors")
+    args, traces, eids = _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids)
+    counters = (ctypes.c_int64 * 3)() if stats else None
+    check_call(LIB.dgla_node2vec_walk_host(*args, counters))
+    return (traces, eids, [int(c) for c in counters]) if stats else (traces, eids)
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

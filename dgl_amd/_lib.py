@@ -236,6 +236,17 @@ LIB.dgla_random_walk.restype = c_int
 LIB.dgla_random_walk.argtypes = _WALK_ARGS + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_random_walk_host.restype = c_int
 LIB.dgla_random_walk_host.argtypes = _WALK_ARGS
+LIB.dgla_csr_sorted_columns_workspace_bytes.restype = c_size_t
+LIB.dgla_csr_sorted_columns_workspace_bytes.argtypes = [P(CSR)]
+LIB.dgla_csr_sorted_columns.restype = c_int
+LIB.dgla_csr_sorted_columns.argtypes = [P(CSR), c_void_p, c_void_p, c_size_t, c_void_p]
+# csr, cdf, member, seeds, num_seeds, num_steps, p, q, rng_seed, traces, eids
+_N2V_ARGS = [P(CSR), c_void_p, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_uint64,
+             c_void_p, c_void_p]
+LIB.dgla_node2vec_walk.restype = c_int
+LIB.dgla_node2vec_walk.argtypes = _N2V_ARGS + [c_void_p]
+LIB.dgla_node2vec_walk_host.restype = c_int
+LIB.dgla_node2vec_walk_host.argtypes = _N2V_ARGS + [P(c_int64)]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

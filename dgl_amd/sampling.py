@@ -12,8 +12,11 @@ block keeps one source and one destination node set per node type (R-GCN mini-ba
 ``random_walk`` / ``pack_traces`` mirror ``dgl.sampling.random_walk`` / ``pack_traces``
 (python/dgl/sampling/randomwalks.py:31-310) over csrc/random_walk.hip: metapath, weighted and restart walks.
 ``RandomWalkNeighborSampler`` / ``PinSAGESampler`` mirror python/dgl/sampling/pinsage.py:27-272: those walks followed by
-the visit-count top-k of csrc/pinsage.hip.
+the visit-count top-k of csrc/pinsage.hip.  ``node2vec_random_walk`` mirrors python/dgl/sampling/node2vec_randomwalk.py
+over csrc/node2vec.hip: the bounded second-order step of csrc/node2vec_step.h.
 """
+import math
+
 import torch
 
 from . import _capi
@@ -588,6 +591,55 @@ def random_walk(g, nodes, *, metapath=None, length=None, prob=None, restart_prob
                                      int(seed), return_eids)
     types = torch.tensor(types, dtype=idt, device=dev)
     return (traces, eids, types) if return_eids else (traces, types)
+
+
+def _walk_members(rel, fmt, csr):
+    """The membership list of relation ``rel`` (every row's column ids ascending, what the node2vec step bisects): built
+    on first use and kept in ONE slot on the relation, keyed by the addresses and ``_version`` of the CSR's arrays and
+    checked at every use, like :func:`_walk_cdf`.  It costs ``nnz`` ids of device memory."""
+    key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device) for t in fmt[:2])
+    slot = getattr(rel, "_walk_members", None)
+    if slot is None or slot[0] != key:
+        slot = rel._walk_members = (key, _capi.csr_sorted_columns(csr))
+    return slot[1]
+
+
+def node2vec_random_walk(g, nodes, p, q, walk_length, prob=None, return_eids=False, seed=None):
+    """``dgl.sampling.node2vec_random_walk`` (python/dgl/sampling/node2vec_randomwalk.py): one node2vec walk of
+    ``walk_length`` steps per entry of ``nodes`` on a homogeneous graph.  ``p`` steers the return to the node the walk
+    came from (weight ``1/p``), ``q`` the move away from it (weight ``1/q`` for a successor that has no edge to the
+    previous node, 1 for one that has); both must be finite and > 0.  ``prob`` names an edge feature of unnormalised
+    weights (zero, negative and NaN weights are never taken).  Returns ``traces`` ``(len(nodes), walk_length + 1)`` with -1
+    after a walk halted, or ``(traces, eids)``.  The walks run on the device (csrc/node2vec.hip): a step makes a bounded
+    number of rejection attempts and then scans the row exactly, so the law is the reference's whatever ``p`` and ``q``
+    (the step rule: include/dgl_amd.h).  ``seed`` as in :func:`random_walk`; with ``p == q == 1`` the walks are those of
+    :func:`random_walk` under the same seed."""
+    if len(g.canonical_etypes) != 1 or len(g.ntypes) != 1:
+        raise _DGLError("node2vec_random_walk: Node2vec only support homogeneous graph.")
+    if torch.is_tensor(nodes) and nodes.dtype != g.idtype:
+        raise _DGLError("Expect argument \"nodes\" to have data type %s. But got %s." % (g.idtype, nodes.dtype))
+    p, q, walk_length = float(p), float(q), int(walk_length)
+    if not (math.isfinite(p) and math.isfinite(q) and p > 0 and q > 0):
+        raise _DGLError("node2vec_random_walk: p and q must be finite and > 0, got p = %r, q = %r" % (p, q))
+    if walk_length < 0:
+        raise _DGLError("node2vec_random_walk: walk_length must not be negative")
+    rel = g._graph.relations[0]
+    w = None
+    if prob is not None:
+        w = g.edata[prob] if isinstance(prob, str) else prob
+        if w.dim() == 0 or w.shape[0] != rel.num_edges or w.numel() != rel.num_edges:
+            raise _DGLError("node2vec_random_walk: prob must hold one value per edge of the graph (%d), got shape %s"
+                            % (rel.num_edges, tuple(w.shape)))
+    dev, idt = g.device, g.idtype
+    fmt = rel.csr()
+    csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst)    # (refuses a CPU graph: no CPU fallback)
+    cdf = None if w is None else _walk_cdf(rel, csr, w.to(dev))   # the slot random_walk uses
+    member = _walk_members(rel, fmt, csr)
+    nodes = torch.as_tensor(nodes).reshape(-1).to(device=dev, dtype=idt).contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    traces, eids = _capi.node2vec_walk(csr, cdf, member, nodes, walk_length, p, q, int(seed), return_eids)
+    return (traces, eids) if return_eids else traces
 
 
 def pack_traces(traces, types):

@@ -619,6 +619,80 @@ int dgla_random_walk_host(const dgla_walk_relation* rels, int num_rels, const in
                           const void* seeds, int64_t num_seeds, double restart_prob, const void* restart_steps,
                           dgla_dtype restart_dtype, uint64_t rng_seed, void* traces, void* eids);
 
+/* ---- node2vec walks: a bounded second-order step (csrc/node2vec.hip) ------------------------------
+ * Replace Node2vecRandomWalk (src/graph/sampling/randomwalks/node2vec_randomwalk.h:67-147, CPU only, behind
+ * dgl.sampling.node2vec_random_walk, python/dgl/sampling/node2vec_randomwalk.py).  The reference's step is an unbounded
+ * rejection loop; here a step makes at most K attempts and then scans the row once, with the same law.  The generator,
+ * the draws r(seed,i,t,k), index() and u(), and the CDF are those of "Random walks" above.  The step rule (ONE
+ * definition for device and host, csrc/node2vec_step.h):
+ *
+ * Setting.  One relation with num_rows == num_cols, as its out-edge CSR (indptr, indices, data = edge-id map or NULL),
+ * an optional CDF (double[nnz] from dgla_random_walk_cdf, NULL = uniform) and a membership list member[nnz]: the
+ * column ids of every row in ascending order, duplicates kept, over the same indptr (dgla_csr_sorted_columns).
+ *
+ * Parameters.  p and q are finite and > 0.  The host computes, once per call,
+ *     m = max(1/p, 1, 1/q),   a0 = (1/p)/m,   a1 = 1/m,   a2 = (1/q)/m
+ * and refuses the call when m is not finite or some a is not > 0; the walk itself divides nothing.
+ *
+ * Class of a candidate x when the previous node is prev: class 0 if x == prev (a self-loop or a duplicate edge is
+ * judged by node id); else class 1 if the edge x -> prev exists, i.e. a bisection of member[indptr[x] .. indptr[x+1])
+ * finds prev; else class 2.  a_class(x) is a0, a1 or a2.
+ *
+ * Step t = 0 of walk i at its seed: rules 2-5 of csrc/random_walk_step.h (no restart), the pick from slot 0.
+ * Step t >= 1 at curr with row [lo, hi), deg = hi - lo, the node before curr being prev:
+ *  1. If deg == 0, the walk halts.
+ *  2. Weighted relation: total = cdf[hi-1]; if !(total > 0) or total is not finite, the walk halts.
+ *  3. Bounded rejection.  K = min(max(deg, 8), 1024).  For attempt k = 0 .. K-1: the candidate position is
+ *     pos = lo + index(r(seed,i,t,2k), deg) (uniform) or the weighted pick of rule 4 of csrc/random_walk_step.h with
+ *     r(seed,i,t,2k) (weighted); x = indices[pos]; the candidate is accepted iff u(seed,i,t,2k+1) < a_class(x).
+ *     (A class whose a is 1.0 always accepts, because u < 1.)
+ *  4. After K rejections, an exact scan of the row in position order, in fp64, every operation rounded on its own:
+ *     d_j = 1 (uniform) or cdf[j] - (j > lo ? cdf[j-1] : 0) (weighted);  g_j = fl(d_j * a_class(indices[j]));
+ *     S = fl(S + g_j) for j = lo .. hi-1 in that order, from S = 0.  If !(S > 0), the walk halts.
+ *     x = u(seed,i,t,2K) * S.  A second pass forms the same running sum and takes the first j whose running sum
+ *     is > x.  If there is none (rounding), it takes the last j with g_j > 0.
+ *  5. trace[i][t+1] = indices[pos], eids[i][t] = data ? data[pos] : pos, prev = curr, curr = indices[pos].
+ * A halted walk writes -1 into trace[i][t+1 ..] and eids[i][t ..].  trace[i][0] = seeds[i] always.  A seed outside
+ * [0, num_rows) halts at once and touches no memory through that id.
+ *
+ * What follows from the rule.  Picks are a pure function of (seed, walk index, step, slot).  Rejection and the scan
+ * draw from the same law, P(j) proportional to d_j * a_class(indices[j]), so falling through after K rejections does
+ * not bias the walk.  With p == q == 1 every a is 1.0, attempt 0 accepts, and the walk is the one of
+ * csrc/random_walk_step.h under the same seed, bit for bit.  A step costs at most K attempts and two scans of the row.
+ *
+ * K follows the degree because an attempt and one row position of the scan cost about the same (one gather and one
+ * bisection): K is part of the rule, not a tuned number.
+ *
+ * Floating point.  g_j and S are a multiply followed by an add: two roundings.  A device compiler contracts the pair
+ * into one fused multiply-add (one rounding) unless told otherwise, a host compiler does not, and the two would then
+ * disagree in the last bit of S: `#pragma clang fp contract(off)` in n2v_scan keeps them apart on every target.
+ * Everything else is integer arithmetic, single fp64 operations and fp64 compares.
+ *
+ * dgla_csr_sorted_columns: writes the membership list of `csr` to member[nnz] (device memory, the CSR's id type):
+ *   every row's column ids in ascending order, duplicates kept, over the same indptr.  Two runs of the stable sort of
+ *   dgla_coo_to_csr (by column, then by row); multigraphs and self-loops are fine; the same bytes on every run; the
+ *   edge-id map plays no part.  `workspace` must hold dgla_csr_sorted_columns_workspace_bytes bytes: the call
+ *   allocates nothing, reads nothing back and does not synchronise.
+ * dgla_node2vec_walk: csr, cdf (NULL = uniform), member, seeds, traces [num_seeds, num_steps + 1] and eids
+ *   [num_seeds, num_steps] (may be NULL) are device memory of the CSR's id type; no workspace, no allocation, nothing
+ *   read back, no synchronisation.
+ * dgla_node2vec_walk_host: the same arguments with every pointer in HOST memory and no stream: the same rule run by
+ *   the CPU, bit for bit what the kernel writes.  Host-only: needs no GPU.  `stats` may be NULL; otherwise it receives
+ *   {steps t >= 1 that recorded a node, candidates drawn by the rejection loops, steps that reached the scan}.  The
+ *   device kernel keeps no such counters.
+ * All fail with -1 and a message, before any launch, for a NULL csr / indices / member / seeds / traces, an id width
+ *   other than 32 / 64, num_rows != num_cols, negative sizes, p or q that is not finite and > 0 (or whose m or
+ *   acceptance probabilities are not usable) and a workspace that is too small.  num_seeds == 0 and num_steps == 0
+ *   are valid. */
+size_t dgla_csr_sorted_columns_workspace_bytes(const dgla_csr* csr);
+int dgla_csr_sorted_columns(const dgla_csr* csr, void* member, void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_node2vec_walk(const dgla_csr* csr, const double* cdf, const void* member, const void* seeds, int64_t num_seeds,
+                       int64_t num_steps, double p, double q, uint64_t rng_seed, void* traces, void* eids,
+                       void* hip_stream);
+int dgla_node2vec_walk_host(const dgla_csr* csr, const double* cdf, const void* member, const void* seeds,
+                            int64_t num_seeds, int64_t num_steps, double p, double q, uint64_t rng_seed, void* traces,
+                            void* eids, int64_t* stats);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
