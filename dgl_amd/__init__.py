@@ -23,7 +23,8 @@ from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401
 from .sampling import (EID, NID, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
-                       node2vec_random_walk, to_block)
+                       global_uniform_negative_sampling, node2vec_random_walk, to_block)
+from . import negative_sampler  # noqa: E402,F401
 from .mm import gather_mm, segment_mm  # noqa: E402,F401
 from .segment import scatter_add, segment_reduce, segment_softmax  # noqa: E402,F401
 from .sparse_kernels import release_static, set_auto_edge_operand, static_features  # noqa: E402,F401

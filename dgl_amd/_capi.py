@@ -750,6 +750,80 @@ def node2vec_walk_host(csr, cdf, member, seeds, num_steps, p, q, rng_seed=0, ret
     return (traces, eids, [int(c) for c in counters]) if stats else (traces, eids)
 
 
+def _member_ok(csr, member):
+    if member is None or _idbits(member) != csr.idtype_bits or member.numel() != csr.nnz or not member.is_contiguous():
+        raise _lib.DGLAMDError("member must be a contiguous tensor of the csr's id type with one entry per edge")
+
+
+def _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed):
+    """The argument list the device and the host negative sampler share (outputs on the device of `csr`'s indptr)."""
+    _member_ok(csr, member)
+    indptr = csr._keep[0]
+    n_slots, num_samples = int(n_slots), int(num_samples)
+    if n_slots < 0 or num_samples < 0:
+        raise _lib.DGLAMDError("the number of slots / samples must not be negative")
+    src = torch.empty(num_samples, dtype=indptr.dtype, device=indptr.device)
+    dst = torch.empty(num_samples, dtype=indptr.dtype, device=indptr.device)
+    count = torch.empty(1, dtype=torch.int64, device=indptr.device)
+    args = [ctypes.byref(csr), member.data_ptr(), n_slots, num_samples, int(num_trials), 1 if exclude_self_loops else 0,
+            1 if replace else 0, int(rng_seed) & 0xFFFFFFFFFFFFFFFF, src.data_ptr(), dst.data_ptr(), count.data_ptr()]
+    return args, src, dst, count
+
+
+def negative_sample(csr, member, n_slots, num_samples, num_trials=3, exclude_self_loops=True, replace=False, rng_seed=0):
+    """Global uniform negative pairs of the out-edge CSR `csr` (dgla_negative_sample): `member` from
+    :func:`csr_sorted_columns`.  Returns ``(src [num_samples], dst [num_samples], count [1] int64)`` on the device; the
+    entries from ``count`` on are -1.  Nothing is read back and nothing is allocated by the library (the workspace is a
+    torch tensor), so the call can be captured in a graph."""
+    _require_gpu(csr._keep[0])
+    _require_gpu(member)
+    args, src, dst, count = _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed)
+    need = LIB.dgla_negative_sample_workspace_bytes(csr.idtype_bits, int(n_slots))
+    ws = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
+    check_call(LIB.dgla_negative_sample(*args, _ptr(ws), need, _stream(src)))
+    return src, dst, count
+
+
+def negative_sample_host(csr, member, n_slots, num_samples, num_trials=3, exclude_self_loops=True, replace=False,
+                         rng_seed=0):
+    """:func:`negative_sample` run by the CPU on CPU tensors (dgla_negative_sample_host; `csr` built with
+    :func:`host_csr`): the same rule compiled for the host, bit for bit what the kernels write.  Needs no GPU."""
+    if member.is_cuda:
+        raise _lib.DGLAMDError("negative_sample_host takes CPU tensors")
+    args, src, dst, count = _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed)
+    check_call(LIB.dgla_negative_sample_host(*args))
+    return src, dst, count
+
+
+def _has_edges_args(csr, member, u, v):
+    _member_ok(csr, member)
+    if u.shape != v.shape or u.dim() != 1 or _idbits(u) != csr.idtype_bits or _idbits(v) != csr.idtype_bits or \
+            not u.is_contiguous() or not v.is_contiguous():
+        raise _lib.DGLAMDError("u and v must be contiguous 1-D tensors of the csr's id type and of one length")
+    out = torch.empty(u.shape[0], dtype=torch.uint8, device=u.device)
+    return [ctypes.byref(csr), member.data_ptr(), u.data_ptr(), v.data_ptr(), u.shape[0], out.data_ptr()], out
+
+
+def csr_has_edges(csr, member, u, v):
+    """Whether u[i] -> v[i] is an edge of `csr` (dgla_csr_has_edges), as a bool tensor: a bisection of the membership
+    list of :func:`csr_sorted_columns`; ids out of range give False.  Nothing is read back."""
+    for t in (member, u, v):
+        _require_gpu(t)
+    args, out = _has_edges_args(csr, member, u, v)
+    check_call(LIB.dgla_csr_has_edges(*args, _stream(u)))
+    return out.view(torch.bool)
+
+
+def csr_has_edges_host(csr, member, u, v):
+    """:func:`csr_has_edges` on CPU tensors (dgla_csr_has_edges_host).  Needs no GPU."""
+    for t in (member, u, v):
+        if t.is_cuda:
+            raise _lib.DGLAMDError("csr_has_edges_host takes CPU tensors")
+    args, out = _has_edges_args(csr, member, u, v)
+    check_call(LIB.dgla_csr_has_edges_host(*args))
+    return out.view(torch.bool)
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

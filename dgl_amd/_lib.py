@@ -247,6 +247,18 @@ LIB.dgla_node2vec_walk.restype = c_int
 LIB.dgla_node2vec_walk.argtypes = _N2V_ARGS + [c_void_p]
 LIB.dgla_node2vec_walk_host.restype = c_int
 LIB.dgla_node2vec_walk_host.argtypes = _N2V_ARGS + [P(c_int64)]
+# csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, seed, out_src, out_dst, out_count
+_NEG_ARGS = [P(CSR), c_void_p, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]
+LIB.dgla_negative_sample_workspace_bytes.restype = c_size_t
+LIB.dgla_negative_sample_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_negative_sample.restype = c_int
+LIB.dgla_negative_sample.argtypes = _NEG_ARGS + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_negative_sample_host.restype = c_int
+LIB.dgla_negative_sample_host.argtypes = _NEG_ARGS
+LIB.dgla_csr_has_edges.restype = c_int
+LIB.dgla_csr_has_edges.argtypes = [P(CSR), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+LIB.dgla_csr_has_edges_host.restype = c_int
+LIB.dgla_csr_has_edges_host.argtypes = [P(CSR), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -667,7 +667,12 @@ class DGLGraph:
         return order[at].to(g.idtype)
 
     def has_edges_between(self, u, v, etype=None):
-        """Whether an edge u -> v exists, pair by pair (heterograph.py has_edges_between)."""
+        """Whether an edge u -> v exists, pair by pair (heterograph.py has_edges_between).  On a GPU graph: one
+        bisection per pair in the relation's cached membership list (dgla_csr_has_edges, csrc/negative_sampling.hip)
+        instead of a sort of all edges per call."""
+        if self.device.type == "cuda":
+            from .sampling import _has_edges
+            return _has_edges(self._graph.relations[self.get_etype_id(etype)], self._ids(u), self._ids(v))
         g = self if len(self._canonical_etypes) == 1 else self[etype]
         u, v = g._ids(u), g._ids(v)
         src, dst = g.edges()

@@ -13,7 +13,8 @@ block keeps one source and one destination node set per node type (R-GCN mini-ba
 (python/dgl/sampling/randomwalks.py:31-310) over csrc/random_walk.hip: metapath, weighted and restart walks.
 ``RandomWalkNeighborSampler`` / ``PinSAGESampler`` mirror python/dgl/sampling/pinsage.py:27-272: those walks followed by
 the visit-count top-k of csrc/pinsage.hip.  ``node2vec_random_walk`` mirrors python/dgl/sampling/node2vec_randomwalk.py
-over csrc/node2vec.hip: the bounded second-order step of csrc/node2vec_step.h.
+over csrc/node2vec.hip: the bounded second-order step of csrc/node2vec_step.h.  ``global_uniform_negative_sampling`` mirrors
+python/dgl/sampling/negative.py over csrc/negative_sampling.hip (the rule: csrc/negative_sample_step.h).
 """
 import math
 
@@ -640,6 +641,103 @@ def node2vec_random_walk(g, nodes, p, q, walk_length, prob=None, return_eids=Fal
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     traces, eids = _capi.node2vec_walk(csr, cdf, member, nodes, walk_length, p, q, int(seed), return_eids)
     return (traces, eids) if return_eids else traces
+
+
+# ---- negative sampling ---------------------------------------------------------------------------
+NEGATIVE_SAMPLING_TRIALS = 3     # trials per slot, as in the reference (python/dgl/sampling/negative.py)
+
+
+def _negative_redundancy(k_hat, num_edges, num_pairs, r=3):
+    """How many more slots than samples to draw: the reference's ``_calc_redundancy`` in closed form.  With
+    ``p_m = num_edges / num_pairs`` and ``p_k = 1 - p_m`` the chance that a pair is no edge, it solves
+    ``k_hat = N p_k - r sqrt(N p_k p_m)`` for N, the larger root ``(-b + sqrt(b^2 - 4ac)) / 2a`` of ``a N^2 + b N + c``
+    with ``a = p_k^2``, ``b = -p_k (2 k_hat + r^2 p_m)``, ``c = k_hat^2``, and returns ``N / k_hat - 1``.  The
+    discriminant is taken in its factored form ``p_k^2 r^2 p_m (4 k_hat + r^2 p_m)``: the subtraction ``b^2 - 4ac`` loses
+    ten digits on a sparse graph."""
+    p_m = num_edges / num_pairs
+    p_k = 1 - p_m
+    n = (2 * k_hat + r ** 2 * p_m + r * math.sqrt(p_m * (4 * k_hat + r ** 2 * p_m))) / (2 * p_k)
+    return n / k_hat - 1.0
+
+
+def _relation_lookup(rel):
+    """``(dgla_csr, membership list)`` of relation ``rel``: the list is the slot :func:`node2vec_random_walk` uses; the
+    struct is kept next to it under the same key, so a small lookup does not pay for building it on every call."""
+    fmt = rel.csr()
+    key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device) for t in fmt[:2])
+    slot = getattr(rel, "_walk_csr", None)
+    if slot is None or slot[0] != key:
+        slot = rel._walk_csr = (key, _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst))    # (refuses a CPU graph)
+    return slot[1], _walk_members(rel, fmt, slot[1])
+
+
+def _has_edges(rel, u, v):
+    """``DGLGraph.has_edges_between`` on a GPU graph: ``u``, ``v`` 1-D id tensors of the graph's id type."""
+    if u.numel() != v.numel():
+        u, v = torch.broadcast_tensors(u, v)
+    csr, member = _relation_lookup(rel)
+    return _capi.csr_has_edges(csr, member, u.contiguous(), v.contiguous())
+
+
+def global_uniform_negative_sampling(g, num_samples, exclude_self_loops=True, replace=False, etype=None, redundancy=None,
+                                     seed=None, padded=False):
+    """``dgl.sampling.global_uniform_negative_sampling`` (python/dgl/sampling/negative.py): up to ``num_samples``
+    pairs ``(src, dst)``, ``src`` uniform over the source nodes and ``dst`` over the destination nodes of edge type
+    ``etype``, such that no edge ``src -> dst`` of that type exists.  ``exclude_self_loops`` also drops ``src == dst``
+    (only when the source and destination node types are equal); without ``replace`` the pairs are distinct.  Fewer than
+    ``num_samples`` pairs may come back when the graph is small or dense.
+
+    The pairs are drawn on the device (csrc/negative_sampling.hip; the rule: include/dgl_amd.h):
+    ``n_slots = int(num_samples * (1 + redundancy))`` slots make up to three uniform draws each and keep the first that
+    is no edge, by a bisection of the relation's membership list (built once per relation, shared with
+    :func:`node2vec_random_walk` and ``has_edges_between``).  ``redundancy=None`` takes the reference's estimate from the
+    density of the graph; a value the caller gives is honoured (the reference overwrites it).
+
+    **Order of the result.**  The reference sorts the pairs it drew and, without ``replace``, returns the
+    lexicographically smallest ``num_samples`` of the distinct ones, a sample biased toward small source ids.  Here the
+    accepted slots stay in slot order and the first occurrence of every pair is kept, so cutting the list at
+    ``num_samples`` is an unbiased sample without replacement, and the result for a smaller ``num_samples`` is a prefix
+    of the result for a larger one at the same number of slots.
+
+    Returns ``(src, dst)`` cut to the number of pairs found, which costs one read of that number by the host.
+    ``padded=True`` returns ``(src, dst, count)`` instead: both tensors of length ``num_samples`` with -1 from ``count``
+    (a 1-element int64 device tensor) on, nothing read back, usable inside a graph capture once the relation's
+    membership list exists.  ``seed`` as in :func:`random_walk`."""
+    num_samples = int(num_samples)
+    if num_samples < 0:
+        raise _DGLError("global_uniform_negative_sampling: num_samples must not be negative")
+    if etype is None:
+        etype = g.canonical_etypes[0]
+    utype, _, vtype = g.to_canonical_etype(etype)
+    exclude_self_loops = bool(exclude_self_loops) and utype == vtype
+    rel = g._graph.relations[g.get_etype_id(etype)]
+    dev, idt = g.device, g.idtype
+    if dev.type != "cuda":
+        raise _DGLError("global_uniform_negative_sampling runs on a ROCm GPU; the graph is on %s (no CPU fallback)" % dev)
+    num_pairs, num_edges = rel.num_src * rel.num_dst, rel.num_edges
+    n_slots = 0
+    if num_samples > 0 and num_pairs > num_edges:     # (a relation in which every pair is an edge has no negatives)
+        if redundancy is None:
+            redundancy = _negative_redundancy(num_samples, num_edges, num_pairs)
+        redundancy = float(redundancy)
+        if not (math.isfinite(redundancy) and redundancy >= 0):
+            raise _DGLError("global_uniform_negative_sampling: redundancy must be finite and >= 0, got %r" % redundancy)
+        n_slots = int(num_samples * (1 + redundancy))
+    if n_slots == 0:
+        src = torch.full((num_samples if padded else 0,), -1, dtype=idt, device=dev)
+        return (src, src.clone(), torch.zeros(1, dtype=torch.int64, device=dev)) if padded else (src, src.clone())
+    csr, member = _relation_lookup(rel)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    src, dst, count = _capi.negative_sample(csr, member, n_slots, num_samples, NEGATIVE_SAMPLING_TRIALS,
+                                            exclude_self_loops, replace, int(seed))
+    if padded:
+        return src, dst, count
+    k = int(count.item())
+    return src[:k], dst[:k]
+
+
+DGLGraph.global_uniform_negative_sampling = global_uniform_negative_sampling
 
 
 def pack_traces(traces, types):

@@ -693,6 +693,66 @@ int dgla_node2vec_walk_host(const dgla_csr* csr, const double* cdf, const void* 
                             int64_t num_seeds, int64_t num_steps, double p, double q, uint64_t rng_seed, void* traces,
                             void* eids, int64_t* stats);
 
+/* ---- Negative sampling: global uniform pairs and the edge lookup (csrc/negative_sampling.hip) -----
+ * Replace CSRGlobalUniformNegativeSampling<kDGLCUDA> (src/array/cuda/negative_sampling.cu, behind
+ * dgl.sampling.global_uniform_negative_sampling, python/dgl/sampling/negative.py) and the search behind
+ * DGLGraph.has_edges_between.  The reference draws with Philox, selects with cub and, without replacement, sorts the
+ * pairs and returns the lexicographically smallest num_samples of them; here the first occurrences are kept in slot
+ * order, so the truncation is an unbiased sample.  The generator and the draws are those of "Random walks" above.  The
+ * rule (ONE definition for device and host, csrc/negative_sample_step.h):
+ *
+ * Setting.  One relation as its out-edge CSR (R = num_rows source nodes, C = num_cols destination nodes, indptr) and
+ * its membership list member[nnz]: the column ids of every row in ascending order, duplicates kept, over the same
+ * indptr (dgla_csr_sorted_columns).  Parameters: n_slots >= 0 slots, num_samples >= 0 result entries, num_trials T in
+ * 1..64, the flags exclude_self_loops and replace, and a 64-bit seed.
+ *
+ * The rule:
+ *  1. Draw.  For slot i in [0, n_slots), trial t = 0 .. T-1:  s = rw_step_key(rw_walk_key(seed, i), t),
+ *     u = rw_index(rw_draw(s, 0), R), v = rw_index(rw_draw(s, 1), C).  The trial is rejected in either of two cases:
+ *     exclude_self_loops and u == v; or n2v_member(member, indptr[u], indptr[u+1], v) finds v (u -> v is an edge).
+ *     The first trial that is not rejected gives the slot its pair (u, v).  A slot with T rejections is empty.
+ *     R == 0 or C == 0 leaves every slot empty and reads no graph memory.
+ *  2. Accept.  A is the list of non-empty slots in ascending i.
+ *  3. Select.  With replace, the result is the first min(|A|, num_samples) pairs of A.  Without replace, first drop
+ *     from A every slot whose pair equals the pair of an earlier slot of A (first occurrences are kept, in slot order),
+ *     then take the first num_samples.
+ *  4. Pad.  out_src and out_dst have num_samples entries of the CSR's id type; the entries beyond the count are -1.
+ *     The count is one int64.
+ *
+ * What follows from the rule.  The result is a pure function of (graph, seed, n_slots, num_samples, T, flags),
+ * whatever the launch geometry.  The result for num_samples = k is a prefix of the result for k' > k at the same
+ * n_slots.  A slot's pair is uniform over the cells that are neither edges nor (when excluded) self-loops, slots are
+ * independent, and first occurrences are kept in slot order, so the truncation to num_samples is an unbiased sample
+ * without replacement.  How duplicates are found (a hash bucket sort on the device, a set on the host) is no part of
+ * the rule.
+ *
+ * Integer arithmetic and integer compares only: host and device agree bit for bit.
+ *
+ * dgla_negative_sample: csr->indptr, member, out_src[num_samples], out_dst[num_samples] (the CSR's id type) and
+ *   out_count (one int64) are device memory; csr->indices and csr->data are not read.  `workspace` must hold
+ *   dgla_negative_sample_workspace_bytes(idtype_bits, n_slots) bytes, a number that depends on n_slots only (50 to 100
+ *   bytes per slot; nothing is sized by num_rows, num_cols or nnz).  Everything is stream-ordered: no allocation,
+ *   nothing read back, no synchronisation, usable inside a hipGraph capture.  The accepted count stays on the device:
+ *   the duplicate search sorts all n_slots slots, the empty ones spread over the buckets by slot index and stepped over.
+ * dgla_negative_sample_host: the same arguments with every pointer in HOST memory, no workspace and no stream: the
+ *   whole rule run sequentially by the CPU, bit for bit what the kernels write.  Host-only: needs no GPU.
+ * dgla_csr_has_edges: out[i] = 1 iff 0 <= u[i] < R, 0 <= v[i] < C and the bisection of row u[i] of the membership list
+ *   finds v[i], else 0; u, v (the CSR's id type) and out (n bytes) are device memory.  An id out of range touches no
+ *   memory.  dgla_csr_has_edges_host: the same on host memory.
+ * All fail with -1 and a message, before any launch, for a NULL csr / indptr / member / output, an id width other than
+ *   32 / 64, negative sizes, num_trials outside 1..64, n_slots or num_samples >= 2^31 and a workspace that is too small.
+ *   n_slots == 0 and num_samples == 0 are valid. */
+size_t dgla_negative_sample_workspace_bytes(int idtype_bits, int64_t n_slots);
+int dgla_negative_sample(const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
+                         int exclude_self_loops, int replace, uint64_t seed, void* out_src, void* out_dst,
+                         int64_t* out_count, void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_negative_sample_host(const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
+                              int exclude_self_loops, int replace, uint64_t seed, void* out_src, void* out_dst,
+                              int64_t* out_count);
+int dgla_csr_has_edges(const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n, uint8_t* out,
+                       void* hip_stream);
+int dgla_csr_has_edges_host(const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n, uint8_t* out);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with

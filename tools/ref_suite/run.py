@@ -42,7 +42,7 @@ MP_FILES = ["python/common/test_heterograph-update-all.py", "python/common/test_
             "python/common/transforms/test_to_block.py"]
 SAMPLING_FILE = "python/common/sampling/test_sampling.py"
 SAMPLING_SELECT = ["test_sample_neighbors_noprob", "test_sample_neighbors_prob", "test_sample_neighbors_outedge",
-                   "test_sample_neighbors_with_0deg"]
+                   "test_sample_neighbors_with_0deg", "test_global_uniform_negative_sampling"]
 NN_FILE = "python/pytorch/nn/test_nn.py"
 NN_SELECT = ["test_graph_conv0", "test_graph_conv", "test_graph_conv_e_weight", "test_graph_conv_e_weight_norm",
              "test_graph_conv_bi", "test_sage_conv", "test_sage_conv_bi", "test_sage_conv2", "test_gat_conv",
