@@ -55,6 +55,35 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _u64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF   # (negative seeds wrap)
+
+
+def _workspace(need, device):
+    return torch.empty(need, dtype=torch.uint8, device=device) if need else None   # (None: the call needs none)
+
+
+def _all_on(gpu, who, *tensors):
+    """The device twin of an entry point takes GPU tensors, the host twin `who` CPU tensors; None entries are skipped."""
+    for t in tensors:
+        if t is None:
+            continue
+        if gpu:
+            _require_gpu(t)
+        elif t.is_cuda:
+            raise _lib.DGLAMDError("%s takes CPU tensors" % who)
+
+
+def _prob_ok(prob):
+    if prob.dtype not in (torch.float32, torch.float64) or prob.dim() != 1 or not prob.is_contiguous():
+        raise _lib.DGLAMDError("prob must be a contiguous 1-D float32 / float64 tensor")
+
+
+def _member_ok(csr, member):
+    if member is None or _idbits(member) != csr.idtype_bits or member.numel() != csr.nnz or not member.is_contiguous():
+        raise _lib.DGLAMDError("member must be a contiguous tensor of the csr's id type with one entry per edge")
+
+
 def make_csr(indptr, indices, eids, num_cols):
     _require_gpu(indptr)
     c = CSR(indptr.shape[0] - 1, int(num_cols), indices.shape[0], _idbits(indptr),
@@ -576,7 +605,7 @@ def sample_neighbors(csr, seeds, fanout, replace=False, rng_seed=0):
     """Uniform in-neighbour sampling over the in-edge CSR `csr` (dgla_sample_neighbors):
     returns ``(indptr, src, eids)`` — a CSR over the seeds with GLOBAL source / edge ids."""
     _require_gpu(seeds)
-    rng_seed = int(rng_seed) & 0xFFFFFFFFFFFFFFFF
+    rng_seed = _u64(rng_seed)
     n = seeds.shape[0]
     dev, dt = seeds.device, seeds.dtype
     indptr = torch.empty(n + 1, dtype=dt, device=dev)
@@ -600,9 +629,8 @@ def sample_neighbors_weighted(csr, prob, seeds, fanout, replace=False, rng_seed=
     edges of weight 0 never appear, so rows may hold fewer than `fanout` entries."""
     _require_gpu(seeds)
     _require_gpu(prob)
-    if prob.dtype not in (torch.float32, torch.float64) or prob.dim() != 1 or not prob.is_contiguous():
-        raise _lib.DGLAMDError("prob must be a contiguous 1-D float32 / float64 tensor")
-    rng_seed = int(rng_seed) & 0xFFFFFFFFFFFFFFFF
+    _prob_ok(prob)
+    rng_seed = _u64(rng_seed)
     n = seeds.shape[0]
     dev, dt = seeds.device, seeds.dtype
     indptr = torch.empty(n + 1, dtype=dt, device=dev)
@@ -629,13 +657,12 @@ def random_walk_cdf(csr, prob):
     """The row-wise inclusive sums of the weights of `csr` (dgla_random_walk_cdf): float64 [nnz] in CSR position order,
     what the weighted step of :func:`random_walk` bisects.  `prob` is float32 / float64, one weight per EDGE ID."""
     _require_gpu(prob)
-    if prob.dtype not in (torch.float32, torch.float64) or prob.dim() != 1 or not prob.is_contiguous():
-        raise _lib.DGLAMDError("prob must be a contiguous 1-D float32 / float64 tensor")
+    _prob_ok(prob)
     if prob.shape[0] != csr.nnz:
         raise _lib.DGLAMDError("prob must hold one value per edge (%d), got %d" % (csr.nnz, prob.shape[0]))
     cdf = torch.empty(csr.nnz, dtype=torch.float64, device=prob.device)
     need = LIB.dgla_random_walk_cdf_workspace_bytes(ctypes.byref(csr))
-    ws = torch.empty(need, dtype=torch.uint8, device=prob.device) if need else None
+    ws = _workspace(need, prob.device)
     check_call(LIB.dgla_random_walk_cdf(ctypes.byref(csr), prob.data_ptr(), _DTYPES[prob.dtype], cdf.data_ptr(),
                                         _ptr(ws), need, _stream(prob)))
     return cdf
@@ -660,7 +687,7 @@ def _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, ret
     eids = torch.empty((n, steps), dtype=seeds.dtype, device=seeds.device) if return_eids else None
     args = [table if rels else None, len(rels), path, steps, seeds.data_ptr(), n, float(restart_prob or 0.0),
             _ptr(restart_steps), _DTYPES[restart_steps.dtype] if restart_steps is not None else 0,
-            int(rng_seed) & 0xFFFFFFFFFFFFFFFF, traces.data_ptr(), _ptr(eids)]
+            _u64(rng_seed), traces.data_ptr(), _ptr(eids)]
     return args, traces, eids, (table, path, rels)
 
 
@@ -668,15 +695,12 @@ def random_walk(rels, metapath, seeds, restart_prob=0.0, restart_steps=None, rng
     """Random walks over the out-edge CSRs `rels` = [(dgla_csr, cdf or None), ...] along `metapath` (relation indices),
     one walk per entry of `seeds` (dgla_random_walk).  Returns ``(traces [n, steps + 1], eids [n, steps] or None)``;
     a walk that halts is padded with -1.  Nothing is read back."""
-    _require_gpu(seeds)
-    for t in [restart_steps] + [c for _, c in rels]:
-        if t is not None:
-            _require_gpu(t)
+    _all_on(True, "random_walk", seeds, restart_steps, *[c for _, c in rels])
     if not seeds.is_contiguous() or (rels and _idbits(seeds) != rels[0][0].idtype_bits):
         raise _lib.DGLAMDError("seeds must be contiguous and of the relations' id type")
     args, traces, eids, keep = _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, return_eids)
     need = LIB.dgla_random_walk_workspace_bytes(len(rels), len(metapath))
-    ws = torch.empty(need, dtype=torch.uint8, device=seeds.device) if need else None
+    ws = _workspace(need, seeds.device)
     check_call(LIB.dgla_random_walk(*args, _ptr(ws), need, _stream(seeds)))
     return traces, eids
 
@@ -684,9 +708,7 @@ def random_walk(rels, metapath, seeds, restart_prob=0.0, restart_steps=None, rng
 def random_walk_host(rels, metapath, seeds, restart_prob=0.0, restart_steps=None, rng_seed=0, return_eids=True):
     """:func:`random_walk` run by the CPU on CPU tensors (dgla_random_walk_host; `rels` built with :func:`host_csr`):
     the same step rule compiled for the host, bit for bit what the kernel writes.  Needs no GPU."""
-    for t in [seeds, restart_steps] + [c for _, c in rels]:
-        if t is not None and t.is_cuda:
-            raise _lib.DGLAMDError("random_walk_host takes CPU tensors")
+    _all_on(False, "random_walk_host", seeds, restart_steps, *[c for _, c in rels])
     if not seeds.is_contiguous() or (rels and _idbits(seeds) != rels[0][0].idtype_bits):
         raise _lib.DGLAMDError("seeds must be contiguous and of the relations' id type")
     args, traces, eids, keep = _walk_args(rels, metapath, seeds, restart_prob, restart_steps, rng_seed, return_eids)
@@ -702,7 +724,7 @@ def csr_sorted_columns(csr):
     _require_gpu(indptr)
     member = torch.empty(csr.nnz, dtype=indptr.dtype, device=indptr.device)
     need = LIB.dgla_csr_sorted_columns_workspace_bytes(ctypes.byref(csr))
-    ws = torch.empty(need, dtype=torch.uint8, device=indptr.device) if need else None
+    ws = _workspace(need, indptr.device)
     check_call(LIB.dgla_csr_sorted_columns(ctypes.byref(csr), member.data_ptr(), _ptr(ws), need, _stream(indptr)))
     return member
 
@@ -711,8 +733,7 @@ def _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids):
     """The argument list the device and the host node2vec walker share."""
     if cdf is not None and (cdf.dtype != torch.float64 or cdf.numel() != csr.nnz or not cdf.is_contiguous()):
         raise _lib.DGLAMDError("the cdf must be a contiguous float64 tensor with one entry per edge")
-    if member is None or _idbits(member) != csr.idtype_bits or member.numel() != csr.nnz or not member.is_contiguous():
-        raise _lib.DGLAMDError("member must be a contiguous tensor of the csr's id type with one entry per edge")
+    _member_ok(csr, member)
     if not seeds.is_contiguous() or _idbits(seeds) != csr.idtype_bits:
         raise _lib.DGLAMDError("seeds must be contiguous and of the csr's id type")
     n, steps = seeds.shape[0], int(num_steps)
@@ -721,7 +742,7 @@ def _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids):
     traces = torch.empty((n, steps + 1), dtype=seeds.dtype, device=seeds.device)
     eids = torch.empty((n, steps), dtype=seeds.dtype, device=seeds.device) if return_eids else None
     args = [ctypes.byref(csr), _ptr(cdf), member.data_ptr(), seeds.data_ptr(), n, steps, float(p), float(q),
-            int(rng_seed) & 0xFFFFFFFFFFFFFFFF, traces.data_ptr(), _ptr(eids)]
+            _u64(rng_seed), traces.data_ptr(), _ptr(eids)]
     return args, traces, eids
 
 
@@ -729,9 +750,7 @@ def node2vec_walk(csr, cdf, member, seeds, num_steps, p, q, rng_seed=0, return_e
     """node2vec walks over the out-edge CSR `csr` (dgla_node2vec_walk): `cdf` from :func:`random_walk_cdf` or None,
     `member` from :func:`csr_sorted_columns`.  Returns ``(traces [n, steps + 1], eids [n, steps] or None)``; a walk that
     halts is padded with -1.  Nothing is read back."""
-    for t in (seeds, member, cdf):
-        if t is not None:
-            _require_gpu(t)
+    _all_on(True, "node2vec_walk", seeds, member, cdf)
     args, traces, eids = _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids)
     check_call(LIB.dgla_node2vec_walk(*args, _stream(seeds)))
     return traces, eids
@@ -741,18 +760,11 @@ def node2vec_walk_host(csr, cdf, member, seeds, num_steps, p, q, rng_seed=0, ret
     """:func:`node2vec_walk` run by the CPU on CPU tensors (dgla_node2vec_walk_host; `csr` built with :func:`host_csr`):
     the same step rule compiled for the host, bit for bit what the kernel writes.  Needs no GPU.  With ``stats`` a third
     result ``[steps t >= 1 that recorded a node, candidates drawn, steps that reached the scan]``."""
-    for t in (seeds, member, cdf):
-        if t is not None and t.is_cuda:
-            raise _lib.DGLAMDError("node2vec_walk_host takes CPU tensors")
+    _all_on(False, "node2vec_walk_host", seeds, member, cdf)
     args, traces, eids = _n2v_args(csr, cdf, member, seeds, num_steps, p, q, rng_seed, return_eids)
     counters = (ctypes.c_int64 * 3)() if stats else None
     check_call(LIB.dgla_node2vec_walk_host(*args, counters))
     return (traces, eids, [int(c) for c in counters]) if stats else (traces, eids)
-
-
-def _member_ok(csr, member):
-    if member is None or _idbits(member) != csr.idtype_bits or member.numel() != csr.nnz or not member.is_contiguous():
-        raise _lib.DGLAMDError("member must be a contiguous tensor of the csr's id type with one entry per edge")
 
 
 def _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed):
@@ -766,7 +778,7 @@ def _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops,
     dst = torch.empty(num_samples, dtype=indptr.dtype, device=indptr.device)
     count = torch.empty(1, dtype=torch.int64, device=indptr.device)
     args = [ctypes.byref(csr), member.data_ptr(), n_slots, num_samples, int(num_trials), 1 if exclude_self_loops else 0,
-            1 if replace else 0, int(rng_seed) & 0xFFFFFFFFFFFFFFFF, src.data_ptr(), dst.data_ptr(), count.data_ptr()]
+            1 if replace else 0, _u64(rng_seed), src.data_ptr(), dst.data_ptr(), count.data_ptr()]
     return args, src, dst, count
 
 
@@ -775,11 +787,10 @@ def negative_sample(csr, member, n_slots, num_samples, num_trials=3, exclude_sel
     :func:`csr_sorted_columns`.  Returns ``(src [num_samples], dst [num_samples], count [1] int64)`` on the device; the
     entries from ``count`` on are -1.  Nothing is read back and nothing is allocated by the library (the workspace is a
     torch tensor), so the call can be captured in a graph."""
-    _require_gpu(csr._keep[0])
-    _require_gpu(member)
+    _all_on(True, "negative_sample", csr._keep[0], member)
     args, src, dst, count = _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed)
     need = LIB.dgla_negative_sample_workspace_bytes(csr.idtype_bits, int(n_slots))
-    ws = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
+    ws = _workspace(need, src.device)
     check_call(LIB.dgla_negative_sample(*args, _ptr(ws), need, _stream(src)))
     return src, dst, count
 
@@ -788,8 +799,7 @@ def negative_sample_host(csr, member, n_slots, num_samples, num_trials=3, exclud
                          rng_seed=0):
     """:func:`negative_sample` run by the CPU on CPU tensors (dgla_negative_sample_host; `csr` built with
     :func:`host_csr`): the same rule compiled for the host, bit for bit what the kernels write.  Needs no GPU."""
-    if member.is_cuda:
-        raise _lib.DGLAMDError("negative_sample_host takes CPU tensors")
+    _all_on(False, "negative_sample_host", member)
     args, src, dst, count = _neg_args(csr, member, n_slots, num_samples, num_trials, exclude_self_loops, replace, rng_seed)
     check_call(LIB.dgla_negative_sample_host(*args))
     return src, dst, count
@@ -807,8 +817,7 @@ def _has_edges_args(csr, member, u, v):
 def csr_has_edges(csr, member, u, v):
     """Whether u[i] -> v[i] is an edge of `csr` (dgla_csr_has_edges), as a bool tensor: a bisection of the membership
     list of :func:`csr_sorted_columns`; ids out of range give False.  Nothing is read back."""
-    for t in (member, u, v):
-        _require_gpu(t)
+    _all_on(True, "csr_has_edges", member, u, v)
     args, out = _has_edges_args(csr, member, u, v)
     check_call(LIB.dgla_csr_has_edges(*args, _stream(u)))
     return out.view(torch.bool)
@@ -816,9 +825,7 @@ def csr_has_edges(csr, member, u, v):
 
 def csr_has_edges_host(csr, member, u, v):
     """:func:`csr_has_edges` on CPU tensors (dgla_csr_has_edges_host).  Needs no GPU."""
-    for t in (member, u, v):
-        if t.is_cuda:
-            raise _lib.DGLAMDError("csr_has_edges_host takes CPU tensors")
+    _all_on(False, "csr_has_edges_host", member, u, v)
     args, out = _has_edges_args(csr, member, u, v)
     check_call(LIB.dgla_csr_has_edges_host(*args))
     return out.view(torch.bool)
@@ -880,7 +887,7 @@ def select_pinsage_neighbors(src, dst, num_samples_per_node, k):
     _require_gpu(src)
     _require_gpu(dst)
     need = LIB.dgla_pinsage_select_workspace_bytes(bits, n, S, k)
-    ws = torch.empty(need, dtype=torch.uint8, device=src.device)
+    ws = _workspace(need, src.device)
     total = ctypes.c_int64(0)
     st = _stream(src)
     check_call(LIB.dgla_pinsage_select_count(bits, _ptr(src), _ptr(dst), n, S, k, ctypes.byref(total), _ptr(ws), need, st))
@@ -893,8 +900,7 @@ def select_pinsage_neighbors_host(src, dst, num_samples_per_node, k):
     """:func:`select_pinsage_neighbors` run by the CPU on CPU tensors (dgla_pinsage_select_host): a plain restatement
     of the rule, what the kernel is tested against.  Needs no GPU and accepts any ``num_samples_per_node``."""
     bits, n, S, k, kp = _pinsage_args("select_pinsage_neighbors_host", src, dst, num_samples_per_node, k, False)
-    if src.is_cuda or dst.is_cuda:
-        raise _lib.DGLAMDError("select_pinsage_neighbors_host takes CPU tensors")
+    _all_on(False, "select_pinsage_neighbors_host", src, dst)
     res = [torch.empty(n * kp, dtype=src.dtype) for _ in range(3)]
     total = ctypes.c_int64(0)
     check_call(LIB.dgla_pinsage_select_host(bits, _ptr(src), _ptr(dst), n, S, k, _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
@@ -915,7 +921,7 @@ def to_block(seeds, src, node_map):
     src_nodes = torch.empty(n + nnz, dtype=dt, device=dev)
     num = torch.empty(1, dtype=torch.int64, device=dev)
     if n > 0:
-        ws = torch.empty(max(1, LIB.dgla_to_block_workspace_bytes(_idbits(seeds), nnz)), dtype=torch.uint8, device=dev)
+        ws = _workspace(max(1, LIB.dgla_to_block_workspace_bytes(_idbits(seeds), nnz)), dev)
         check_call(LIB.dgla_to_block_padded(_idbits(seeds), seeds.data_ptr(), n, None, _ptr(src), nnz,
                                             int(node_map.shape[0]), node_map.data_ptr(), _ptr(local),
                                             src_nodes.data_ptr(), num.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -945,16 +951,14 @@ def sample_neighbors_padded(csr, seeds, num_valid, fanout, replace=False, rng_se
     indptr = torch.empty(n + 1 + int(sink_rows), dtype=dt, device=dev)
     src = torch.empty(cap, dtype=dt, device=dev)
     eids = torch.empty(cap, dtype=dt, device=dev)
-    ws = torch.empty(max(1, LIB.dgla_sample_neighbors_workspace_bytes(_idbits(seeds), n)), dtype=torch.uint8,
-                     device=dev)
+    ws = _workspace(max(1, LIB.dgla_sample_neighbors_workspace_bytes(_idbits(seeds), n)), dev)
     if prob is not None:
         _require_gpu(prob)
-        if prob.dtype not in (torch.float32, torch.float64) or prob.dim() != 1 or not prob.is_contiguous():
-            raise _lib.DGLAMDError("prob must be a contiguous 1-D float32 / float64 tensor")
+        _prob_ok(prob)
     check_call(LIB.dgla_sample_neighbors_padded(
         ctypes.byref(csr), _ptr(prob), _DTYPES[prob.dtype] if prob is not None else 0, seeds.data_ptr(), n,
         _ptr(num_valid), int(fanout), 1 if replace else 0,
-        int(rng_seed) & 0xFFFFFFFFFFFFFFFF, _ptr(rng_counter), int(sink_rows), indptr.data_ptr(), src.data_ptr(),
+        _u64(rng_seed), _ptr(rng_counter), int(sink_rows), indptr.data_ptr(), src.data_ptr(),
         eids.data_ptr(),
         ws.data_ptr(), ws.numel(), _stream(seeds)))
     return indptr, src, eids
@@ -970,7 +974,7 @@ def to_block_padded(seeds, num_valid, src, node_map, fill=0, num_nodes=0):
     local = torch.empty(nnz, dtype=dt, device=dev)
     src_nodes = torch.full((n + nnz,), int(fill), dtype=dt, device=dev)
     num = torch.empty(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(1, LIB.dgla_to_block_workspace_bytes(_idbits(seeds), nnz)), dtype=torch.uint8, device=dev)
+    ws = _workspace(max(1, LIB.dgla_to_block_workspace_bytes(_idbits(seeds), nnz)), dev)
     check_call(LIB.dgla_to_block_padded(_idbits(seeds), seeds.data_ptr(), n, _ptr(num_valid), _ptr(src), nnz,
                                         int(num_nodes), node_map.data_ptr(), _ptr(local), src_nodes.data_ptr(), num.data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream(seeds)))

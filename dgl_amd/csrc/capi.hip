@@ -51,11 +51,6 @@ int launch_edge_softmax(const CsrView&, int, const void*, const void*, void*, in
                         void*, size_t, bool, hipStream_t, bool out_pos = false, bool b_is_grad = false);
 size_t edge_softmax_workspace_bytes(int64_t, int64_t, int, int64_t);
 
-static int fail(const std::string& msg) {
-  last_error() = msg;
-  return -1;
-}
-
 static int parse_op(const char* s, bool allow_dot) {
   if (!s) return -1;
   if (!strcmp(s, "add")) return kAdd;

@@ -207,6 +207,19 @@ inline int64_t spmm_num_waves(int64_t num_rows, int64_t nnz) {
 
 std::string& last_error();
 
+// The one way an entry point refuses a call: the message goes to dgla_last_error(), the entry point returns -1.
+inline int fail(const std::string& m) {
+  last_error() = m;
+  return -1;
+}
+
+// Every piece of a workspace starts on a 256-byte boundary.
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+// A read-only pointer that names the global address space (global_load instead of flat_load).
+template <typename T>
+using gptr = const __attribute__((address_space(1))) T*;
+
 // Optional HIP events recorded around the dominant (merge) kernel of dgla_spmm_csr, so a
 // benchmark can time that kernel alone on the launch stream (dgla_spmm_set_profile_events).
 struct ProfileEvents {

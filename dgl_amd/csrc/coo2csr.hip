@@ -16,16 +16,11 @@
 
 #include <cstring>
 
-#include "common.h"
+#include "host_util.h"
 #include "sort.hip.h"
 
 namespace dgla {
 namespace {
-
-int cfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
 
 template <typename Idx>
 __global__ void zero_indptr_kernel(Idx* indptr, int64_t n) {
@@ -78,28 +73,22 @@ size_t dgla_coo_to_csr_workspace_bytes(int idtype_bits, int64_t num_rows, int64_
 static int coo_to_csr_impl(int idtype_bits, int64_t num_rows, int64_t num_minor, int64_t nnz, const void* row,
                            const void* col, const void* eids, void* indptr, void* indices, void* eids_out,
                            void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return cfail("idtype must be int32 or int64");
-  if (num_rows < 0 || nnz < 0) return cfail("negative size");
-  if (!indptr) return cfail("indptr is null");
-  if (nnz > 0 && (!row || !col || !indices || !eids_out)) return cfail("coo / output arrays are null");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (num_rows < 0 || nnz < 0) return fail("negative size");
+  if (!indptr) return fail("indptr is null");
+  if (nnz > 0 && (!row || !col || !indices || !eids_out)) return fail("coo / output arrays are null");
   if (idtype_bits == 32 && (nnz > 0x7fffffffLL || num_rows > 0x7fffffffLL))
-    return cfail("int32 ids cannot address this many edges / rows");
+    return fail("int32 ids cannot address this many edges / rows");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, indptr);
   msd::Plan p;
   if (nnz > 0 && num_rows > 0) p = plan_for(idtype_bits, num_rows, num_minor, nnz);
-  void* owned = nullptr;
-  if (p.bytes && (!workspace || workspace_bytes < p.bytes)) {
-    DGLA_CHECK_HIP(hipMallocAsync(&owned, p.bytes, s));
-    workspace = owned;
-  }
-  const int rc = idtype_bits == 32
-                     ? run<int32_t>(p, num_rows, nnz, row, col, eids, indptr, indices, eids_out,
-                                    static_cast<char*>(workspace), s)
-                     : run<int64_t>(p, num_rows, nnz, row, col, eids, indptr, indices, eids_out,
-                                    static_cast<char*>(workspace), s);
-  if (owned) (void)hipFreeAsync(owned, s);
-  return rc;
+  Scratch ws(s);
+  ws.p = static_cast<char*>(workspace);   // (a call without a plan hands the caller's pointer through)
+  if (p.bytes && ws.take(workspace, workspace_bytes, p.bytes)) return -1;
+  return with_idx(idtype_bits, [&](auto tag) {
+    return run<decltype(tag)>(p, num_rows, nnz, row, col, eids, indptr, indices, eids_out, ws.p, s);
+  });
 }
 
 int dgla_coo_to_csr(int idtype_bits, int64_t num_rows, int64_t nnz, const void* row, const void* col,

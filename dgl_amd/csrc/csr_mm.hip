@@ -30,7 +30,7 @@
 
 #include <vector>
 
-#include "common.h"
+#include "host_util.h"
 #include "sort.hip.h"
 
 namespace dgla {
@@ -39,11 +39,6 @@ namespace spgemm {
 constexpr int kWaveMax = 64;       // terms of a row handled by one wavefront
 constexpr int kBlockMax = 2048;    // terms of a row handled by one workgroup in LDS (36 KiB with fp64 values: 4 per CU)
 constexpr int kSpaWindow = 4096;   // columns per dense-accumulator window (36 KiB with fp64 values)
-
-int fail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
 
 template <typename Idx>
 struct Operand {   // one CSR operand on the device
@@ -287,37 +282,14 @@ struct Layout {
 };
 inline Layout layout_for(int64_t num_rows, int n_ops, int idbits) {
   Layout l;
-  size_t o = 0;
-  l.off_ub = o;
-  o += msd::align256(sizeof(int64_t) * static_cast<size_t>(num_rows + 1));
-  l.off_cnt = o;
-  o += msd::align256(sizeof(int64_t) * static_cast<size_t>(num_rows + 1));
-  l.off_scan = o;
-  o += msd::scan_temp_bytes(num_rows + 1, sizeof(int64_t));
-  l.off_ops = o;
-  o += msd::align256((idbits == 32 ? sizeof(Operand<int32_t>) : sizeof(Operand<int64_t>)) * static_cast<size_t>(n_ops));
-  l.bytes = o;
+  Carver c;
+  l.off_ub = c.take(sizeof(int64_t) * static_cast<size_t>(num_rows + 1));
+  l.off_cnt = c.take(sizeof(int64_t) * static_cast<size_t>(num_rows + 1));
+  l.off_scan = c.take(msd::scan_temp_bytes(num_rows + 1, sizeof(int64_t)));
+  l.off_ops = c.take((idbits == 32 ? sizeof(Operand<int32_t>) : sizeof(Operand<int64_t>)) * static_cast<size_t>(n_ops));
+  l.bytes = c.bytes();
   return l;
 }
-
-struct Scratch {   // the caller's workspace, or stream-ordered scratch for the duration of the call
-  void* owned = nullptr;
-  char* p = nullptr;
-  hipStream_t s;
-  explicit Scratch(hipStream_t st) : s(st) {}
-  int take(void* ws, size_t have, size_t need) {
-    if (ws && have >= need) {
-      p = static_cast<char*>(ws);
-      return 0;
-    }
-    DGLA_CHECK_HIP(hipMallocAsync(&owned, need, s));
-    p = static_cast<char*>(owned);
-    return 0;
-  }
-  ~Scratch() {
-    if (owned) (void)hipFreeAsync(owned, s);
-  }
-};
 
 // the three class launches over all rows; terms == 0: nothing to do (every row is empty)
 template <typename Idx, typename T, typename Src, bool FILL>
@@ -564,11 +536,11 @@ int dgla_csr_mm_count(const dgla_csr* a, const dgla_csr* b, void* c_indptr, int6
   Scratch ws(s);
   if (ws.take(workspace, workspace_bytes, l.bytes)) return -1;
   const bool any = a->nnz > 0 && b->nnz > 0;
-  if (a->idtype_bits == 32)
-    return count_rows<int32_t>(MmSrc<int32_t, float>{operand_of<int32_t>(a, nullptr), operand_of<int32_t>(b, nullptr)},
-                               a->num_rows, any, c_indptr, nnz_out, ws.p, l, s);
-  return count_rows<int64_t>(MmSrc<int64_t, float>{operand_of<int64_t>(a, nullptr), operand_of<int64_t>(b, nullptr)},
-                             a->num_rows, any, c_indptr, nnz_out, ws.p, l, s);
+  return with_idx(a->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    return count_rows<Idx>(MmSrc<Idx, float>{operand_of<Idx>(a, nullptr), operand_of<Idx>(b, nullptr)}, a->num_rows, any,
+                           c_indptr, nnz_out, ws.p, l, s);
+  });
 }
 
 int dgla_csr_mm_fill(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dgla_csr* b, const void* b_w,
@@ -584,8 +556,9 @@ int dgla_csr_mm_fill(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const
   const Layout l = layout_for(a->num_rows, 0, a->idtype_bits);
   Scratch ws(s);
   if (ws.take(workspace, workspace_bytes, l.bytes)) return -1;
-  return a->idtype_bits == 32 ? mm_fill<int32_t>(a, dtype, a_w, b, b_w, c_indptr, c_indices, c_w, ws.p, l, s)
-                              : mm_fill<int64_t>(a, dtype, a_w, b, b_w, c_indptr, c_indices, c_w, ws.p, l, s);
+  return with_idx(a->idtype_bits, [&](auto tag) {
+    return mm_fill<decltype(tag)>(a, dtype, a_w, b, b_w, c_indptr, c_indices, c_w, ws.p, l, s);
+  });
 }
 
 size_t dgla_csr_sum_workspace_bytes(const dgla_csr* const* ops, int n) {
@@ -605,16 +578,13 @@ int dgla_csr_sum_count(const dgla_csr* const* ops, int n, void* c_indptr, int64_
   if (ws.take(workspace, workspace_bytes, l.bytes)) return -1;
   bool any = false;
   for (int k = 0; k < n; ++k) any = any || ops[k]->nnz > 0;
-  if (ops[0]->idtype_bits == 32) {
-    std::vector<Operand<int32_t>> host;
-    if (upload_ops<int32_t>(ops, nullptr, n, &host, ws.p + l.off_ops, s)) return -1;
-    return count_rows<int32_t>(SumSrc<int32_t, float>{reinterpret_cast<const Operand<int32_t>*>(ws.p + l.off_ops), n}, rows, any,
-                               c_indptr, nnz_out, ws.p, l, s);
-  }
-  std::vector<Operand<int64_t>> host;
-  if (upload_ops<int64_t>(ops, nullptr, n, &host, ws.p + l.off_ops, s)) return -1;
-  return count_rows<int64_t>(SumSrc<int64_t, float>{reinterpret_cast<const Operand<int64_t>*>(ws.p + l.off_ops), n}, rows, any,
-                             c_indptr, nnz_out, ws.p, l, s);
+  return with_idx(ops[0]->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    std::vector<Operand<Idx>> host;
+    if (upload_ops<Idx>(ops, nullptr, n, &host, ws.p + l.off_ops, s)) return -1;
+    return count_rows<Idx>(SumSrc<Idx, float>{reinterpret_cast<const Operand<Idx>*>(ws.p + l.off_ops), n}, rows, any,
+                           c_indptr, nnz_out, ws.p, l, s);
+  });
 }
 
 int dgla_csr_sum_fill(const dgla_csr* const* ops, int n, dgla_dtype dtype, const void* const* weights, const void* c_indptr,
@@ -634,19 +604,13 @@ int dgla_csr_sum_fill(const dgla_csr* const* ops, int n, dgla_dtype dtype, const
   const Layout l = layout_for(rows, n, ops[0]->idtype_bits);
   Scratch ws(s);
   if (ws.take(workspace, workspace_bytes, l.bytes)) return -1;
-  int rc;
-  if (ops[0]->idtype_bits == 32) {
-    std::vector<Operand<int32_t>> host;
-    if (upload_ops<int32_t>(ops, weights, n, &host, ws.p + l.off_ops, s)) return -1;
-    rc = sum_fill<int32_t>(reinterpret_cast<const Operand<int32_t>*>(ws.p + l.off_ops), n, rows, dtype, c_indptr, c_indices, c_w,
-                           ws.p, l, s);
-  } else {
-    std::vector<Operand<int64_t>> host;
-    if (upload_ops<int64_t>(ops, weights, n, &host, ws.p + l.off_ops, s)) return -1;
-    rc = sum_fill<int64_t>(reinterpret_cast<const Operand<int64_t>*>(ws.p + l.off_ops), n, rows, dtype, c_indptr, c_indices, c_w,
-                           ws.p, l, s);
-  }
-  return rc;
+  return with_idx(ops[0]->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    std::vector<Operand<Idx>> host;
+    if (upload_ops<Idx>(ops, weights, n, &host, ws.p + l.off_ops, s)) return -1;
+    return sum_fill<Idx>(reinterpret_cast<const Operand<Idx>*>(ws.p + l.off_ops), n, rows, dtype, c_indptr, c_indices, c_w,
+                         ws.p, l, s);
+  });
 }
 
 int dgla_csr_mask(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dgla_coo* b, void* out, void* hip_stream) {
@@ -663,8 +627,7 @@ int dgla_csr_mask(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dg
   if (b->nnz > (int64_t(0xffffffffLL) * 256) / kMaskGroup) return fail("csr_mask: too many queries for one launch");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
-  return a->idtype_bits == 32 ? mask_dispatch<int32_t>(a, dtype, a_w, b, out, s)
-                              : mask_dispatch<int64_t>(a, dtype, a_w, b, out, s);
+  return with_idx(a->idtype_bits, [&](auto tag) { return mask_dispatch<decltype(tag)>(a, dtype, a_w, b, out, s); });
 }
 
 }  // extern "C"

@@ -20,11 +20,6 @@
 namespace dgla {
 namespace {
 
-int xfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
 template <typename Idx, typename Piece, int K>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const Piece* __restrict__ src,
                                                           const Idx* __restrict__ idx,
@@ -67,7 +62,7 @@ template <typename Idx, typename Piece>
 int run_gather(const void* src, const void* idx, void* dst, int64_t n, int64_t row_bytes,
                hipStream_t s) {
   const int64_t pieces = row_bytes / static_cast<int64_t>(sizeof(Piece));
-  if (pieces > 0xffff) return xfail("gather_rows: rows longer than 65535 pieces are not supported");
+  if (pieces > 0xffff) return fail("gather_rows: rows longer than 65535 pieces are not supported");
   const int64_t total = n * pieces;
   const unsigned magic = 0xFFFFFFFFu / static_cast<unsigned>(pieces) + 1u;
   if (pieces <= 4 && n >= (int64_t(1) << 20)) {
@@ -136,10 +131,10 @@ int run_scatter(const void* src, const void* idx, void* dst, int64_t n, int64_t 
                 hipStream_t s) {
   constexpr int K = 4;
   const int64_t pieces = row_bytes / static_cast<int64_t>(sizeof(Piece));
-  if (pieces > 0xffff) return xfail("scatter_rows: rows longer than 65535 pieces are not supported");
+  if (pieces > 0xffff) return fail("scatter_rows: rows longer than 65535 pieces are not supported");
   const int64_t total = n * pieces;
   const int64_t blocks = (total + 256 * K - 1) / (256 * K);
-  if (blocks > 0x7fffffffLL) return xfail("scatter_rows: too many pieces for one launch");
+  if (blocks > 0x7fffffffLL) return fail("scatter_rows: too many pieces for one launch");
   const unsigned magic = 0xFFFFFFFFu / static_cast<unsigned>(pieces) + 1u;
   hipLaunchKernelGGL((scatter_rows_kernel<Idx, Piece, K>), dim3(static_cast<unsigned>(blocks)), dim3(256),
                      0, s, static_cast<const Piece*>(src), static_cast<const Idx*>(idx),
@@ -292,10 +287,10 @@ extern "C" {
 
 int dgla_gather_rows(int idtype_bits, const void* src, const void* idx, int64_t n,
                      int64_t row_bytes, void* dst, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return xfail("idtype must be int32 or int64");
-  if (n < 0 || row_bytes < 0) return xfail("negative size");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (n < 0 || row_bytes < 0) return fail("negative size");
   if (n == 0 || row_bytes == 0) return 0;
-  if (!src || !idx || !dst) return xfail("gather_rows: null pointer");
+  if (!src || !idx || !dst) return fail("gather_rows: null pointer");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, dst);
   const uintptr_t both = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
@@ -314,10 +309,10 @@ int dgla_gather_rows(int idtype_bits, const void* src, const void* idx, int64_t 
 
 int dgla_scatter_rows(int idtype_bits, const void* src, const void* idx, int64_t n,
                       int64_t row_bytes, void* dst, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return xfail("idtype must be int32 or int64");
-  if (n < 0 || row_bytes < 0) return xfail("negative size");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (n < 0 || row_bytes < 0) return fail("negative size");
   if (n == 0 || row_bytes == 0) return 0;
-  if (!src || !idx || !dst) return xfail("scatter_rows: null pointer");
+  if (!src || !idx || !dst) return fail("scatter_rows: null pointer");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, dst);
   const uintptr_t both = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
@@ -336,12 +331,12 @@ int dgla_scatter_rows(int idtype_bits, const void* src, const void* idx, int64_t
 
 int dgla_partition_map(int idtype_bits, int mode, int num_parts, const void* range, const void* idx,
                        int64_t n, void* part_out, void* local_out, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return xfail("idtype must be int32 or int64");
-  if (mode != 0 && mode != 1) return xfail("partition mode must be 0 (remainder) or 1 (range)");
-  if (num_parts < 1) return xfail("num_parts must be positive");
-  if (mode == 1 && !range) return xfail("range partition needs the range array");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (mode != 0 && mode != 1) return fail("partition mode must be 0 (remainder) or 1 (range)");
+  if (num_parts < 1) return fail("num_parts must be positive");
+  if (mode == 1 && !range) return fail("range partition needs the range array");
   if (n == 0) return 0;
-  if (n < 0 || !idx) return xfail("partition_map: bad index array");
+  if (n < 0 || !idx) return fail("partition_map: bad index array");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, idx);
   if (idtype_bits == 32)
@@ -361,12 +356,12 @@ int dgla_partition_map(int idtype_bits, int mode, int num_parts, const void* ran
 int dgla_partition_to_global(int idtype_bits, int mode, int num_parts, const void* range,
                              const void* local_idx, int64_t n, int part_id, void* out,
                              void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return xfail("idtype must be int32 or int64");
-  if (mode != 0 && mode != 1) return xfail("partition mode must be 0 (remainder) or 1 (range)");
-  if (num_parts < 1 || part_id < 0 || part_id >= num_parts) return xfail("invalid part id");
-  if (mode == 1 && !range) return xfail("range partition needs the range array");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (mode != 0 && mode != 1) return fail("partition mode must be 0 (remainder) or 1 (range)");
+  if (num_parts < 1 || part_id < 0 || part_id >= num_parts) return fail("invalid part id");
+  if (mode == 1 && !range) return fail("range partition needs the range array");
   if (n == 0) return 0;
-  if (n < 0 || !local_idx || !out) return xfail("partition_to_global: bad arrays");
+  if (n < 0 || !local_idx || !out) return fail("partition_to_global: bad arrays");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
   if (idtype_bits == 32)
@@ -385,7 +380,7 @@ int dgla_partition_to_global(int idtype_bits, int mode, int num_parts, const voi
 
 /* ---- peer-mapped halo exchange (see the comment above peer_push_kernel) ---- */
 int dgla_peer_alloc(size_t bytes, int kind, void** out) {
-  if (!out) return xfail("dgla_peer_alloc: null result");
+  if (!out) return fail("dgla_peer_alloc: null result");
   *out = nullptr;
   if (bytes == 0) bytes = 256;
   // kind 1 / 2: memory a REMOTE GPU's stores become visible in while a kernel here polls it (fine-grained / uncached).
@@ -401,7 +396,7 @@ int dgla_peer_alloc(size_t bytes, int kind, void** out) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     *out = nullptr;
-    return xfail(std::string("dgla_peer_alloc(kind ") + std::to_string(kind) + "): " + hipGetErrorString(e) +
+    return fail(std::string("dgla_peer_alloc(kind ") + std::to_string(kind) + "): " + hipGetErrorString(e) +
                  " (no fall-back to coarse-grained memory: it is not coherent for peer writes)");
   }
   DGLA_CHECK_HIP(hipMemset(*out, 0, bytes));
@@ -416,7 +411,7 @@ int dgla_peer_free(void* ptr) {
 
 int dgla_ipc_export(void* ptr, void* handle64) {
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handles travel as 64 bytes");
-  if (!ptr || !handle64) return xfail("dgla_ipc_export: null argument");
+  if (!ptr || !handle64) return fail("dgla_ipc_export: null argument");
   hipIpcMemHandle_t h;
   DGLA_CHECK_HIP(hipIpcGetMemHandle(&h, ptr));
   memcpy(handle64, &h, 64);
@@ -424,7 +419,7 @@ int dgla_ipc_export(void* ptr, void* handle64) {
 }
 
 int dgla_ipc_import(const void* handle64, void** out) {
-  if (!handle64 || !out) return xfail("dgla_ipc_import: null argument");
+  if (!handle64 || !out) return fail("dgla_ipc_import: null argument");
   hipIpcMemHandle_t h;
   memcpy(&h, handle64, 64);
   DGLA_CHECK_HIP(hipIpcOpenMemHandle(out, h, hipIpcMemLazyEnablePeerAccess));
@@ -439,8 +434,8 @@ int dgla_ipc_release(void* ptr) {
 int dgla_peer_push(const void* x_local, int64_t row_bytes, const int64_t* serve_rows, const void* segments,
                    int num_segments, int64_t num_blocks, uint64_t epoch, void* arrive, void* hip_stream) {
   if (num_segments <= 0 || num_blocks <= 0) return 0;
-  if (!x_local || !segments || !arrive) return xfail("dgla_peer_push: null argument");
-  if (row_bytes <= 0 || row_bytes % 4) return xfail("dgla_peer_push: rows must be a whole number of 4-byte words");
+  if (!x_local || !segments || !arrive) return fail("dgla_peer_push: null argument");
+  if (row_bytes <= 0 || row_bytes % 4) return fail("dgla_peer_push: rows must be a whole number of 4-byte words");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, x_local);
   const dim3 grid(static_cast<unsigned>(num_blocks));
@@ -460,7 +455,7 @@ int dgla_peer_push(const void* x_local, int64_t row_bytes, const int64_t* serve_
 int dgla_peer_wait(const void* flags, int num_flags, uint64_t epoch, void* status, int64_t max_spins,
                    void* hip_stream) {
   if (num_flags <= 0) return 0;
-  if (!flags || !status) return xfail("dgla_peer_wait: null argument");
+  if (!flags || !status) return fail("dgla_peer_wait: null argument");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, flags);
   hipLaunchKernelGGL(peer_wait_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint64_t*>(flags), num_flags, epoch,

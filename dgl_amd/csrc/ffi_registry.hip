@@ -50,11 +50,6 @@ struct Registrar {
   Registrar(const char* name, PackedFn f) { Registry::get().add(name, std::move(f)); }
 };
 
-static int ffi_fail(const std::string& msg) {
-  last_error() = msg;
-  return -1;
-}
-
 // thread-local stream, like the reference's per-thread CUDAThreadEntry / current torch stream
 static thread_local hipStream_t tls_stream = nullptr;
 static thread_local int tls_device = -1;  // device id named by the last DGLSetStream, -1 = never set
@@ -64,38 +59,38 @@ static bool is_array(int tc) { return tc == kArrayHandle || tc == kNDArrayContai
 
 static int get_int(const FfiArgs& a, int i, int64_t* out) {
   if (i >= a.n || (a.tc[i] != kObjectInt && a.tc[i] != kObjectUInt))
-    return ffi_fail("argument " + std::to_string(i) + ": expected an integer");
+    return fail("argument " + std::to_string(i) + ": expected an integer");
   *out = a.v[i].v_int64;
   return 0;
 }
 static int get_float(const FfiArgs& a, int i, double* out) {
   if (i >= a.n || (a.tc[i] != kObjectFloat && a.tc[i] != kObjectInt))
-    return ffi_fail("argument " + std::to_string(i) + ": expected a number");
+    return fail("argument " + std::to_string(i) + ": expected a number");
   *out = a.tc[i] == kObjectFloat ? a.v[i].v_float64 : static_cast<double>(a.v[i].v_int64);
   return 0;
 }
 static int get_str(const FfiArgs& a, int i, const char** out) {
   if (i >= a.n || a.tc[i] != kStr)
-    return ffi_fail("argument " + std::to_string(i) + ": expected a string");
+    return fail("argument " + std::to_string(i) + ": expected a string");
   *out = a.v[i].v_str;
   return 0;
 }
 static int get_handle(const FfiArgs& a, int i, void** out) {
   if (i >= a.n || (a.tc[i] != kObjectHandle && a.tc[i] != kHandle))
-    return ffi_fail("argument " + std::to_string(i) + ": expected an object handle");
+    return fail("argument " + std::to_string(i) + ": expected an object handle");
   *out = a.v[i].v_handle;
   return 0;
 }
 // An NDArray argument.  "Absent" operands are empty arrays (IsNullArray == shape[0] == 0,
 // include/dgl/aten/array_ops.h:37) or kNull.
 static int get_array(const FfiArgs& a, int i, DGLArray** out) {
-  if (i >= a.n) return ffi_fail("argument " + std::to_string(i) + " is missing");
+  if (i >= a.n) return fail("argument " + std::to_string(i) + " is missing");
   if (a.tc[i] == kNull) {
     *out = nullptr;
     return 0;
   }
   if (!is_array(a.tc[i]))
-    return ffi_fail("argument " + std::to_string(i) + ": expected an NDArray");
+    return fail("argument " + std::to_string(i) + ": expected an NDArray");
   *out = static_cast<DGLArray*>(a.v[i].v_handle);
   return 0;
 }
@@ -112,7 +107,7 @@ static int check_contiguous(const DGLArray* t, const char* name) {
   int64_t expect = 1;
   for (int i = t->ndim - 1; i >= 0; --i) {
     if (t->shape[i] != 1 && t->strides[i] != expect)
-      return ffi_fail(std::string(name) + " must be contiguous");
+      return fail(std::string(name) + " must be contiguous");
     expect *= t->shape[i];
   }
   return 0;
@@ -126,7 +121,7 @@ static int float_dtype(const DGLArray* t, dgla_dtype* out) {
     if (d.code == 2 && d.bits == 16) return *out = DGLA_F16, 0;
     if (d.code == 4 && d.bits == 16) return *out = DGLA_BF16, 0;
   }
-  return ffi_fail("feature arrays must be float16 / bfloat16 / float32 / float64");
+  return fail("feature arrays must be float16 / bfloat16 / float32 / float64");
 }
 
 static void* data_ptr(const DGLArray* t) {
@@ -224,7 +219,7 @@ static bool plan_ok(UnitGraph* g) {
 
 static int idbits_of(const DGLArray* t, int* bits) {
   if (t->dtype.code != 0 || (t->dtype.bits != 32 && t->dtype.bits != 64))
-    return ffi_fail("index arrays must be int32 or int64");
+    return fail("index arrays must be int32 or int64");
   *bits = t->dtype.bits;
   return 0;
 }
@@ -259,14 +254,14 @@ static int set_format(const FfiArgs& a, int which) {
   if (get_handle(a, 0, &h) || get_array(a, 1, &x) || get_array(a, 2, &y) || get_array(a, 3, &d))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!x || !y) return ffi_fail("index arrays are required");
+  if (!x || !y) return fail("index arrays are required");
   int bx, by;
   if (idbits_of(x, &bx) || idbits_of(y, &by)) return -1;
-  if (bx != g->idbits || by != g->idbits) return ffi_fail("index dtype does not match the graph");
+  if (bx != g->idbits || by != g->idbits) return fail("index dtype does not match the graph");
   if (!null_array(d)) {
     int bd;
     if (idbits_of(d, &bd)) return -1;
-    if (bd != g->idbits) return ffi_fail("edge-id dtype does not match the graph");
+    if (bd != g->idbits) return fail("edge-id dtype does not match the graph");
   }
   if (check_contiguous(x, "indptr/row") || check_contiguous(y, "indices/col")) return -1;
   SparseFmt f;
@@ -276,11 +271,11 @@ static int set_format(const FfiArgs& a, int which) {
   f.data = null_array(d) ? nullptr : data_ptr(d);
   f.nnz = y->ndim ? y->shape[0] : 0;
   if (which == 0) {
-    if (x->shape[0] != f.nnz) return ffi_fail("row and col must have the same length");
+    if (x->shape[0] != f.nnz) return fail("row and col must have the same length");
     g->coo = f;
   } else {
     const int64_t rows = which == 1 ? g->num_src : g->num_dst;
-    if (x->shape[0] != rows + 1) return ffi_fail("indptr must have num_rows + 1 entries");
+    if (x->shape[0] != rows + 1) return fail("indptr must have num_rows + 1 entries");
     (which == 1 ? g->csr : g->csc) = f;
     if (which == 2) {
       g->plan_valid = g->esm_plan_valid = false;
@@ -296,7 +291,7 @@ static int set_format(const FfiArgs& a, int which) {
 static Registrar r_create("dgl_amd._CAPI_UnitGraphCreate", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   int64_t ns, nd, bits;
   if (get_int(a, 0, &ns) || get_int(a, 1, &nd) || get_int(a, 2, &bits)) return -1;
-  if (bits != 32 && bits != 64) return ffi_fail("idtype bits must be 32 or 64");
+  if (bits != 32 && bits != 64) return fail("idtype bits must be 32 or 64");
   UnitGraph* g = new UnitGraph();
   g->num_src = ns;
   g->num_dst = nd;
@@ -375,13 +370,13 @@ static int unpack_spmm(const FfiArgs& a, SpmmCall* c) {
   if (a.n > 6 && get_array(a, 6, &c->ArgU)) return -1;
   if (a.n > 7 && get_array(a, 7, &c->ArgE)) return -1;
   c->g = static_cast<UnitGraph*>(h);
-  if (null_array(c->V)) return ffi_fail("out array is empty");
+  if (null_array(c->V)) return fail("out array is empty");
   // CheckCtx / CheckContiguous (src/array/kernel.cc:483-497)
   const DGLArray* arrs[5] = {c->U, c->E, c->V, c->ArgU, c->ArgE};
   const char* names[5] = {"U_data", "E_data", "out", "Arg_U", "Arg_E"};
   for (int i = 0; i < 5; ++i) {
     if (null_array(arrs[i])) continue;
-    if (!on_gpu(arrs[i])) return ffi_fail(std::string(names[i]) + " is not on the GPU device of the graph");
+    if (!on_gpu(arrs[i])) return fail(std::string(names[i]) + " is not on the GPU device of the graph");
     if (check_contiguous(arrs[i], names[i])) return -1;
   }
   if (float_dtype(c->V, &c->dtype)) return -1;
@@ -389,7 +384,7 @@ static int unpack_spmm(const FfiArgs& a, SpmmCall* c) {
     dgla_dtype d;
     if (null_array(t)) continue;
     if (float_dtype(t, &d)) return -1;
-    if (d != c->dtype) return ffi_fail("operand and output dtypes differ");
+    if (d != c->dtype) return fail("operand and output dtypes differ");
   }
   to_tensor(c->U, &c->u);
   to_tensor(c->E, &c->e);
@@ -689,7 +684,7 @@ static Registrar r_spmm("sparse._CAPI_DGLKernelSpMM", [](const FfiArgs& a, DGLVa
                          null_array(c.ArgU) ? nullptr : data_ptr(c.ArgU),
                          null_array(c.ArgE) ? nullptr : data_ptr(c.ArgE), tls_stream);
   }
-  return ffi_fail("SpMM only supports CSC and COO formats");  // kernel.cc:41
+  return fail("SpMM only supports CSC and COO formats");  // kernel.cc:41
 });
 
 // reduce "sum" followed by / clamp(in_degree, 1), fused (the `mean` reducer of dgl.ops.gspmm,
@@ -700,7 +695,7 @@ static Registrar r_spmm_mean("sparse._CAPI_DGLKernelSpMMMean",
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
   UnitGraph* g = c.g;
-  if (!g->csc.present) return ffi_fail("SpMMMean needs the CSC format");
+  if (!g->csc.present) return fail("SpMMMean needs the CSC format");
   dgla_csr csc = csr_of(g, g->csc, true);
   uint32_t flags = (plan_ok(g) ? DGLA_PLAN_VALID : 0) | DGLA_MEAN;
   const UnitGraph::SplitKey key = static_split_flags(g, c, &flags);
@@ -721,7 +716,7 @@ static Registrar r_spmm_acc("sparse._CAPI_DGLKernelSpMMAccumulate",
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
   UnitGraph* g = c.g;
-  if (!g->csc.present) return ffi_fail("SpMMAccumulate needs the CSC format");  // kernel.cc:212-217
+  if (!g->csc.present) return fail("SpMMAccumulate needs the CSC format");  // kernel.cc:212-217
   const dgla_csr csc = csr_of(g, g->csc, true);
   const uint32_t flags = (plan_ok(g) ? DGLA_PLAN_VALID : 0) | DGLA_ACCUMULATE;
   const int rc = dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &c.e.t, &c.v.t, nullptr,
@@ -746,16 +741,16 @@ static int spmm_stacked_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool want
       get_array(a, 4, &Ut) || get_array(a, 5, &Et) || get_array(a, 6, &V) || get_array(a, 7, &rel))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("stacked SpMM needs the CSC format");
-  if (null_array(V)) return ffi_fail("out array is empty");
+  if (!g->csc.present) return fail("stacked SpMM needs the CSC format");
+  if (null_array(V)) return fail("out array is empty");
   dgla_dtype dt;
   if (float_dtype(V, &dt)) return -1;
   for (const DGLArray* t : {U0, E0}) {
     dgla_dtype d;
     if (null_array(t)) continue;
-    if (!on_gpu(t)) return ffi_fail("operand is not on the GPU device of the graph");
+    if (!on_gpu(t)) return fail("operand is not on the GPU device of the graph");
     if (check_contiguous(t, "operand") || float_dtype(t, &d)) return -1;
-    if (d != dt) return ffi_fail("operand and output dtypes differ");
+    if (d != dt) return fail("operand and output dtypes differ");
   }
   TensorArg u, e, v;
   to_tensor(U0, &u);
@@ -770,7 +765,7 @@ static int spmm_stacked_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool want
     return last_error().empty() ? 0 : -1;
   }
   *rtc = kNull;
-  if (null_array(rel) || rel->dtype.bits != 8) return ffi_fail("rel must be a uint8 array");
+  if (null_array(rel) || rel->dtype.bits != 8) return fail("rel must be a uint8 array");
   const int64_t n_rel = !null_array(Ut) ? Ut->shape[0] : (!null_array(Et) ? Et->shape[0] : 0);
   const int rc = dgla_spmm_csr_stacked(
       op, &csc, data_ptr(rel), static_cast<int>(n_rel), dt, &u.t, &e.t,
@@ -805,16 +800,16 @@ static int spmm_stacked_cmp_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool 
       get_array(a, 12, &UT) || get_array(a, 13, &ET))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("stacked SpMM needs the CSC format");
-  if (null_array(V)) return ffi_fail("out array is empty");
+  if (!g->csc.present) return fail("stacked SpMM needs the CSC format");
+  if (null_array(V)) return fail("out array is empty");
   dgla_dtype dt;
   if (float_dtype(V, &dt)) return -1;
   for (const DGLArray* t : {U0, E0}) {
     dgla_dtype d;
     if (null_array(t)) continue;
-    if (!on_gpu(t)) return ffi_fail("operand is not on the GPU device of the graph");
+    if (!on_gpu(t)) return fail("operand is not on the GPU device of the graph");
     if (check_contiguous(t, "operand") || float_dtype(t, &d)) return -1;
-    if (d != dt) return ffi_fail("operand and output dtypes differ");
+    if (d != dt) return fail("operand and output dtypes differ");
   }
   TensorArg u, e, v;
   to_tensor(U0, &u);
@@ -829,15 +824,15 @@ static int spmm_stacked_cmp_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool 
     return last_error().empty() ? 0 : -1;
   }
   *rtc = kNull;
-  if (null_array(rel) || rel->dtype.bits != 8) return ffi_fail("rel must be a uint8 array");
+  if (null_array(rel) || rel->dtype.bits != 8) return fail("rel must be a uint8 array");
   if (null_array(types) || on_gpu(types) || types->dtype.bits != 32 || types->ndim != 2 || types->shape[0] != 2)
-    return ffi_fail("types must be a host int32 array of shape [2, num_rel]");
+    return fail("types must be a host int32 array of shape [2, num_rel]");
   const int64_t n_rel = types->shape[1];
   for (const DGLArray* t : {AU, AE, UT, ET}) {
     if (null_array(t)) continue;
-    if (!on_gpu(t)) return ffi_fail("arg array is not on the GPU device of the graph");
+    if (!on_gpu(t)) return fail("arg array is not on the GPU device of the graph");
     if (check_contiguous(t, "arg array")) return -1;
-    if (t->dtype.bits != g->idbits) return ffi_fail("arg arrays must have the graph's id type");
+    if (t->dtype.bits != g->idbits) return fail("arg arrays must have the graph's id type");
   }
   const int32_t* tp = static_cast<const int32_t*>(data_ptr(types));
   const int rc = dgla_spmm_csr_stacked_cmp(
@@ -871,15 +866,15 @@ static Registrar r_sddmm("sparse._CAPI_DGLKernelSDDMM", [](const FfiArgs& a, DGL
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
   if (g->num_edges == 0) return 0;
-  if (null_array(out)) return ffi_fail("out array is empty");
+  if (null_array(out)) return fail("out array is empty");
   dgla_dtype dt;
   if (float_dtype(out, &dt)) return -1;
   for (const DGLArray* t : {lhs, rhs, out}) {
     if (null_array(t)) continue;
     dgla_dtype d;
-    if (!on_gpu(t)) return ffi_fail("array is not on the GPU device of the graph");
+    if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
     if (check_contiguous(t, "array") || float_dtype(t, &d)) return -1;
-    if (d != dt) return ffi_fail("operand and output dtypes differ");
+    if (d != dt) return fail("operand and output dtypes differ");
   }
   TensorArg l, r, o;
   to_tensor(lhs, &l);
@@ -896,7 +891,7 @@ static Registrar r_sddmm("sparse._CAPI_DGLKernelSDDMM", [](const FfiArgs& a, DGL
     return dgla_sddmm_csr(op, &csr, dt, &l.t, &r.t, &o.t, static_cast<int>(lt),
                           static_cast<int>(rt), tls_stream);
   }
-  return ffi_fail("SDDMM only supports CSR and COO formats");  // kernel.cc:245
+  return fail("SDDMM only supports CSR and COO formats");  // kernel.cc:245
 });
 
 // Will this call run the merge-path kernels (and so leave a valid plan in g->esm_ws)?
@@ -916,7 +911,7 @@ static int edge_softmax_ffi(const FfiArgs& a, bool backward) {
       get_array(a, 4, &z))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("edge_softmax needs the CSC format");
+  if (!g->csc.present) return fail("edge_softmax needs the CSC format");
   const dgla_csr csc = csr_of(g, g->csc, true);
   dgla_dtype dt;
   TensorArg tx, ty, tz;
@@ -925,7 +920,7 @@ static int edge_softmax_ffi(const FfiArgs& a, bool backward) {
   to_tensor(z, &tz);
   if (!backward) {
     // (g, op, U(null), E = score, V = out)
-    if (null_array(y) || null_array(z)) return g->num_edges == 0 ? 0 : ffi_fail("score / out missing");
+    if (null_array(y) || null_array(z)) return g->num_edges == 0 ? 0 : fail("score / out missing");
     if (float_dtype(y, &dt)) return -1;
     const bool merge = esm_uses_workspace(g, csc, dt, y);
     const int rc = dgla_edge_softmax_forward(&csc, dt, &ty.t, &tz.t, g->esm_ws, g->esm_ws_bytes,
@@ -935,7 +930,7 @@ static int edge_softmax_ffi(const FfiArgs& a, bool backward) {
   }
   // (g, op, out, sds, back_out, ufeat(null))
   if (null_array(x) || null_array(y) || null_array(z))
-    return g->num_edges == 0 ? 0 : ffi_fail("out / sds / back missing");
+    return g->num_edges == 0 ? 0 : fail("out / sds / back missing");
   if (float_dtype(x, &dt)) return -1;
   const bool merge = esm_uses_workspace(g, csc, dt, x);
   const int rc = dgla_edge_softmax_backward(&csc, dt, &tx.t, &ty.t, &tz.t, g->esm_ws,
@@ -975,7 +970,7 @@ static Registrar r_esb("sparse._CAPI_DGLKernelEdge_softmax_backward",
 static int seg_arrays_ok_fwd(std::initializer_list<const DGLArray*> arrs) {  // CheckCtx / CheckContiguous of the lambdas
   for (const DGLArray* t : arrs) {
     if (!t || t->ndim == 0) continue;
-    if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+    if (!on_gpu(t)) return fail("array is not on a GPU device");
     if (check_contiguous(t, "array")) return -1;
   }
   return 0;
@@ -998,8 +993,8 @@ static void gat_tensor(const DGLArray* a, TensorArg* out) {  // to_tensor that k
 static int gat_same_dtype(const DGLArray* ft, std::initializer_list<const DGLArray*> arrs, const DGLArray* mz) {
   for (const DGLArray* t : arrs)
     if (t->dtype.code != ft->dtype.code || t->dtype.bits != ft->dtype.bits || t->dtype.lanes != ft->dtype.lanes)
-      return ffi_fail("gat_attention: mixed dtypes (ft, el, er, out, dout and the gradients share one element type)");
-  if (mz->dtype.code != 2 || mz->dtype.bits != 32) return ffi_fail("gat_attention: mz must be float32");
+      return fail("gat_attention: mixed dtypes (ft, el, er, out, dout and the gradients share one element type)");
+  if (mz->dtype.code != 2 || mz->dtype.bits != 32) return fail("gat_attention: mz must be float32");
   return 0;
 }
 // (g, heads, dim) -> bytes of scratch
@@ -1010,7 +1005,7 @@ static Registrar r_gatw("dgl_amd._CAPI_GATAttentionWorkspaceBytes", [](const Ffi
   UnitGraph* g = static_cast<UnitGraph*>(h);
   *rtc = kObjectInt;
   ret->v_int64 = 0;
-  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (!g->csc.present) return fail("gat_attention needs the CSC format");
   const dgla_csr csc = csr_of(g, g->csc, true);
   ret->v_int64 = static_cast<int64_t>(dgla_gat_attention_workspace_bytes(&csc, heads, dim));
   return 0;
@@ -1025,9 +1020,9 @@ static Registrar r_gatf("dgl_amd._CAPI_GATAttentionForward", [](const FfiArgs& a
       get_float(a, 4, &slope) || get_array(a, 5, &out) || get_array(a, 6, &mz) || get_array(a, 7, &ws))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (!g->csc.present) return fail("gat_attention needs the CSC format");
   if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
-    return ffi_fail("gat_attention: ft / el / er / out / mz are required");
+    return fail("gat_attention: ft / el / er / out / mz are required");
   if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
@@ -1051,9 +1046,9 @@ static Registrar r_gatb("dgl_amd._CAPI_GATAttentionBackward", [](const FfiArgs& 
       get_array(a, 8, &dft) || get_array(a, 9, &del_) || get_array(a, 10, &der) || get_array(a, 11, &ws))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present || !g->csr.present) return ffi_fail("gat_attention backward needs the CSC and the CSR format");
+  if (!g->csc.present || !g->csr.present) return fail("gat_attention backward needs the CSC and the CSR format");
   for (DGLArray* t : {ft, el, er, out, mz, dout, dft, del_, der})
-    if (gat_missing(t)) return ffi_fail("gat_attention backward: every tensor is required");
+    if (gat_missing(t)) return fail("gat_attention backward: every tensor is required");
   if (seg_arrays_ok_fwd({ft, el, er, out, mz, dout, dft, del_, der, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out, dout, dft, del_, der}, mz)) return -1;
@@ -1078,9 +1073,9 @@ static Registrar r_gattf("dgl_amd._CAPI_GATAttentionTrainForward", [](const FfiA
       get_array(a, 8, &mz) || get_array(a, 9, &ws))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (!g->csc.present) return fail("gat_attention needs the CSC format");
   if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
-    return ffi_fail("gat_attention: ft / el / er / out / mz are required");
+    return fail("gat_attention: ft / el / er / out / mz are required");
   if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
@@ -1108,9 +1103,9 @@ static Registrar r_gattb("dgl_amd._CAPI_GATAttentionTrainBackward", [](const Ffi
       get_array(a, 12, &ws))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present || !g->csr.present) return ffi_fail("gat_attention backward needs the CSC and the CSR format");
+  if (!g->csc.present || !g->csr.present) return fail("gat_attention backward needs the CSC and the CSR format");
   for (DGLArray* t : {ft, el, er, mz, dout, dft, del_, der})
-    if (gat_missing(t)) return ffi_fail("gat_attention backward: every tensor is required");
+    if (gat_missing(t)) return fail("gat_attention backward: every tensor is required");
   if (seg_arrays_ok_fwd({ft, el, er, mz, dout, dft, del_, der, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, dout, dft, del_, der}, mz)) return -1;
@@ -1135,9 +1130,9 @@ static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& 
       get_float(a, 4, &slope) || get_float(a, 5, &p) || get_int(a, 6, &seed) || get_array(a, 7, &attn))
     return -1;
   UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return ffi_fail("gat_attention needs the CSC format");
+  if (!g->csc.present) return fail("gat_attention needs the CSC format");
   if (gat_missing(el) || gat_missing(er) || gat_missing(mz) || gat_missing(attn))
-    return ffi_fail("gat_attention_weights: el / er / mz / attn are required");
+    return fail("gat_attention_weights: el / er / mz / attn are required");
   if (seg_arrays_ok_fwd({el, er, mz, attn})) return -1;
   dgla_dtype dt;
   if (float_dtype(el, &dt) || gat_same_dtype(el, {er, attn}, mz)) return -1;
@@ -1158,29 +1153,29 @@ static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& 
 static int spgemm_csr(const FfiArgs& a, int i, dgla_csr* out) {
   void* h;
   if (get_handle(a, i, &h)) return -1;
-  if (!h || *static_cast<const uint32_t*>(h) != kMagicUnit) return ffi_fail("argument " + std::to_string(i) + ": not a unit graph");
+  if (!h || *static_cast<const uint32_t*>(h) != kMagicUnit) return fail("argument " + std::to_string(i) + ": not a unit graph");
   const UnitGraph* g = static_cast<const UnitGraph*>(h);
-  if (!g->csr.present) return ffi_fail("csr_mm / csr_sum / csr_mask need the CSR format of their operands");
+  if (!g->csr.present) return fail("csr_mm / csr_sum / csr_mask need the CSR format of their operands");
   *out = csr_of(g, g->csr, false);
   return 0;
 }
 static int spgemm_ids(const DGLArray* t, int bits, const char* name) {
-  if (!t || t->ndim == 0) return ffi_fail(std::string(name) + " is required");
-  if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+  if (!t || t->ndim == 0) return fail(std::string(name) + " is required");
+  if (!on_gpu(t)) return fail("array is not on a GPU device");
   if (check_contiguous(t, name)) return -1;
   int b;
   if (idbits_of(t, &b)) return -1;
-  if (b != bits) return ffi_fail(std::string(name) + " must have the id type of the operands");
+  if (b != bits) return fail(std::string(name) + " must have the id type of the operands");
   return 0;
 }
 // weights: 1-D (or (n, 1)), one per edge
 static int spgemm_weights(const DGLArray* t, int64_t nnz, dgla_dtype* dt, const char* name) {
-  if (!t || t->ndim == 0) return ffi_fail(std::string(name) + " is required");
-  if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+  if (!t || t->ndim == 0) return fail(std::string(name) + " is required");
+  if (!on_gpu(t)) return fail("array is not on a GPU device");
   if (check_contiguous(t, name) || float_dtype(t, dt)) return -1;
-  if (t->ndim > 2 || (t->ndim == 2 && t->shape[1] != 1)) return ffi_fail(std::string(name) + " must be one scalar per edge (1-D)");
+  if (t->ndim > 2 || (t->ndim == 2 && t->shape[1] != 1)) return fail(std::string(name) + " must be one scalar per edge (1-D)");
   if (t->shape[0] != nnz)
-    return ffi_fail(std::string(name) + " has " + std::to_string(t->shape[0]) + " entries for " + std::to_string(nnz) + " edges");
+    return fail(std::string(name) + " has " + std::to_string(t->shape[0]) + " entries for " + std::to_string(nnz) + " edges");
   return 0;
 }
 static void spgemm_ws(const DGLArray* ws, void** p, size_t* bytes) {
@@ -1193,7 +1188,7 @@ static Registrar r_csrmmc("dgl_amd._CAPI_CSRMMCount", [](const FfiArgs& a, DGLVa
   DGLArray *ip, *ws;
   if (spgemm_csr(a, 0, &A) || spgemm_csr(a, 1, &B) || get_array(a, 2, &ip) || get_array(a, 3, &ws)) return -1;
   if (spgemm_ids(ip, A.idtype_bits, "c_indptr")) return -1;
-  if (ip->shape[0] != A.num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  if (ip->shape[0] != A.num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
   void* w;
   size_t wb;
   spgemm_ws(ws, &w, &wb);
@@ -1215,8 +1210,8 @@ static Registrar r_csrmmf("dgl_amd._CAPI_CSRMMFill", [](const FfiArgs& a, DGLVal
   if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(bw, B.nnz, &dtb, "b_weights")) return -1;
   if (spgemm_ids(ip, A.idtype_bits, "c_indptr") || spgemm_ids(ix, A.idtype_bits, "c_indices")) return -1;
   if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
-  if (dt != dtb || dt != dtc) return ffi_fail("csr_mm: the weights of a, b and c must share one element type");
-  if (ip->shape[0] != A.num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  if (dt != dtb || dt != dtc) return fail("csr_mm: the weights of a, b and c must share one element type");
+  if (ip->shape[0] != A.num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
   void* w;
   size_t wb;
   spgemm_ws(ws, &w, &wb);
@@ -1227,7 +1222,7 @@ static Registrar r_csrmmf("dgl_amd._CAPI_CSRMMFill", [](const FfiArgs& a, DGLVal
 static Registrar r_csrsumc("dgl_amd._CAPI_CSRSumCount", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   int64_t n;
   if (get_int(a, 0, &n)) return -1;
-  if (n < 1 || n > 4096) return ffi_fail("csr_sum: the number of operands must be in [1, 4096]");
+  if (n < 1 || n > 4096) return fail("csr_sum: the number of operands must be in [1, 4096]");
   std::vector<dgla_csr> ops(n);
   std::vector<const dgla_csr*> ptrs(n);
   for (int k = 0; k < n; ++k) {
@@ -1237,7 +1232,7 @@ static Registrar r_csrsumc("dgl_amd._CAPI_CSRSumCount", [](const FfiArgs& a, DGL
   DGLArray *ip, *ws;
   if (get_array(a, 1 + n, &ip) || get_array(a, 2 + n, &ws)) return -1;
   if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr")) return -1;
-  if (ip->shape[0] != ops[0].num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  if (ip->shape[0] != ops[0].num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
   void* w;
   size_t wb;
   spgemm_ws(ws, &w, &wb);
@@ -1252,7 +1247,7 @@ static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLV
   *rtc = kNull;
   int64_t n;
   if (get_int(a, 0, &n)) return -1;
-  if (n < 1 || n > 4096) return ffi_fail("csr_sum: the number of operands must be in [1, 4096]");
+  if (n < 1 || n > 4096) return fail("csr_sum: the number of operands must be in [1, 4096]");
   std::vector<dgla_csr> ops(n);
   std::vector<const dgla_csr*> ptrs(n);
   std::vector<const void*> wts(n);
@@ -1265,7 +1260,7 @@ static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLV
     DGLArray* t;
     dgla_dtype dk;
     if (get_array(a, 1 + n + k, &t) || spgemm_weights(t, ops[k].nnz, &dk, "weights")) return -1;
-    if (k > 0 && dk != dt) return ffi_fail("csr_sum: the weights must share one element type");
+    if (k > 0 && dk != dt) return fail("csr_sum: the weights must share one element type");
     dt = dk;
     wts[k] = t->data ? data_ptr(t) : nullptr;
   }
@@ -1275,8 +1270,8 @@ static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLV
   dgla_dtype dtc;
   if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr") || spgemm_ids(ix, ops[0].idtype_bits, "c_indices")) return -1;
   if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
-  if (dtc != dt) return ffi_fail("csr_sum: the weights must share one element type");
-  if (ip->shape[0] != ops[0].num_rows + 1) return ffi_fail("c_indptr must have num_rows + 1 entries");
+  if (dtc != dt) return fail("csr_sum: the weights must share one element type");
+  if (ip->shape[0] != ops[0].num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
   void* w;
   size_t wb;
   spgemm_ws(ws, &w, &wb);
@@ -1290,13 +1285,13 @@ static Registrar r_csrmask("dgl_amd._CAPI_CSRMask", [](const FfiArgs& a, DGLValu
   void* hb;
   DGLArray *aw, *out;
   if (spgemm_csr(a, 0, &A) || get_array(a, 1, &aw) || get_handle(a, 2, &hb) || get_array(a, 3, &out)) return -1;
-  if (!hb || *static_cast<const uint32_t*>(hb) != kMagicUnit) return ffi_fail("argument 2: not a unit graph");
+  if (!hb || *static_cast<const uint32_t*>(hb) != kMagicUnit) return fail("argument 2: not a unit graph");
   const UnitGraph* gb = static_cast<const UnitGraph*>(hb);
-  if (!gb->coo.present) return ffi_fail("csr_mask needs the COO format of its second operand");
+  if (!gb->coo.present) return fail("csr_mask needs the COO format of its second operand");
   const dgla_coo B = coo_of(gb);
   dgla_dtype dt, dto;
   if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(out, B.nnz, &dto, "out")) return -1;
-  if (dt != dto) return ffi_fail("csr_mask: a_weights and out must share one element type");
+  if (dt != dto) return fail("csr_mask: a_weights and out must share one element type");
   return dgla_csr_mask(&A, dt, aw->data ? data_ptr(aw) : nullptr, &B, out->data ? data_ptr(out) : nullptr, tls_stream);
 });
 
@@ -1304,7 +1299,7 @@ static Registrar r_csrmask("dgl_amd._CAPI_CSRMask", [](const FfiArgs& a, DGLValu
 static int seg_arrays_ok(std::initializer_list<const DGLArray*> arrs) {
   for (const DGLArray* t : arrs) {
     if (!t || t->ndim == 0) continue;
-    if (!on_gpu(t)) return ffi_fail("array is not on a GPU device");
+    if (!on_gpu(t)) return fail("array is not on a GPU device");
     if (check_contiguous(t, "array")) return -1;
   }
   return 0;
@@ -1319,21 +1314,21 @@ static Registrar r_segred("sparse._CAPI_DGLKernelSegmentReduce",
   if (get_str(a, 0, &op) || get_array(a, 1, &feat) || get_array(a, 2, &offsets) ||
       get_array(a, 3, &out) || get_array(a, 4, &arg))
     return -1;
-  if (!feat || !offsets || !out || out->ndim == 0) return ffi_fail("feat / offsets / out is required");
+  if (!feat || !offsets || !out || out->ndim == 0) return fail("feat / offsets / out is required");
   if (seg_arrays_ok({feat, offsets, out, arg})) return -1;
   // CheckCtx / CheckContiguous as the reference lambda; dtype rules of SegmentReduceDispatch
   dgla_dtype dt, df;
   int bits;
   if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(offsets, &bits)) return -1;
-  if (dt != df) return ffi_fail("feat and out dtypes differ");
+  if (dt != df) return fail("feat and out dtypes differ");
   if (offsets->ndim != 1 || offsets->shape[0] != out->shape[0] + 1)
-    return ffi_fail("offsets must have out.shape[0] + 1 entries");
+    return fail("offsets must have out.shape[0] + 1 entries");
   const bool cmp = strcmp(op, "sum") != 0;
   if (cmp) {
     int abits;
-    if (null_array(arg) && out->shape[0] > 0 ) return ffi_fail("arg is required for max/min");
+    if (null_array(arg) && out->shape[0] > 0 ) return fail("arg is required for max/min");
     if (!null_array(arg) && (idbits_of(arg, &abits) || abits != bits))
-      return ffi_fail("arg dtype must equal the offsets dtype");
+      return fail("arg dtype must equal the offsets dtype");
   }
   TensorArg tf, to;
   tf.shape.assign(feat->shape, feat->shape + feat->ndim);
@@ -1350,16 +1345,16 @@ static Registrar r_scatter("sparse._CAPI_DGLKernelScatterAdd",
   *rtc = kNull;
   DGLArray *feat, *idx, *out;
   if (get_array(a, 0, &feat) || get_array(a, 1, &idx) || get_array(a, 2, &out)) return -1;
-  if (!feat || !idx || !out) return ffi_fail("feat / idx / out is required");
+  if (!feat || !idx || !out) return fail("feat / idx / out is required");
   if (null_array(feat)) return 0;
-  if (null_array(out)) return ffi_fail("out is empty but feat is not");
+  if (null_array(out)) return fail("out is empty but feat is not");
   if (seg_arrays_ok({feat, idx, out})) return -1;
   dgla_dtype dt, df;
   int bits;
   if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(idx, &bits)) return -1;
-  if (dt != df) return ffi_fail("feat and out dtypes differ");
+  if (dt != df) return fail("feat and out dtypes differ");
   if (idx->ndim != 1 || idx->shape[0] != feat->shape[0])
-    return ffi_fail("idx must have one entry per row of feat");
+    return fail("idx must have one entry per row of feat");
   TensorArg tf, to;
   to_tensor(feat, &tf);
   to_tensor(out, &to);
@@ -1372,13 +1367,13 @@ static Registrar r_bwdseg("sparse._CAPI_DGLKernelBwdSegmentCmp",
   *rtc = kNull;
   DGLArray *feat, *arg, *out;
   if (get_array(a, 0, &feat) || get_array(a, 1, &arg) || get_array(a, 2, &out)) return -1;
-  if (!feat || !arg || !out) return ffi_fail("feat / arg / out is required");
+  if (!feat || !arg || !out) return fail("feat / arg / out is required");
   if (null_array(feat) || null_array(out)) return 0;  // nothing to scatter / nowhere to write
   if (seg_arrays_ok({feat, arg, out})) return -1;
   dgla_dtype dt, df;
   int bits;
   if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(arg, &bits)) return -1;
-  if (dt != df) return ffi_fail("feat and out dtypes differ");
+  if (dt != df) return fail("feat and out dtypes differ");
   TensorArg tf, to;
   to_tensor(feat, &tf);
   to_tensor(out, &to);
@@ -1388,8 +1383,8 @@ static Registrar r_bwdseg("sparse._CAPI_DGLKernelBwdSegmentCmp",
 // ---- segment / gather mm (src/array/kernel.cc:501-540) ---------------------------------------
 static int mm_dims(const DGLArray* t, int want_ndim, const char* name) {
   if (!t || t->ndim != want_ndim)
-    return ffi_fail(std::string(name) + " must be a " + std::to_string(want_ndim) + "-D array");
-  if (!on_gpu(t)) return ffi_fail(std::string(name) + " is not on a GPU device");
+    return fail(std::string(name) + " must be a " + std::to_string(want_ndim) + "-D array");
+  if (!on_gpu(t)) return fail(std::string(name) + " is not on a GPU device");
   return check_contiguous(t, name);
 }
 
@@ -1403,20 +1398,20 @@ static Registrar r_segmm("sparse._CAPI_DGLKernelSEGMENTMM",
       get_array(a, 3, &seglen) || get_int(a, 4, &a_trans) || get_int(a, 5, &b_trans))
     return -1;
   if (mm_dims(A, 2, "A") || mm_dims(B, 3, "B") || mm_dims(C, 2, "C")) return -1;
-  if (!seglen || seglen->ndim != 1) return ffi_fail("seglen_A must be a 1-D array");
-  if (a_trans) return ffi_fail("segment_mm: A_trans is not supported (the reference never sets it)");
+  if (!seglen || seglen->ndim != 1) return fail("seglen_A must be a 1-D array");
+  if (a_trans) return fail("segment_mm: A_trans is not supported (the reference never sets it)");
   dgla_dtype dt, db, dc;
   int bits;
   if (float_dtype(A, &dt) || float_dtype(B, &db) || float_dtype(C, &dc) || idbits_of(seglen, &bits))
     return -1;
-  if (dt != db || dt != dc) return ffi_fail("A, B and C dtypes differ");
+  if (dt != db || dt != dc) return fail("A, B and C dtypes differ");
   // kernel.cc:47-66 checks
-  if (seglen->shape[0] != B->shape[0]) return ffi_fail("segment_mm expects len(seglen_A) == B.shape[0]");
+  if (seglen->shape[0] != B->shape[0]) return fail("segment_mm expects len(seglen_A) == B.shape[0]");
   const int64_t k = A->shape[1];
   const int64_t n = C->shape[1];
-  if (C->shape[0] != A->shape[0]) return ffi_fail("segment_mm expects C.shape[0] == A.shape[0]");
+  if (C->shape[0] != A->shape[0]) return fail("segment_mm expects C.shape[0] == A.shape[0]");
   if (b_trans ? (B->shape[2] != k || B->shape[1] != n) : (B->shape[1] != k || B->shape[2] != n))
-    return ffi_fail("segment_mm expects A.shape[1] == B.shape[1] (B.shape[2] with B_trans) and C to match");
+    return fail("segment_mm expects A.shape[1] == B.shape[1] (B.shape[2] with B_trans) and C to match");
   const int on_host = on_gpu(seglen) ? 0 : 1;
   return dgla_segment_mm(bits, dt, data_ptr(A), data_ptr(B), data_ptr(C), data_ptr(seglen), on_host,
                          A->shape[0], B->shape[0], k, n, b_trans ? 1 : 0, nullptr, 0, tls_stream);
@@ -1430,15 +1425,15 @@ static Registrar r_segmm_b("sparse._CAPI_DGLKernelSEGMENTMMBackwardB",
   if (get_array(a, 0, &A) || get_array(a, 1, &dC) || get_array(a, 2, &dB) || get_array(a, 3, &seglen))
     return -1;
   if (mm_dims(A, 2, "A") || mm_dims(dC, 2, "dC") || mm_dims(dB, 3, "dB")) return -1;
-  if (!seglen || seglen->ndim != 1) return ffi_fail("seglen must be a 1-D array");
+  if (!seglen || seglen->ndim != 1) return fail("seglen must be a 1-D array");
   dgla_dtype dt, d2, d3;
   int bits;
   if (float_dtype(A, &dt) || float_dtype(dC, &d2) || float_dtype(dB, &d3) || idbits_of(seglen, &bits))
     return -1;
-  if (dt != d2 || dt != d3) return ffi_fail("A, dC and dB dtypes differ");
-  if (A->shape[0] != dC->shape[0]) return ffi_fail("segment_mm backward expects A and dC to have the same rows");
+  if (dt != d2 || dt != d3) return fail("A, dC and dB dtypes differ");
+  if (A->shape[0] != dC->shape[0]) return fail("segment_mm backward expects A and dC to have the same rows");
   if (seglen->shape[0] != dB->shape[0] || dB->shape[1] != A->shape[1] || dB->shape[2] != dC->shape[1])
-    return ffi_fail("segment_mm backward expects dB of shape (len(seglen), A.shape[1], dC.shape[1])");
+    return fail("segment_mm backward expects dB of shape (len(seglen), A.shape[1], dC.shape[1])");
   return dgla_segment_mm_backward_b(bits, dt, data_ptr(A), data_ptr(dC), data_ptr(dB), data_ptr(seglen),
                                     on_gpu(seglen) ? 0 : 1, A->shape[0], dB->shape[0], A->shape[1],
                                     dC->shape[1], nullptr, 0, tls_stream);
@@ -1453,22 +1448,22 @@ static int gather_mm_ffi(const FfiArgs& a, bool scatter) {
   if (mm_dims(A, 2, "A") || mm_dims(B, 3, "B") || mm_dims(C, 2, "C")) return -1;
   dgla_dtype dt, d2, d3;
   if (float_dtype(A, &dt) || float_dtype(B, &d2) || float_dtype(C, &d3)) return -1;
-  if (dt != d2 || dt != d3) return ffi_fail("A, B and C dtypes differ");
+  if (dt != d2 || dt != d3) return fail("A, B and C dtypes differ");
   int bits = 0;
   int64_t rows = -1;
   for (DGLArray* t : {ia, ib, ic}) {
     if (null_array(t)) continue;
     int b;
-    if (!on_gpu(t)) return ffi_fail("index arrays must be on the GPU");
+    if (!on_gpu(t)) return fail("index arrays must be on the GPU");
     if (idbits_of(t, &b)) return -1;
-    if (bits && b != bits) return ffi_fail("index arrays must share one dtype");
-    if (rows >= 0 && t->shape[0] != rows) return ffi_fail("index arrays must have the same length");
+    if (bits && b != bits) return fail("index arrays must share one dtype");
+    if (rows >= 0 && t->shape[0] != rows) return fail("index arrays must have the same length");
     bits = b;
     rows = t->shape[0];
   }
-  if (rows < 0) return ffi_fail("gather_mm needs at least one index array");
-  if (A->shape[1] != B->shape[1]) return ffi_fail("gather_mm expects A.shape[1] == B.shape[1]");
-  if (C->shape[1] != B->shape[2]) return ffi_fail("gather_mm expects C.shape[1] == B.shape[2]");
+  if (rows < 0) return fail("gather_mm needs at least one index array");
+  if (A->shape[1] != B->shape[1]) return fail("gather_mm expects A.shape[1] == B.shape[1]");
+  if (C->shape[1] != B->shape[2]) return fail("gather_mm expects C.shape[1] == B.shape[2]");
   auto ptr = [](DGLArray* t) { return null_array(t) ? nullptr : data_ptr(t); };
   return dgla_gather_mm(bits, dt, data_ptr(A), data_ptr(B), data_ptr(C), ptr(ia), ptr(ib), ptr(ic),
                         rows, A->shape[1], B->shape[2], tls_stream);
@@ -1513,7 +1508,7 @@ struct HeteroGraphObj {
 static uint32_t magic_of(const void* h) { return h ? *static_cast<const uint32_t*>(h) : 0; }
 
 static Registrar r_value("_Value", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
-  if (a.n != 1) return ffi_fail("_Value takes one argument");
+  if (a.n != 1) return fail("_Value takes one argument");
   ObjValue* o = new ObjValue();
   o->v = a.v[0];
   o->tc = a.tc[0];
@@ -1549,7 +1544,7 @@ static int get_list(const FfiArgs& a, int i, const ObjList** out) {
     return 0;
   }
   if (get_handle(a, i, &h) || magic_of(h) != kMagicList)
-    return ffi_fail("argument " + std::to_string(i) + ": expected a list (see _List)");
+    return fail("argument " + std::to_string(i) + ": expected a list (see _List)");
   *out = static_cast<const ObjList*>(h);
   return 0;
 }
@@ -1558,7 +1553,7 @@ static int get_list(const FfiArgs& a, int i, const ObjList** out) {
 static int list_array(const ObjList* l, size_t i, DGLArray** out) {
   *out = nullptr;
   if (i >= l->items.size() || l->items[i].tc == kNull) return 0;
-  if (!is_array(l->items[i].tc)) return ffi_fail("list entry " + std::to_string(i) + " is not an NDArray");
+  if (!is_array(l->items[i].tc)) return fail("list entry " + std::to_string(i) + " is not an NDArray");
   *out = static_cast<DGLArray*>(l->items[i].v.v_handle);
   return 0;
 }
@@ -1568,7 +1563,7 @@ static Registrar r_hg_create("dgl_amd._CAPI_HeteroGraphCreate",
                              [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   int64_t nt;
   if (get_int(a, 0, &nt)) return -1;
-  if ((a.n - 1) % 3) return ffi_fail("expected (num_ntypes, [unit graph, src ntype, dst ntype] ...)");
+  if ((a.n - 1) % 3) return fail("expected (num_ntypes, [unit graph, src ntype, dst ntype] ...)");
   HeteroGraphObj* hg = new HeteroGraphObj();
   hg->num_ntypes = static_cast<int>(nt);
   for (int i = 1; i < a.n; i += 3) {
@@ -1577,7 +1572,7 @@ static Registrar r_hg_create("dgl_amd._CAPI_HeteroGraphCreate",
     if (get_handle(a, i, &h) || get_int(a, i + 1, &s) || get_int(a, i + 2, &d) ||
         magic_of(h) != kMagicUnit || s < 0 || s >= nt || d < 0 || d >= nt) {
       delete hg;
-      return ffi_fail("bad relation " + std::to_string((i - 1) / 3));
+      return fail("bad relation " + std::to_string((i - 1) / 3));
     }
     hg->rel.push_back(static_cast<UnitGraph*>(h));
     hg->src.push_back(static_cast<int>(s));
@@ -1718,11 +1713,11 @@ static int spmm_unit(UnitGraph* g, const char* op, const char* reduce, dgla_dtyp
     return rc;
   }
   if (g->coo.present) {
-    if (accumulate) return ffi_fail("accumulating SpMM needs the CSC format");  // kernel.cc:212-217
+    if (accumulate) return fail("accumulating SpMM needs the CSC format");  // kernel.cc:212-217
     const dgla_coo coo = coo_of(g);
     return dgla_spmm_coo(op, reduce, &coo, dt, u, e, v, arg_u, arg_e, tls_stream);
   }
-  return ffi_fail("SpMM only supports CSC and COO formats");
+  return fail("SpMM only supports CSC and COO formats");
 }
 
 // (hg, op, reduce, List U [by src ntype], List E [by etype], List V [by dst ntype],
@@ -1739,10 +1734,10 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
       get_list(a, 4, &LE) || get_list(a, 5, &LV) || get_list(a, 6, &LAU) || get_list(a, 7, &LAE) ||
       get_list(a, 8, &LUT) || get_list(a, 9, &LET))
     return -1;
-  if (magic_of(h) != kMagicHetero) return ffi_fail("argument 0: expected a heterograph handle");
+  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
   HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
   const bool is_sum = !strcmp(reduce, "sum"), is_max = !strcmp(reduce, "max");
-  if (!is_sum && !is_max && strcmp(reduce, "min")) return ffi_fail(std::string("Unsupported SpMM reducer: ") + reduce);
+  if (!is_sum && !is_max && strcmp(reduce, "min")) return fail(std::string("Unsupported SpMM reducer: ") + reduce);
   const bool use_u = strcmp(op, "copy_rhs") != 0, use_e = strcmp(op, "copy_lhs") != 0;
   const size_t n_et = hg->rel.size();
 
@@ -1763,7 +1758,7 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
     if (float_dtype(V, &dt)) return -1;
     for (const DGLArray* t : {U, E, V, AU, AE}) {
       if (null_array(t)) continue;
-      if (!on_gpu(t)) return ffi_fail("array is not on the GPU device of the graph");
+      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
       if (check_contiguous(t, "array")) return -1;
     }
     const int64_t n_out = numel(V);
@@ -1785,8 +1780,8 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
       if (!null_array(ET) && fill_index(g->idbits, data_ptr(ET), n_out, -1)) return -1;
     }
     if (g->num_edges == 0) continue;
-    if (use_u && null_array(AU)) return ffi_fail("Arg_U is required for max/min");
-    if (use_e && null_array(AE)) return ffi_fail("Arg_E is required for max/min");
+    if (use_u && null_array(AU)) return fail("Arg_U is required for max/min");
+    if (use_e && null_array(AE)) return fail("Arg_E is required for max/min");
     // candidate of this relation into scratch, then the strict running compare
     const size_t vb = static_cast<size_t>(n_out) * dtype_bytes(dt);
     const size_t ib = static_cast<size_t>(n_out) * (g->idbits / 8);
@@ -1835,8 +1830,8 @@ static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
   if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_list(a, 2, &LL) || get_list(a, 3, &LR) ||
       get_list(a, 4, &LO) || get_int(a, 5, &lt) || get_int(a, 6, &rt))
     return -1;
-  if (magic_of(h) != kMagicHetero) return ffi_fail("argument 0: expected a heterograph handle");
-  if (lt < 0 || lt > 2 || rt < 0 || rt > 2) return ffi_fail("targets must be 0 (u), 1 (e) or 2 (v)");
+  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
+  if (lt < 0 || lt > 2 || rt < 0 || rt > 2) return fail("targets must be 0 (u), 1 (e) or 2 (v)");
   HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
   for (size_t et = 0; et < hg->rel.size(); ++et) {
     UnitGraph* g = hg->rel[et];
@@ -1851,7 +1846,7 @@ static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
     if (float_dtype(out, &dt)) return -1;
     for (const DGLArray* t : {lhs, rhs, out}) {
       if (null_array(t)) continue;
-      if (!on_gpu(t)) return ffi_fail("array is not on the GPU device of the graph");
+      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
       if (check_contiguous(t, "array")) return -1;
     }
     TensorArg l, r, o;
@@ -1866,7 +1861,7 @@ static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
       const dgla_csr csr = csr_of(g, g->csr, false);
       rc = dgla_sddmm_csr(op, &csr, dt, &l.t, &r.t, &o.t, static_cast<int>(lt), static_cast<int>(rt), tls_stream);
     } else {
-      return ffi_fail("SDDMM only supports CSR and COO formats");
+      return fail("SDDMM only supports CSR and COO formats");
     }
     if (rc) return rc;
   }
@@ -1888,7 +1883,7 @@ static Registrar r_ugmm("sparse._CAPI_DGLKernelUpdateGradMinMaxHetero",
   if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_list(a, 2, &LF) || get_list(a, 3, &LI) ||
       get_list(a, 4, &LT) || get_list(a, 5, &LO))
     return -1;
-  if (magic_of(h) != kMagicHetero) return ffi_fail("argument 0: expected a heterograph handle");
+  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
   const bool lhs = strcmp(op, "copy_lhs") == 0;
   if (!lhs && strcmp(op, "copy_rhs") != 0) return 0;  // segment_reduce.cuh:190: other operators: no-op
   HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
@@ -1910,9 +1905,9 @@ static Registrar r_ugmm("sparse._CAPI_DGLKernelUpdateGradMinMaxHetero",
     dgla_dtype dt;
     int bi, bt;
     if (float_dtype(feat, &dt) || idbits_of(idx, &bi) || idbits_of(idt, &bt)) return -1;
-    if (bi != bt) return ffi_fail("idx and idx_type must have the same integer type");
+    if (bi != bt) return fail("idx and idx_type must have the same integer type");
     for (const DGLArray* t : {feat, idx, idt, out}) {
-      if (!on_gpu(t)) return ffi_fail("array is not on the GPU device of the graph");
+      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
       if (check_contiguous(t, "array")) return -1;
     }
     TensorArg f, o;

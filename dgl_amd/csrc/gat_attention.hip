@@ -934,15 +934,15 @@ size_t dgla_gat_attention_workspace_bytes(const dgla_csr* csc, int64_t heads, in
 int dgla_gat_attention_forward(const dgla_csr* csc, dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el,
                                const dgla_tensor* er, float negative_slope, const dgla_tensor* out, void* mz,
                                void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !present(out) || (!mz && csc->num_rows > 0)) return gfail("gat_attention_forward: csc / out / mz are required");
+  if (!csc || !present(out) || (!mz && csc->num_rows > 0)) return fail("gat_attention_forward: csc / out / mz are required");
   Shape sh;
   if (shape_of(dtype, ft, el, er, &sh)) return -1;
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return gfail("idtype must be int32 or int64");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows || out->ndim != 3 ||
       out->shape[0] != csc->num_rows || out->shape[1] != sh.H || out->shape[2] != sh.D)
-    return gfail("gat_attention_forward: tensor shapes do not match the graph");
+    return fail("gat_attention_forward: tensor shapes do not match the graph");
   if (csc->nnz > 0 && (!workspace || workspace_bytes < dgla_gat_attention_workspace_bytes(csc, sh.H, sh.D)))
-    return gfail("gat_attention_forward: workspace too small (dgla_gat_attention_workspace_bytes)");
+    return fail("gat_attention_forward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   if (!sh.legacy) {
@@ -970,24 +970,24 @@ int dgla_gat_attention_backward(const dgla_csr* csc, const dgla_csr* csr, dgla_d
                                 void* hip_stream) {
   if (!csc || !csr || !present(out) || !present(dout) || !present(d_ft) || !present(d_el) || !present(d_er) ||
       (!mz && csc->num_rows > 0))
-    return gfail("gat_attention_backward: every tensor is required");
+    return fail("gat_attention_backward: every tensor is required");
   Shape sh;
   if (shape_of(dtype, ft, el, er, &sh)) return -1;
   if (csc->idtype_bits != csr->idtype_bits || (csc->idtype_bits != 32 && csc->idtype_bits != 64))
-    return gfail("gat_attention_backward: the two CSRs must share one id type (int32 or int64)");
+    return fail("gat_attention_backward: the two CSRs must share one id type (int32 or int64)");
   if (csc->nnz != csr->nnz || csc->num_rows != csr->num_cols || csc->num_cols != csr->num_rows)
-    return gfail("gat_attention_backward: csr is not the out-edge CSR of csc's graph");
+    return fail("gat_attention_backward: csr is not the out-edge CSR of csc's graph");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows)
-    return gfail("gat_attention_backward: tensor shapes do not match the graph");
+    return fail("gat_attention_backward: tensor shapes do not match the graph");
   for (const dgla_tensor* t : {out, dout})
     if (t->ndim != 3 || t->shape[0] != csc->num_rows || t->shape[1] != sh.H || t->shape[2] != sh.D)
-      return gfail("gat_attention_backward: out / dout must be (N_dst, H, D)");
+      return fail("gat_attention_backward: out / dout must be (N_dst, H, D)");
   if (d_ft->ndim != 3 || d_ft->shape[0] != ft->shape[0] || d_ft->shape[1] != sh.H || d_ft->shape[2] != sh.D ||
       d_el->ndim != 3 || d_el->shape[0] != el->shape[0] || d_el->shape[1] != sh.H || d_el->shape[2] != 1 ||
       d_er->ndim != 3 || d_er->shape[0] != er->shape[0] || d_er->shape[1] != sh.H || d_er->shape[2] != 1)
-    return gfail("gat_attention_backward: d_ft / d_el / d_er must have the shapes of ft / el / er");
+    return fail("gat_attention_backward: d_ft / d_el / d_er must have the shapes of ft / el / er");
   if (csc->nnz > 0 && (!workspace || workspace_bytes < dgla_gat_attention_workspace_bytes(csc, sh.H, sh.D)))
-    return gfail("gat_attention_backward: workspace too small (dgla_gat_attention_workspace_bytes)");
+    return fail("gat_attention_backward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, d_ft->data);
   if (!sh.legacy) {

@@ -11,11 +11,6 @@ namespace {
 
 constexpr int kGatChunk = 512;  // edges per wavefront
 
-int gfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
 // exp(x) for x <= 0 on v_exp_f32 with the product x * log2(e) carried as hi + lo (same routine as the fused edge
 // softmax, csrc/edge_softmax.hip: |relative error| < 3e-7 over [-88, 0]; exp(-inf) = 0)
 __device__ __forceinline__ float gat_exp(float x) {
@@ -250,8 +245,6 @@ __global__ __launch_bounds__(64) void gat_sum_wide_fixup_kernel(const int64_t* _
   }
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 int pad4(int x) { return (x + 3) & ~3; }  // partial states start on 16-byte boundaries
 
 int64_t num_chunks(int64_t nnz) { return (nnz + kGatChunk - 1) / kGatChunk; }
@@ -292,14 +285,14 @@ bool present(const dgla_tensor* t) {
 }
 
 int shape_of(dgla_dtype dtype, const dgla_tensor* ft, const dgla_tensor* el, const dgla_tensor* er, Shape* s) {
-  if (!present(ft) || !present(el) || !present(er)) return gfail("gat_attention: ft / el / er are required");
+  if (!present(ft) || !present(el) || !present(er)) return fail("gat_attention: ft / el / er are required");
   if (ft->ndim != 3 || el->ndim != 3 || er->ndim != 3 || el->shape[2] != 1 || er->shape[2] != 1)
-    return gfail("gat_attention: ft must be (N_src, H, D), el (N_src, H, 1), er (N_dst, H, 1)");
+    return fail("gat_attention: ft must be (N_src, H, D), el (N_src, H, 1), er (N_dst, H, 1)");
   const int64_t H = ft->shape[1], D = ft->shape[2];
   if (el->shape[1] != H || er->shape[1] != H || el->shape[0] != ft->shape[0])
-    return gfail("gat_attention: head counts / node counts of ft, el, er differ");
+    return fail("gat_attention: head counts / node counts of ft, el, er differ");
   if (!accepted(dtype, H, D, &s->V, &s->lph_log2))
-    return gfail("gat_attention: needs fp32 / fp16 / bf16 operands with H * next_pow2(ceil(D / V)) <= 64, V = min(16 / "
+    return fail("gat_attention: needs fp32 / fp16 / bf16 operands with H * next_pow2(ceil(D / V)) <= 64, V = min(16 / "
                  "sizeof(element), largest power of two dividing D) (dgla_gat_attention_supported; use the composed "
                  "operators otherwise)");
   s->H = static_cast<int>(H);

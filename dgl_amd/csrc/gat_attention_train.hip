@@ -515,7 +515,7 @@ int weights_typed(const dgla_csr* csc, int H, const void* el, const void* er, co
 int drop_of(const char* who, float p, uint64_t seed, Drop* dr) {
   dr->seed = seed;
   if (!gat_dropout_params(p, &dr->threshold, &dr->scale))
-    return gfail(std::string(who) + ": the dropout probability p must lie in [0, 1)");
+    return fail(std::string(who) + ": the dropout probability p must lie in [0, 1)");
   return 0;
 }
 
@@ -531,17 +531,17 @@ int dgla_gat_attention_train_forward(const dgla_csr* csc, dgla_dtype dtype, cons
                                      const dgla_tensor* out, void* mz, void* workspace, size_t workspace_bytes,
                                      void* hip_stream) {
   if (!csc || !present(out) || (!mz && csc->num_rows > 0))
-    return gfail("gat_attention_train_forward: csc / out / mz are required");
+    return fail("gat_attention_train_forward: csc / out / mz are required");
   Drop dr;
   if (drop_of("gat_attention_train_forward", p, seed, &dr)) return -1;
   Shape sh;
   if (shape_of(dtype, ft, el, er, &sh)) return -1;
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return gfail("idtype must be int32 or int64");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows || out->ndim != 3 ||
       out->shape[0] != csc->num_rows || out->shape[1] != sh.H || out->shape[2] != sh.D)
-    return gfail("gat_attention_train_forward: tensor shapes do not match the graph");
+    return fail("gat_attention_train_forward: tensor shapes do not match the graph");
   if (csc->nnz > 0 && (!workspace || workspace_bytes < dgla_gat_attention_workspace_bytes(csc, sh.H, sh.D)))
-    return gfail("gat_attention_train_forward: workspace too small (dgla_gat_attention_workspace_bytes)");
+    return fail("gat_attention_train_forward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   WidePtrs q{};
@@ -559,25 +559,25 @@ int dgla_gat_attention_train_backward(const dgla_csr* csc, const dgla_csr* csr, 
                                       const dgla_tensor* d_el, const dgla_tensor* d_er, void* workspace,
                                       size_t workspace_bytes, void* hip_stream) {
   if (!csc || !csr || !present(dout) || !present(d_ft) || !present(d_el) || !present(d_er) || (!mz && csc->num_rows > 0))
-    return gfail("gat_attention_train_backward: every tensor is required");
+    return fail("gat_attention_train_backward: every tensor is required");
   Drop dr;
   if (drop_of("gat_attention_train_backward", p, seed, &dr)) return -1;
   Shape sh;
   if (shape_of(dtype, ft, el, er, &sh)) return -1;
   if (csc->idtype_bits != csr->idtype_bits || (csc->idtype_bits != 32 && csc->idtype_bits != 64))
-    return gfail("gat_attention_train_backward: the two CSRs must share one id type (int32 or int64)");
+    return fail("gat_attention_train_backward: the two CSRs must share one id type (int32 or int64)");
   if (csc->nnz != csr->nnz || csc->num_rows != csr->num_cols || csc->num_cols != csr->num_rows)
-    return gfail("gat_attention_train_backward: csr is not the out-edge CSR of csc's graph");
+    return fail("gat_attention_train_backward: csr is not the out-edge CSR of csc's graph");
   if (ft->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows)
-    return gfail("gat_attention_train_backward: tensor shapes do not match the graph");
+    return fail("gat_attention_train_backward: tensor shapes do not match the graph");
   if (dout->ndim != 3 || dout->shape[0] != csc->num_rows || dout->shape[1] != sh.H || dout->shape[2] != sh.D)
-    return gfail("gat_attention_train_backward: dout must be (N_dst, H, D)");
+    return fail("gat_attention_train_backward: dout must be (N_dst, H, D)");
   if (d_ft->ndim != 3 || d_ft->shape[0] != ft->shape[0] || d_ft->shape[1] != sh.H || d_ft->shape[2] != sh.D ||
       d_el->ndim != 3 || d_el->shape[0] != el->shape[0] || d_el->shape[1] != sh.H || d_el->shape[2] != 1 ||
       d_er->ndim != 3 || d_er->shape[0] != er->shape[0] || d_er->shape[1] != sh.H || d_er->shape[2] != 1)
-    return gfail("gat_attention_train_backward: d_ft / d_el / d_er must have the shapes of ft / el / er");
+    return fail("gat_attention_train_backward: d_ft / d_el / d_er must have the shapes of ft / el / er");
   if (csc->nnz > 0 && (!workspace || workspace_bytes < dgla_gat_attention_workspace_bytes(csc, sh.H, sh.D)))
-    return gfail("gat_attention_train_backward: workspace too small (dgla_gat_attention_workspace_bytes)");
+    return fail("gat_attention_train_backward: workspace too small (dgla_gat_attention_workspace_bytes)");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, d_ft->data);
   WidePtrs q{};
@@ -596,19 +596,19 @@ int dgla_gat_attention_weights(const dgla_csr* csc, dgla_dtype dtype, const dgla
                                const void* mz, float negative_slope, float p, uint64_t seed, const dgla_tensor* attn,
                                void* hip_stream) {
   if (!csc || !present(el) || !present(er) || !present(attn) || (!mz && csc->num_rows > 0))
-    return gfail("gat_attention_weights: csc / el / er / mz / attn are required");
+    return fail("gat_attention_weights: csc / el / er / mz / attn are required");
   Drop dr;
   if (drop_of("gat_attention_weights", p, seed, &dr)) return -1;
   if (dtype != DGLA_F32 && dtype != DGLA_F16 && dtype != DGLA_BF16)
-    return gfail("gat_attention_weights: needs fp32 / fp16 / bf16 operands");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return gfail("idtype must be int32 or int64");
+    return fail("gat_attention_weights: needs fp32 / fp16 / bf16 operands");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
   if (el->ndim != 3 || er->ndim != 3 || el->shape[2] != 1 || er->shape[2] != 1 || el->shape[1] != er->shape[1] ||
       el->shape[1] < 1 || el->shape[1] > 64 || el->shape[0] != csc->num_cols || er->shape[0] != csc->num_rows)
-    return gfail("gat_attention_weights: el must be (N_src, H, 1), er (N_dst, H, 1) with 1 <= H <= 64");
+    return fail("gat_attention_weights: el must be (N_src, H, 1), er (N_dst, H, 1) with 1 <= H <= 64");
   const int H = static_cast<int>(el->shape[1]);
   if ((attn->ndim != 2 && attn->ndim != 3) || attn->shape[0] != csc->nnz || attn->shape[1] != H ||
       (attn->ndim == 3 && attn->shape[2] != 1))
-    return gfail("gat_attention_weights: attn must be (E, H, 1)");
+    return fail("gat_attention_weights: attn must be (E, H, 1)");
   if (csc->nnz <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, attn->data);
@@ -629,8 +629,8 @@ int dgla_gat_dropout_mask_host(uint64_t seed, float p, const int64_t* eids, int6
   uint32_t threshold;
   float scale;
   if (!gat_dropout_params(p, &threshold, &scale))
-    return gfail("gat_dropout_mask_host: the dropout probability p must lie in [0, 1)");
-  if (n < 0 || heads < 1 || (n > 0 && (!eids || !keep))) return gfail("gat_dropout_mask_host: eids / keep / heads are required");
+    return fail("gat_dropout_mask_host: the dropout probability p must lie in [0, 1)");
+  if (n < 0 || heads < 1 || (n > 0 && (!eids || !keep))) return fail("gat_dropout_mask_host: eids / keep / heads are required");
   for (int64_t i = 0; i < n; ++i)
     for (int h = 0; h < heads; ++h)
       keep[i * heads + h] = gat_keep(seed, static_cast<uint64_t>(eids[i]), h, threshold) ? 1 : 0;

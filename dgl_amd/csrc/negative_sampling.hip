@@ -30,34 +30,25 @@
 #include "../../include/dgl_amd.h"
 
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <utility>
 
-#include "common.h"
+#include "host_util.h"
 #include "negative_sample_step.h"
 #include "sort.hip.h"
 
 namespace dgla {
 namespace {
 
-int gfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
-constexpr int kNegBlock = 256;
+constexpr int kNegBlock = 256;         // every launch here: grid1(n) blocks of kNegBlock threads
 constexpr int kNegMaxBucketBits = 30;  // B + 1 int32 row starts must stay addressable with int32 ids
-
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-unsigned grid1(int64_t n) { return static_cast<unsigned>((n + kNegBlock - 1) / kNegBlock < 1 ? 1 : (n + kNegBlock - 1) / kNegBlock); }
+static_assert(kNegBlock == 256, "grid1 counts blocks of 256");
 
 int bucket_bits(int64_t n) {
   const int b = msd::bits_for(n);
   return b > kNegMaxBucketBits ? kNegMaxBucketBits : b;
 }
-
-template <typename T>
-using gptr = const __attribute__((address_space(1))) T*;
 
 // ---- draw -------------------------------------------------------------------------------------
 // Slot i: pu[i], pv[i] = the pair or -1, flag[i] = accepted.  REPLACE: cnt[block] = accepted slots of the workgroup
@@ -185,38 +176,37 @@ struct NegLayout {  // offsets into the workspace of dgla_negative_sample
 
 NegLayout neg_layout(int idtype_bits, int64_t n) {
   NegLayout L{};
-  const size_t w = idtype_bits == 32 ? 4 : 8, ids = align256(w * static_cast<size_t>(n)),
-               words = align256(sizeof(int32_t) * static_cast<size_t>(n));
+  const size_t ids = (idtype_bits == 32 ? 4 : 8) * static_cast<size_t>(n), words = sizeof(int32_t) * static_cast<size_t>(n);
   L.nb = (n + kNegBlock - 1) / kNegBlock;
   L.kb = bucket_bits(n);
   const int64_t B = int64_t(1) << L.kb;
-  size_t o = 0;
-  L.pu = o, o += ids;
-  L.pv = o, o += ids;
-  L.flag = o, o += words;
-  L.cnt = o, o += align256(sizeof(int32_t) * static_cast<size_t>(L.nb + 1));
-  L.base = o, o += align256(sizeof(int32_t) * static_cast<size_t>(L.nb + 1));
-  L.scan = o, o += msd::scan_temp_bytes(L.nb + 1, sizeof(int32_t));
+  Carver c;
+  L.pu = c.take(ids);
+  L.pv = c.take(ids);
+  L.flag = c.take(words);
+  L.cnt = c.take(sizeof(int32_t) * static_cast<size_t>(L.nb + 1));
+  L.base = c.take(sizeof(int32_t) * static_cast<size_t>(L.nb + 1));
+  L.scan = c.take(msd::scan_temp_bytes(L.nb + 1, sizeof(int32_t)));
   // the duplicate search (sized whatever `replace` is: the size query does not know it)
-  L.row = o, o += words;
-  L.s_flag = o, o += words;
-  L.s_slot = o, o += words;
-  L.bstart = o, o += align256(sizeof(int32_t) * static_cast<size_t>(B + 1));
-  L.sort = o;
+  L.row = c.take(words);
+  L.s_flag = c.take(words);
+  L.s_slot = c.take(words);
+  L.bstart = c.take(sizeof(int32_t) * static_cast<size_t>(B + 1));
   L.sort_bytes = align256(dgla_coo_to_csr_workspace_bytes(32, B, n));
-  L.bytes = o + L.sort_bytes;
+  L.sort = c.take(L.sort_bytes);
+  L.bytes = c.bytes();
   return L;
 }
 
 int check_has_edges(const char* who, const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n,
                     const void* out) {
   const std::string w = std::string(who) + ": ";
-  if (!csr) return gfail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return gfail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0 || n < 0) return gfail(w + "negative size");
-  if (csr->num_rows > 0 && !csr->indptr) return gfail(w + "indptr is null");
-  if (csr->nnz > 0 && !member) return gfail(w + "member is null");
-  if (n > 0 && (!u || !v || !out)) return gfail(w + "u / v / out are null");
+  if (!csr) return fail(w + "csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
+  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0 || n < 0) return fail(w + "negative size");
+  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
+  if (csr->nnz > 0 && !member) return fail(w + "member is null");
+  if (n > 0 && (!u || !v || !out)) return fail(w + "u / v / out are null");
   return 0;
 }
 
@@ -224,19 +214,19 @@ int check_has_edges(const char* who, const dgla_csr* csr, const void* member, co
 int check_neg(const char* who, const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
               const void* out_src, const void* out_dst, const void* out_count) {
   const std::string w = std::string(who) + ": ";
-  if (!csr) return gfail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return gfail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return gfail(w + "negative size");
-  if (n_slots < 0 || num_samples < 0) return gfail(w + "negative number of slots / samples");
+  if (!csr) return fail(w + "csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
+  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return fail(w + "negative size");
+  if (n_slots < 0 || num_samples < 0) return fail(w + "negative number of slots / samples");
   if (n_slots >= (int64_t(1) << 31) || num_samples >= (int64_t(1) << 31))
-    return gfail(w + "n_slots and num_samples must be below 2^31, got " + std::to_string(n_slots) + " and " +
+    return fail(w + "n_slots and num_samples must be below 2^31, got " + std::to_string(n_slots) + " and " +
                  std::to_string(num_samples));
   if (num_trials < 1 || num_trials > kNegMaxTrials)
-    return gfail(w + "num_trials must be in 1 .. " + std::to_string(kNegMaxTrials) + ", got " + std::to_string(num_trials));
-  if (csr->num_rows > 0 && !csr->indptr) return gfail(w + "indptr is null");
-  if (csr->nnz > 0 && !member) return gfail(w + "member is null");
-  if (num_samples > 0 && (!out_src || !out_dst)) return gfail(w + "out_src / out_dst are null");
-  if (!out_count) return gfail(w + "out_count is null");
+    return fail(w + "num_trials must be in 1 .. " + std::to_string(kNegMaxTrials) + ", got " + std::to_string(num_trials));
+  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
+  if (csr->nnz > 0 && !member) return fail(w + "member is null");
+  if (num_samples > 0 && (!out_src || !out_dst)) return fail(w + "out_src / out_dst are null");
+  if (!out_count) return fail(w + "out_count is null");
   return 0;
 }
 
@@ -322,40 +312,37 @@ int dgla_negative_sample(const dgla_csr* csr, const void* member, int64_t n_slot
   if (drawable) {
     L = neg_layout(csr->idtype_bits, n_slots);
     if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-      return gfail("negative_sample: workspace of " + std::to_string(L.bytes) + " bytes required");
+      return fail("negative_sample: workspace of " + std::to_string(L.bytes) + " bytes required");
   }
   const DeviceGuard dev(s, out_count);
   if (!drawable) {
-    if (csr->idtype_bits == 32)
-      hipLaunchKernelGGL(neg_fill_kernel<int32_t>, dim3(grid1(num_samples)), dim3(kNegBlock), 0, s, num_samples,
-                         static_cast<int32_t*>(out_src), static_cast<int32_t*>(out_dst), out_count);
-    else
-      hipLaunchKernelGGL(neg_fill_kernel<int64_t>, dim3(grid1(num_samples)), dim3(kNegBlock), 0, s, num_samples,
-                         static_cast<int64_t*>(out_src), static_cast<int64_t*>(out_dst), out_count);
+    with_idx(csr->idtype_bits, [&](auto tag) {
+      using Idx = decltype(tag);
+      hipLaunchKernelGGL(neg_fill_kernel<Idx>, dim3(grid1(num_samples)), dim3(kNegBlock), 0, s, num_samples,
+                         static_cast<Idx*>(out_src), static_cast<Idx*>(out_dst), out_count);
+    });
     DGLA_CHECK_HIP(hipGetLastError());
     return 0;
   }
   char* ws = static_cast<char*>(workspace);
-  return csr->idtype_bits == 32
-             ? run_neg<int32_t>(csr, member, n_slots, num_samples, num_trials, exclude_self_loops != 0, replace != 0, seed,
-                                out_src, out_dst, out_count, ws, L, s)
-             : run_neg<int64_t>(csr, member, n_slots, num_samples, num_trials, exclude_self_loops != 0, replace != 0, seed,
-                                out_src, out_dst, out_count, ws, L, s);
+  return with_idx(csr->idtype_bits, [&](auto tag) {
+    return run_neg<decltype(tag)>(csr, member, n_slots, num_samples, num_trials, exclude_self_loops != 0, replace != 0, seed,
+                                  out_src, out_dst, out_count, ws, L, s);
+  });
 }
 
 int dgla_negative_sample_host(const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
                               int exclude_self_loops, int replace, uint64_t seed, void* out_src, void* out_dst,
                               int64_t* out_count) {
   if (check_neg("negative_sample_host", csr, member, n_slots, num_samples, num_trials, out_src, out_dst, out_count)) return -1;
-  const bool rep = replace != 0;
-#define DGLA_NEG_HOST(Idx, E) \
-  neg_host<Idx, E>(csr, member, n_slots, num_samples, num_trials, rep, seed, out_src, out_dst, out_count)
-  if (csr->idtype_bits == 32) {
-    if (exclude_self_loops) DGLA_NEG_HOST(int32_t, true); else DGLA_NEG_HOST(int32_t, false);
-  } else {
-    if (exclude_self_loops) DGLA_NEG_HOST(int64_t, true); else DGLA_NEG_HOST(int64_t, false);
-  }
-#undef DGLA_NEG_HOST
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    auto run = [&](auto excl) {
+      neg_host<Idx, decltype(excl)::value>(csr, member, n_slots, num_samples, num_trials, replace != 0, seed, out_src,
+                                           out_dst, out_count);
+    };
+    if (exclude_self_loops) run(std::true_type{}); else run(std::false_type{});
+  });
   return 0;
 }
 
@@ -365,29 +352,25 @@ int dgla_csr_has_edges(const dgla_csr* csr, const void* member, const void* u, c
   if (n == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
-  if (csr->idtype_bits == 32)
-    hipLaunchKernelGGL(has_edges_kernel<int32_t>, dim3(grid1(n)), dim3(kNegBlock), 0, s,
-                       static_cast<const int32_t*>(csr->indptr), static_cast<const int32_t*>(member), csr->num_rows,
-                       csr->num_cols, static_cast<const int32_t*>(u), static_cast<const int32_t*>(v), n, out);
-  else
-    hipLaunchKernelGGL(has_edges_kernel<int64_t>, dim3(grid1(n)), dim3(kNegBlock), 0, s,
-                       static_cast<const int64_t*>(csr->indptr), static_cast<const int64_t*>(member), csr->num_rows,
-                       csr->num_cols, static_cast<const int64_t*>(u), static_cast<const int64_t*>(v), n, out);
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    hipLaunchKernelGGL(has_edges_kernel<Idx>, dim3(grid1(n)), dim3(kNegBlock), 0, s, static_cast<const Idx*>(csr->indptr),
+                       static_cast<const Idx*>(member), csr->num_rows, csr->num_cols, static_cast<const Idx*>(u),
+                       static_cast<const Idx*>(v), n, out);
+  });
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 int dgla_csr_has_edges_host(const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n, uint8_t* out) {
   if (check_has_edges("csr_has_edges_host", csr, member, u, v, n, out)) return -1;
-  for (int64_t i = 0; i < n; ++i) {
-    if (csr->idtype_bits == 32)
-      out[i] = neg_has_edge(static_cast<const int32_t*>(csr->indptr), static_cast<const int32_t*>(member), csr->num_rows,
-                            csr->num_cols, static_cast<int64_t>(static_cast<const int32_t*>(u)[i]),
-                            static_cast<int64_t>(static_cast<const int32_t*>(v)[i]));
-    else
-      out[i] = neg_has_edge(static_cast<const int64_t*>(csr->indptr), static_cast<const int64_t*>(member), csr->num_rows,
-                            csr->num_cols, static_cast<const int64_t*>(u)[i], static_cast<const int64_t*>(v)[i]);
-  }
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    const Idx *indptr = static_cast<const Idx*>(csr->indptr), *mem = static_cast<const Idx*>(member),
+              *us = static_cast<const Idx*>(u), *vs = static_cast<const Idx*>(v);
+    for (int64_t i = 0; i < n; ++i)
+      out[i] = neg_has_edge(indptr, mem, csr->num_rows, csr->num_cols, static_cast<int64_t>(us[i]), static_cast<int64_t>(vs[i]));
+  });
   return 0;
 }
 

@@ -19,23 +19,13 @@
 #include "../../include/dgl_amd.h"
 
 #include <string>
+#include <type_traits>
 
-#include "common.h"
+#include "host_util.h"
 #include "node2vec_step.h"
 
 namespace dgla {
 namespace {
-
-int nfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-unsigned grid1(int64_t n) { return static_cast<unsigned>((n + 255) / 256 < 1 ? 1 : (n + 255) / 256); }
-
-template <typename T>
-using gptr = const __attribute__((address_space(1))) T*;
 
 // ---- the walk ---------------------------------------------------------------------------------
 // WEIGHTED is a compile-time switch (N2vUniform in csrc/node2vec_step.h says why a run-time test of `cdf` will not do).
@@ -81,27 +71,27 @@ struct SortedLayout {  // offsets into the workspace of dgla_csr_sorted_columns
 };
 
 SortedLayout sorted_layout(const dgla_csr* c) {
-  const size_t w = c->idtype_bits == 32 ? 4 : 8, e = align256(w * static_cast<size_t>(c->nnz));
-  SortedLayout L{};
-  size_t o = 0;
-  L.rows = o, o += e;
-  L.t_indices = o, o += e;
-  L.junk = o, o += e;
-  L.cols = o, o += e;
-  L.t_indptr = o, o += align256(w * static_cast<size_t>(c->num_cols + 1));
-  L.indptr2 = o, o += align256(w * static_cast<size_t>(c->num_rows + 1));
-  L.sort = o;
+  const size_t w = c->idtype_bits == 32 ? 4 : 8, e = w * static_cast<size_t>(c->nnz);
   const size_t s1 = dgla_coo_to_csr_workspace_bytes(c->idtype_bits, c->num_cols, c->nnz),
                s2 = dgla_coo_to_csr_workspace_bytes(c->idtype_bits, c->num_rows, c->nnz);
-  L.bytes = o + align256(s1 > s2 ? s1 : s2);
+  Carver cv;
+  SortedLayout L;
+  L.rows = cv.take(e);
+  L.t_indices = cv.take(e);
+  L.junk = cv.take(e);
+  L.cols = cv.take(e);
+  L.t_indptr = cv.take(w * static_cast<size_t>(c->num_cols + 1));
+  L.indptr2 = cv.take(w * static_cast<size_t>(c->num_rows + 1));
+  L.sort = cv.take(s1 > s2 ? s1 : s2);
+  L.bytes = cv.bytes();
   return L;
 }
 
 int check_sorted(const dgla_csr* csr) {
-  if (!csr || !csr->indptr) return nfail("csr_sorted_columns: csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return nfail("csr_sorted_columns: idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return nfail("csr_sorted_columns: negative size");
-  if (csr->nnz > 0 && !csr->indices) return nfail("csr_sorted_columns: indices are null");
+  if (!csr || !csr->indptr) return fail("csr_sorted_columns: csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail("csr_sorted_columns: idtype must be int32 or int64");
+  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return fail("csr_sorted_columns: negative size");
+  if (csr->nnz > 0 && !csr->indices) return fail("csr_sorted_columns: indices are null");
   return 0;
 }
 
@@ -131,17 +121,17 @@ int run_sorted(const dgla_csr* c, void* member, char* ws, const SortedLayout& L,
 int check_n2v(const char* who, const dgla_csr* csr, const void* member, const void* seeds, int64_t num_seeds,
               int64_t num_steps, double p, double q, const void* traces, N2vAccept* a) {
   const std::string w = std::string(who) + ": ";
-  if (!csr || !csr->indptr) return nfail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return nfail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return nfail(w + "negative size");
+  if (!csr || !csr->indptr) return fail(w + "csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
+  if (csr->num_rows < 0 || csr->nnz < 0) return fail(w + "negative size");
   if (csr->num_rows != csr->num_cols)
-    return nfail(w + "the relation must join one node set to itself (num_rows " + std::to_string(csr->num_rows) +
+    return fail(w + "the relation must join one node set to itself (num_rows " + std::to_string(csr->num_rows) +
                  " != num_cols " + std::to_string(csr->num_cols) + ")");
-  if (csr->nnz > 0 && (!csr->indices || !member)) return nfail(w + "indices / member are null");
-  if (num_steps < 0 || num_seeds < 0) return nfail(w + "negative number of steps / seeds");
-  if (num_seeds > 0 && (!seeds || !traces)) return nfail(w + "seeds / traces are null");
+  if (csr->nnz > 0 && (!csr->indices || !member)) return fail(w + "indices / member are null");
+  if (num_steps < 0 || num_seeds < 0) return fail(w + "negative number of steps / seeds");
+  if (num_seeds > 0 && (!seeds || !traces)) return fail(w + "seeds / traces are null");
   if (!n2v_accept(p, q, a))
-    return nfail(w + "p and q must be finite and > 0 with usable acceptance probabilities (p = " + std::to_string(p) +
+    return fail(w + "p and q must be finite and > 0 with usable acceptance probabilities (p = " + std::to_string(p) +
                  ", q = " + std::to_string(q) + ")");
   return 0;
 }
@@ -181,15 +171,15 @@ size_t dgla_csr_sorted_columns_workspace_bytes(const dgla_csr* csr) {
 int dgla_csr_sorted_columns(const dgla_csr* csr, void* member, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (check_sorted(csr)) return -1;
   if (csr->nnz == 0) return 0;
-  if (csr->num_rows == 0 || csr->num_cols == 0) return nfail("csr_sorted_columns: edges without rows / columns");
-  if (!member) return nfail("csr_sorted_columns: member is null");
+  if (csr->num_rows == 0 || csr->num_cols == 0) return fail("csr_sorted_columns: edges without rows / columns");
+  if (!member) return fail("csr_sorted_columns: member is null");
   const SortedLayout L = sorted_layout(csr);
   if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-    return nfail("csr_sorted_columns: workspace of " + std::to_string(L.bytes) + " bytes required");
+    return fail("csr_sorted_columns: workspace of " + std::to_string(L.bytes) + " bytes required");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, member);
   char* ws = static_cast<char*>(workspace);
-  return csr->idtype_bits == 32 ? run_sorted<int32_t>(csr, member, ws, L, s) : run_sorted<int64_t>(csr, member, ws, L, s);
+  return with_idx(csr->idtype_bits, [&](auto tag) { return run_sorted<decltype(tag)>(csr, member, ws, L, s); });
 }
 
 int dgla_node2vec_walk(const dgla_csr* csr, const double* cdf, const void* member, const void* seeds, int64_t num_seeds,
@@ -200,18 +190,17 @@ int dgla_node2vec_walk(const dgla_csr* csr, const double* cdf, const void* membe
   if (num_seeds == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, traces);
-#define DGLA_N2V(Idx, W)                                                                                           \
-  hipLaunchKernelGGL((node2vec_walk_kernel<Idx, W>), dim3(grid1(num_seeds)), dim3(256), 0, s,                      \
-                     static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),                  \
-                     static_cast<const Idx*>(csr->data), static_cast<const Idx*>(member), cdf, csr->num_rows, a,   \
-                     num_steps, static_cast<const Idx*>(seeds), num_seeds, rng_seed, static_cast<Idx*>(traces),    \
-                     static_cast<Idx*>(eids))
-  if (csr->idtype_bits == 32) {
-    if (cdf) DGLA_N2V(int32_t, true); else DGLA_N2V(int32_t, false);
-  } else {
-    if (cdf) DGLA_N2V(int64_t, true); else DGLA_N2V(int64_t, false);
-  }
-#undef DGLA_N2V
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    auto launch = [&](auto weighted) {
+      hipLaunchKernelGGL((node2vec_walk_kernel<Idx, decltype(weighted)::value>), dim3(grid1(num_seeds)), dim3(256), 0, s,
+                         static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
+                         static_cast<const Idx*>(csr->data), static_cast<const Idx*>(member), cdf, csr->num_rows, a,
+                         num_steps, static_cast<const Idx*>(seeds), num_seeds, rng_seed, static_cast<Idx*>(traces),
+                         static_cast<Idx*>(eids));
+    };
+    if (cdf) launch(std::true_type{}); else launch(std::false_type{});
+  });
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -222,10 +211,9 @@ int dgla_node2vec_walk_host(const dgla_csr* csr, const double* cdf, const void* 
   N2vAccept a;
   if (check_n2v("node2vec_walk_host", csr, member, seeds, num_seeds, num_steps, p, q, traces, &a)) return -1;
   int64_t local[3] = {0, 0, 0};
-  if (csr->idtype_bits == 32)
-    n2v_host<int32_t>(csr, cdf, member, seeds, num_seeds, num_steps, a, rng_seed, traces, eids, stats ? local : nullptr);
-  else
-    n2v_host<int64_t>(csr, cdf, member, seeds, num_seeds, num_steps, a, rng_seed, traces, eids, stats ? local : nullptr);
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    n2v_host<decltype(tag)>(csr, cdf, member, seeds, num_seeds, num_steps, a, rng_seed, traces, eids, stats ? local : nullptr);
+  });
   if (stats) stats[0] = local[0], stats[1] = local[1], stats[2] = local[2];
   return 0;
 }

@@ -29,7 +29,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "host_util.h"
 #include "sort.hip.h"
 
 namespace dgla {
@@ -38,11 +38,6 @@ namespace pinsage {
 constexpr int kWaveMax = 64;        // samples of a segment handled by one wavefront
 constexpr int kBlockMax = 1024;     // ... by one 256-thread workgroup
 constexpr int kMaxSamples = 4096;   // ... by one 512-thread workgroup: the largest accepted S (48 KiB of LDS with int64 ids)
-
-int fail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
 
 template <typename Idx>
 struct Unsigned {
@@ -198,19 +193,14 @@ struct Layout {
 Layout make_layout(int idtype_bits, int64_t num_dst, int64_t kp) {
   const size_t i = idtype_bits / 8, n = static_cast<size_t>(num_dst), slots = n * static_cast<size_t>(kp);
   Layout l;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += msd::align256(bytes);
-    return o;
-  };
-  l.off_src = take(slots * i);
-  l.off_cnt = take(slots * i);
-  l.off_num = take(n * i);
-  l.off_dst = take(n * i);
-  l.off_off = take(n * sizeof(int64_t));
-  l.off_scan = take(msd::scan_temp_bytes(num_dst, sizeof(int64_t)));
-  l.bytes = at;
+  Carver c;
+  l.off_src = c.take(slots * i);
+  l.off_cnt = c.take(slots * i);
+  l.off_num = c.take(n * i);
+  l.off_dst = c.take(n * i);
+  l.off_off = c.take(n * sizeof(int64_t));
+  l.off_scan = c.take(msd::scan_temp_bytes(num_dst, sizeof(int64_t)));
+  l.bytes = c.bytes();
   return l;
 }
 
@@ -301,9 +291,9 @@ int dgla_pinsage_select_padded(int idtype_bits, const void* src, const void* dst
   if (out_dst && !dst) return fail("pinsage_select_padded: out_dst asked for without dst");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_src);
-  return idtype_bits == 32
-             ? launch_select<int32_t>(src, dst, num_dst, num_samples_per_node, kp, out_src, out_cnt, out_num, out_dst, s)
-             : launch_select<int64_t>(src, dst, num_dst, num_samples_per_node, kp, out_src, out_cnt, out_num, out_dst, s);
+  return with_idx(idtype_bits, [&](auto tag) {
+    return launch_select<decltype(tag)>(src, dst, num_dst, num_samples_per_node, kp, out_src, out_cnt, out_num, out_dst, s);
+  });
 }
 
 size_t dgla_pinsage_select_workspace_bytes(int idtype_bits, int64_t num_dst, int64_t num_samples_per_node, int64_t k) {
@@ -327,8 +317,9 @@ int dgla_pinsage_select_count(int idtype_bits, const void* src, const void* dst,
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, workspace);
   char* ws = static_cast<char*>(workspace);
-  return idtype_bits == 32 ? count_compact<int32_t>(src, dst, num_dst, num_samples_per_node, kp, total_out, ws, l, s)
-                           : count_compact<int64_t>(src, dst, num_dst, num_samples_per_node, kp, total_out, ws, l, s);
+  return with_idx(idtype_bits, [&](auto tag) {
+    return count_compact<decltype(tag)>(src, dst, num_dst, num_samples_per_node, kp, total_out, ws, l, s);
+  });
 }
 
 int dgla_pinsage_select_fill(int idtype_bits, int64_t num_dst, int64_t num_samples_per_node, int64_t k, void* res_src,
@@ -344,8 +335,9 @@ int dgla_pinsage_select_fill(int idtype_bits, int64_t num_dst, int64_t num_sampl
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, workspace);
   const char* ws = static_cast<const char*>(workspace);
-  return idtype_bits == 32 ? fill_compact<int32_t>(num_dst, kp, res_src, res_dst, res_cnt, ws, l, s)
-                           : fill_compact<int64_t>(num_dst, kp, res_src, res_dst, res_cnt, ws, l, s);
+  return with_idx(idtype_bits, [&](auto tag) {
+    return fill_compact<decltype(tag)>(num_dst, kp, res_src, res_dst, res_cnt, ws, l, s);
+  });
 }
 
 int dgla_pinsage_select_host(int idtype_bits, const void* src, const void* dst, int64_t num_dst,
@@ -357,13 +349,11 @@ int dgla_pinsage_select_host(int idtype_bits, const void* src, const void* dst, 
   *total_out = 0;
   if (num_dst == 0) return 0;
   if (!src || !dst || !res_src || !res_dst || !res_cnt) return fail("pinsage_select_host: a null array");
-  *total_out = idtype_bits == 32
-                   ? select_host<int32_t>(static_cast<const int32_t*>(src), static_cast<const int32_t*>(dst), num_dst,
-                                          num_samples_per_node, kp, static_cast<int32_t*>(res_src),
-                                          static_cast<int32_t*>(res_dst), static_cast<int32_t*>(res_cnt))
-                   : select_host<int64_t>(static_cast<const int64_t*>(src), static_cast<const int64_t*>(dst), num_dst,
-                                          num_samples_per_node, kp, static_cast<int64_t*>(res_src),
-                                          static_cast<int64_t*>(res_dst), static_cast<int64_t*>(res_cnt));
+  *total_out = with_idx(idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    return select_host<Idx>(static_cast<const Idx*>(src), static_cast<const Idx*>(dst), num_dst, num_samples_per_node, kp,
+                            static_cast<Idx*>(res_src), static_cast<Idx*>(res_dst), static_cast<Idx*>(res_cnt));
+  });
   return 0;
 }
 

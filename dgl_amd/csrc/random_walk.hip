@@ -5,8 +5,8 @@
 // python/dgl/sampling/randomwalks.py:31-226.
 //
 // MI355X-first choices:
-//  * The picks are a pure function of (rng_seed, walk index, step, draw slot) — the counter-based generator of
-//    csrc/sampling.hip — so a run is reproducible from its seed whatever the launch geometry, and the host walker
+//  * The picks are a pure function of (rng_seed, walk index, step, draw slot) — the counter-based generator
+//    csrc/sampling.hip draws from too — so a run is reproducible from its seed whatever the launch geometry, and the host walker
 //    (dgla_random_walk_host) that shares csrc/random_walk_step.h with the kernel reproduces it bit for bit.
 //  * The weighted step is a bisection in a per-relation CDF built once (walk_cdf_kernel): O(log deg) dependent loads per
 //    visit of a 17 000-edge hub row instead of 17 000.
@@ -18,19 +18,11 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "host_util.h"
 #include "random_walk_step.h"
 
 namespace dgla {
 namespace {
-
-int wfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-unsigned grid1(int64_t n) { return static_cast<unsigned>((n + 255) / 256 < 1 ? 1 : (n + 255) / 256); }
 
 // ---- the walk ---------------------------------------------------------------------------------
 template <typename Idx>
@@ -55,11 +47,19 @@ struct WalkTable {
 
 // (one switch for both: a call whose table or metapath does not fit reads both from `workspace`)
 bool walk_in_args(int num_rels, int64_t num_steps) { return num_rels <= kArgRels && num_steps <= kArgSteps; }
-size_t table_ws_bytes(int num_rels) { return align256(sizeof(WalkRel<int64_t>) * static_cast<size_t>(num_rels)); }
-size_t path_ws_bytes(int64_t num_steps) { return align256(sizeof(int32_t) * static_cast<size_t>(num_steps)); }
 
-template <typename T>
-using gptr = const __attribute__((address_space(1))) T*;
+struct WalkLayout {  // offsets into the workspace of dgla_random_walk; bytes == 0: everything travels in the arguments
+  size_t table = 0, path = 0, bytes = 0;
+};
+WalkLayout walk_layout(int num_rels, int64_t num_steps) {
+  WalkLayout L;
+  if (walk_in_args(num_rels, num_steps)) return L;
+  Carver c;
+  L.table = c.take(sizeof(WalkRel<int64_t>) * static_cast<size_t>(num_rels));
+  L.path = c.take(sizeof(int32_t) * static_cast<size_t>(num_steps));
+  L.bytes = c.bytes();
+  return L;
+}
 
 // WS: the table and the metapath come from `workspace` (ws_rel / ws_path) instead of the kernel arguments — a
 // compile-time switch, so that either form reads them with scalar loads (a run-time choice between the two address
@@ -188,29 +188,29 @@ int check_walk(const char* who, const dgla_walk_relation* rels, int num_rels, co
                const void* seeds, int64_t num_seeds, const void* restart_steps, dgla_dtype restart_dtype,
                const void* traces, int* idbits) {
   const std::string w = std::string(who) + ": ";
-  if (!rels || num_rels < 1) return wfail(w + "the relation table is null or empty");
-  if (num_steps < 0 || num_seeds < 0) return wfail(w + "negative number of steps / seeds");
+  if (!rels || num_rels < 1) return fail(w + "the relation table is null or empty");
+  if (num_steps < 0 || num_seeds < 0) return fail(w + "negative number of steps / seeds");
   for (int r = 0; r < num_rels; ++r) {
     const dgla_csr* c = rels[r].csr;
-    if (!c || !c->indptr) return wfail(w + "relation " + std::to_string(r) + " has a null csr");
-    if (c->idtype_bits != 32 && c->idtype_bits != 64) return wfail(w + "idtype must be int32 or int64");
-    if (c->idtype_bits != rels[0].csr->idtype_bits) return wfail(w + "the relations have mixed id widths");
-    if (c->nnz > 0 && !c->indices) return wfail(w + "relation " + std::to_string(r) + " has null indices");
-    if (c->num_rows < 0 || c->nnz < 0) return wfail(w + "relation " + std::to_string(r) + " has a negative size");
+    if (!c || !c->indptr) return fail(w + "relation " + std::to_string(r) + " has a null csr");
+    if (c->idtype_bits != 32 && c->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
+    if (c->idtype_bits != rels[0].csr->idtype_bits) return fail(w + "the relations have mixed id widths");
+    if (c->nnz > 0 && !c->indices) return fail(w + "relation " + std::to_string(r) + " has null indices");
+    if (c->num_rows < 0 || c->nnz < 0) return fail(w + "relation " + std::to_string(r) + " has a negative size");
   }
-  if (num_steps > 0 && !metapath) return wfail(w + "metapath is null");
+  if (num_steps > 0 && !metapath) return fail(w + "metapath is null");
   for (int64_t t = 0; t < num_steps; ++t) {
     if (metapath[t] < 0 || metapath[t] >= num_rels)
-      return wfail(w + "metapath[" + std::to_string(t) + "] = " + std::to_string(metapath[t]) + " is out of range");
+      return fail(w + "metapath[" + std::to_string(t) + "] = " + std::to_string(metapath[t]) + " is out of range");
     if (t > 0 && rels[metapath[t - 1]].csr->num_cols != rels[metapath[t]].csr->num_rows)
-      return wfail(w + "the metapath does not chain at step " + std::to_string(t) + ": relation " +
+      return fail(w + "the metapath does not chain at step " + std::to_string(t) + ": relation " +
                    std::to_string(metapath[t - 1]) + " ends in " + std::to_string(rels[metapath[t - 1]].csr->num_cols) +
                    " nodes, relation " + std::to_string(metapath[t]) + " starts from " +
                    std::to_string(rels[metapath[t]].csr->num_rows));
   }
   if (restart_steps && restart_dtype != DGLA_F32 && restart_dtype != DGLA_F64)
-    return wfail(w + "restart_steps must be float32 or float64");
-  if (num_seeds > 0 && (!seeds || !traces)) return wfail(w + "seeds / traces are null");
+    return fail(w + "restart_steps must be float32 or float64");
+  if (num_seeds > 0 && (!seeds || !traces)) return fail(w + "seeds / traces are null");
   *idbits = rels[0].csr->idtype_bits;
   return 0;
 }
@@ -224,12 +224,12 @@ WalkRel<Idx> make_rel(const dgla_walk_relation& r) {
 template <typename Idx>
 int run_walk(const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps, const void* seeds,
              int64_t num_seeds, double restart_prob, const void* restart_steps, dgla_dtype restart_dtype, uint64_t rng_seed,
-             void* traces, void* eids, char* ws, hipStream_t s) {
+             void* traces, void* eids, char* ws, const WalkLayout& L, hipStream_t s) {
   WalkTable<Idx> tab;
   std::memset(&tab, 0, sizeof(tab));
   const WalkRel<Idx>* ws_rel = nullptr;
   const int32_t* ws_path = nullptr;
-  const bool in_args = walk_in_args(num_rels, num_steps);
+  const bool in_args = L.bytes == 0;
   if (in_args) {
     for (int r = 0; r < num_rels; ++r) tab.rel[r] = make_rel<Idx>(rels[r]);
     for (int64_t t = 0; t < num_steps; ++t) tab.path[t >> 2] |= static_cast<uint32_t>(metapath[t]) << ((t & 3) * 8);
@@ -239,9 +239,9 @@ int run_walk(const dgla_walk_relation* rels, int num_rels, const int32_t* metapa
       const WalkRel<Idx> v = make_rel<Idx>(rels[r]);
       std::memcpy(&words[static_cast<size_t>(r) * 5], &v, sizeof(v));
     }
-    if (upload_words(words.data(), static_cast<int64_t>(words.size()), ws, s)) return -1;
-    ws_rel = reinterpret_cast<const WalkRel<Idx>*>(ws);
-    char* dst = ws + table_ws_bytes(num_rels);
+    if (upload_words(words.data(), static_cast<int64_t>(words.size()), ws + L.table, s)) return -1;
+    ws_rel = reinterpret_cast<const WalkRel<Idx>*>(ws + L.table);
+    char* dst = ws + L.path;
     words.assign(static_cast<size_t>((num_steps + 1) / 2), 0);
     std::memcpy(words.data(), metapath, sizeof(int32_t) * static_cast<size_t>(num_steps));
     if (upload_words(words.data(), static_cast<int64_t>(words.size()), dst, s)) return -1;
@@ -259,9 +259,11 @@ int run_walk(const dgla_walk_relation* rels, int num_rels, const int32_t* metapa
 
 // the kernel's walk on the host, through the same rw_walk
 template <typename Idx>
-void walk_host(const dgla_walk_relation* rels, const int32_t* metapath, int64_t num_steps, const Idx* seeds,
+void walk_host(const dgla_walk_relation* rels, const int32_t* metapath, int64_t num_steps, const void* seeds_v,
                int64_t num_seeds, double restart_prob, const void* restart_steps, dgla_dtype restart_dtype,
-               uint64_t rng_seed, Idx* traces, Idx* eids) {
+               uint64_t rng_seed, void* traces_v, void* eids_v) {
+  const Idx* seeds = static_cast<const Idx*>(seeds_v);
+  Idx *traces = static_cast<Idx*>(traces_v), *eids = static_cast<Idx*>(eids_v);
   auto rel_at = [&](int64_t t) { return make_rel<Idx>(rels[metapath[t]]); };
   auto p_at = [&](int64_t t) {
     if (!restart_steps) return restart_prob;
@@ -288,32 +290,32 @@ size_t dgla_random_walk_cdf_workspace_bytes(const dgla_csr* csr) {
 int dgla_random_walk_cdf(const dgla_csr* csr, const void* prob, dgla_dtype prob_dtype, double* cdf, void* workspace,
                          size_t workspace_bytes, void* hip_stream) {
   (void)workspace;
-  if (!csr || !csr->indptr) return wfail("random_walk_cdf: csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return wfail("random_walk_cdf: idtype must be int32 or int64");
-  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return wfail("random_walk_cdf: prob must be float32 or float64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return wfail("random_walk_cdf: negative size");
-  if (csr->nnz > 0 && (!prob || !cdf)) return wfail("random_walk_cdf: prob / cdf are null");
-  if (workspace_bytes < dgla_random_walk_cdf_workspace_bytes(csr)) return wfail("random_walk_cdf: workspace too small");
+  if (!csr || !csr->indptr) return fail("random_walk_cdf: csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail("random_walk_cdf: idtype must be int32 or int64");
+  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("random_walk_cdf: prob must be float32 or float64");
+  if (csr->num_rows < 0 || csr->nnz < 0) return fail("random_walk_cdf: negative size");
+  if (csr->nnz > 0 && (!prob || !cdf)) return fail("random_walk_cdf: prob / cdf are null");
+  if (workspace_bytes < dgla_random_walk_cdf_workspace_bytes(csr)) return fail("random_walk_cdf: workspace too small");
   if (csr->nnz == 0 || csr->num_rows == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, cdf);
-#define DGLA_CDF(Idx, W)                                                                                   \
-  hipLaunchKernelGGL((walk_cdf_kernel<Idx, W>), dim3(grid1(csr->num_rows)), dim3(256), 0, s,                \
-                     static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->data),              \
-                     static_cast<const W*>(prob), csr->num_rows, cdf)
-  if (csr->idtype_bits == 32) {
-    if (prob_dtype == DGLA_F32) DGLA_CDF(int32_t, float); else DGLA_CDF(int32_t, double);
-  } else {
-    if (prob_dtype == DGLA_F32) DGLA_CDF(int64_t, float); else DGLA_CDF(int64_t, double);
-  }
-#undef DGLA_CDF
+  with_idx(csr->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    auto launch = [&](auto w) {
+      using W = decltype(w);
+      hipLaunchKernelGGL((walk_cdf_kernel<Idx, W>), dim3(grid1(csr->num_rows)), dim3(256), 0, s,
+                         static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->data),
+                         static_cast<const W*>(prob), csr->num_rows, cdf);
+    };
+    if (prob_dtype == DGLA_F32) launch(float{}); else launch(double{});
+  });
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 size_t dgla_random_walk_workspace_bytes(int num_rels, int64_t num_steps) {
   if (num_rels < 0 || num_steps < 0) return 0;
-  return walk_in_args(num_rels, num_steps) ? 0 : table_ws_bytes(num_rels) + path_ws_bytes(num_steps);
+  return walk_layout(num_rels, num_steps).bytes;
 }
 
 int dgla_random_walk(const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps,
@@ -324,17 +326,17 @@ int dgla_random_walk(const dgla_walk_relation* rels, int num_rels, const int32_t
   if (check_walk("random_walk", rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_steps, restart_dtype,
                  traces, &idbits))
     return -1;
-  const size_t need = dgla_random_walk_workspace_bytes(num_rels, num_steps);
-  if (need > 0 && (!workspace || workspace_bytes < need))  // no allocation here
-    return wfail("random_walk: workspace of " + std::to_string(need) + " bytes required");
+  const WalkLayout L = walk_layout(num_rels, num_steps);
+  if (L.bytes > 0 && (!workspace || workspace_bytes < L.bytes))  // no allocation here
+    return fail("random_walk: workspace of " + std::to_string(L.bytes) + " bytes required");
   if (num_seeds == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, traces);
   char* ws = static_cast<char*>(workspace);
-  return idbits == 32 ? run_walk<int32_t>(rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_prob,
-                                          restart_steps, restart_dtype, rng_seed, traces, eids, ws, s)
-                      : run_walk<int64_t>(rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_prob,
-                                          restart_steps, restart_dtype, rng_seed, traces, eids, ws, s);
+  return with_idx(idbits, [&](auto tag) {
+    return run_walk<decltype(tag)>(rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_prob, restart_steps,
+                                   restart_dtype, rng_seed, traces, eids, ws, L, s);
+  });
 }
 
 int dgla_random_walk_host(const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps,
@@ -344,12 +346,10 @@ int dgla_random_walk_host(const dgla_walk_relation* rels, int num_rels, const in
   if (check_walk("random_walk_host", rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_steps,
                  restart_dtype, traces, &idbits))
     return -1;
-  if (idbits == 32)
-    walk_host<int32_t>(rels, metapath, num_steps, static_cast<const int32_t*>(seeds), num_seeds, restart_prob,
-                       restart_steps, restart_dtype, rng_seed, static_cast<int32_t*>(traces), static_cast<int32_t*>(eids));
-  else
-    walk_host<int64_t>(rels, metapath, num_steps, static_cast<const int64_t*>(seeds), num_seeds, restart_prob,
-                       restart_steps, restart_dtype, rng_seed, static_cast<int64_t*>(traces), static_cast<int64_t*>(eids));
+  with_idx(idbits, [&](auto tag) {
+    walk_host<decltype(tag)>(rels, metapath, num_steps, seeds, num_seeds, restart_prob, restart_steps, restart_dtype,
+                             rng_seed, traces, eids);
+  });
   return 0;
 }
 

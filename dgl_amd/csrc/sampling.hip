@@ -25,29 +25,18 @@
 
 #include <cstring>
 
-#include "common.h"
+#include "host_util.h"
+#include "random_walk_step.h"
 #include "sort.hip.h"
 
 namespace dgla {
 namespace {
 
-int sfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
 constexpr int kMaxFanout = 128;
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// uniform integer in [0, n) from the (seed, row, draw) counter: multiply-high reduction
+// uniform integer in [0, n) from the (seed, row, draw) counter of csrc/random_walk_step.h: multiply-high reduction
 __device__ __forceinline__ uint64_t draw(uint64_t seed, uint64_t row, uint32_t k, uint64_t n) {
-  const uint64_t r = mix64(mix64(seed ^ (row * 0xD1B54A32D192ED03ull)) + k);
-  return __umul64hi(r, n);
+  return rw_index(rw_step_key(rw_walk_key(seed, row), k), n);
 }
 
 template <typename Idx>
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(const Idx* __restrict_
 template <typename F>
 __device__ __forceinline__ double clock_key(uint64_t seed, uint64_t row, uint64_t pos, F p) {
   // u in (0, 1]: 53 random bits, never 0, so that -ln(u) is finite
-  const uint64_t r = mix64(mix64(seed ^ (row * 0xD1B54A32D192ED03ull)) + 0x5851F42D4C957F2Dull * (pos + 1));
+  const uint64_t r = rw_mix64(rw_walk_key(seed, row) + 0x5851F42D4C957F2Dull * (pos + 1));
   const double u = (static_cast<double>(r >> 11) + 1.0) * (1.0 / 9007199254740992.0);
   return -log(u) / static_cast<double>(p);
 }
@@ -317,7 +306,7 @@ __global__ __launch_bounds__(256) void weighted_pick_kernel(
   }
   for (int m = 32; m >= 1; m >>= 1) total += __shfl_xor(total, m, 64);
   for (int t = 0; t < picks; ++t) {
-    const uint64_t rr = mix64(mix64(rng_seed ^ (static_cast<uint64_t>(r) * 0xD1B54A32D192ED03ull)) + 0x2545F4914F6CDD1Dull * (t + 1));
+    const uint64_t rr = rw_mix64(rw_walk_key(rng_seed, static_cast<uint64_t>(r)) + 0x2545F4914F6CDD1Dull * (t + 1));
     const double target = (static_cast<double>(rr >> 11) + 0.5) * (1.0 / 9007199254740992.0) * total;
     double run = 0.0;       // weight of the chunks already passed
     int64_t chosen = -1, last_positive = -1;
@@ -435,31 +424,62 @@ __global__ __launch_bounds__(256) void reset_map_kernel(const Idx* __restrict__ 
   if (i < capacity && i < *num_src) node_map[src_nodes[i]] = -1;
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-unsigned grid1(int64_t n) { return static_cast<unsigned>((n + 255) / 256 < 1 ? 1 : (n + 255) / 256); }
-
-template <typename Idx>
-size_t scan_temp_bytes(int64_t n) {
-  return msd::scan_temp_bytes(n, sizeof(Idx));
+// ---- host side ------------------------------------------------------------------------------
+// Workspace of the three samplers (plain, weighted, padded): the per-seed counts, num_seeds + 1 ids that the exclusive
+// scan turns into out_indptr, and the scan's temporary.
+struct SampleLayout {
+  size_t counts, scan, bytes;
+};
+SampleLayout sample_layout(int idtype_bits, int64_t num_seeds) {
+  const size_t ib = idtype_bits == 32 ? 4 : 8;
+  Carver c;
+  SampleLayout L;
+  L.counts = c.take(ib * (num_seeds + 1));
+  L.scan = c.take(msd::scan_temp_bytes(num_seeds + 1, ib));
+  L.bytes = c.bytes();
+  return L;
 }
 
-// scratch of the keys-only sort (sort.hip.h); sized for the widest keys of the id type, so the same buffer serves
-// callers with and without a node count
+// Workspace of to_block: the sorted source ids, the new-node flags and their ranks (nnz + 1 entries each), and one
+// temporary that serves the keys-only sort and then the scan.  The sort's share is sized for the widest keys of the id
+// type, so the same buffer serves callers with and without a node count.
+struct BlockLayout {
+  size_t sorted, flag, rank, temp, bytes;
+};
+BlockLayout block_layout(int idtype_bits, int64_t nnz) {
+  const size_t ib = idtype_bits == 32 ? 4 : 8;
+  const size_t scan_b = msd::scan_temp_bytes(nnz + 1, sizeof(int32_t));
+  const size_t sort_b = nnz > 0 ? msd::make_keys_plan(nnz, 0, ib).bytes : 0;
+  Carver c;
+  BlockLayout L;
+  L.sorted = c.take(ib * (nnz + 1));
+  L.flag = c.take(sizeof(int32_t) * (nnz + 1));
+  L.rank = c.take(sizeof(int32_t) * (nnz + 1));
+  L.temp = c.take(scan_b > sort_b ? scan_b : sort_b);
+  L.bytes = c.bytes();
+  return L;
+}
+
+// the sink rows of the padded form, behind either sampler
 template <typename Idx>
-size_t sort_keys_temp_bytes(int64_t n) { return msd::make_keys_plan(n, 0, sizeof(Idx)).bytes; }
+void launch_pad_tail(const void* seeds, int64_t num_seeds, int fanout, int sinks, const int64_t* num_valid,
+                     void* out_indptr, void* out_src, void* out_eids, hipStream_t s) {
+  const int64_t cap = num_seeds * fanout;
+  hipLaunchKernelGGL(pad_tail_kernel<Idx>, dim3(grid1(cap > sinks ? cap : sinks + 1)), dim3(256), 0, s,
+                     static_cast<Idx*>(out_indptr), num_seeds, cap, sinks, static_cast<const Idx*>(seeds),
+                     num_valid, static_cast<Idx*>(out_src), static_cast<Idx*>(out_eids));
+}
 
 template <typename Idx>
 int run_sample(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fanout, int replace,
-               uint64_t rng_seed, void* out_indptr, void* out_src, void* out_eids, char* ws, hipStream_t s,
-               const int64_t* num_valid = nullptr, const int64_t* rng_counter = nullptr, int sinks = 0) {
+               uint64_t rng_seed, void* out_indptr, void* out_src, void* out_eids, char* ws, const SampleLayout& L,
+               hipStream_t s, const int64_t* num_valid = nullptr, const int64_t* rng_counter = nullptr, int sinks = 0) {
   // counts -> exclusive scan in place of out_indptr (num_seeds + 1 entries)
-  Idx* counts = reinterpret_cast<Idx*>(ws);
-  void* temp = ws + align256(sizeof(Idx) * (num_seeds + 1));
-  size_t temp_bytes = scan_temp_bytes<Idx>(num_seeds + 1);
+  Idx* counts = reinterpret_cast<Idx*>(ws + L.counts);
   hipLaunchKernelGGL(sample_count_kernel<Idx>, dim3(grid1(num_seeds + 1)), dim3(256), 0, s,
                      static_cast<const Idx*>(csc->indptr), static_cast<const Idx*>(seeds), num_seeds,
                      fanout, replace, counts, num_valid);
-  if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, temp, s)) return -1;
+  if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, ws + L.scan, s)) return -1;
   if (out_src) {
 #define DGLA_PICK(FM)                                                                                      \
   hipLaunchKernelGGL((sample_pick_kernel<Idx, FM>), dim3(grid1(num_seeds)), dim3(256), 0, s,                \
@@ -475,12 +495,7 @@ int run_sample(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fa
       DGLA_PICK(kMaxFanout);
 #undef DGLA_PICK
   }
-  if (sinks > 0) {
-    const int64_t cap = num_seeds * fanout;
-    hipLaunchKernelGGL(pad_tail_kernel<Idx>, dim3(grid1(cap > sinks ? cap : sinks + 1)), dim3(256), 0, s,
-                       static_cast<Idx*>(out_indptr), num_seeds, cap, sinks, static_cast<const Idx*>(seeds),
-                       num_valid, static_cast<Idx*>(out_src), static_cast<Idx*>(out_eids));
-  }
+  if (sinks > 0) launch_pad_tail<Idx>(seeds, num_seeds, fanout, sinks, num_valid, out_indptr, out_src, out_eids, s);
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -488,17 +503,15 @@ int run_sample(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fa
 template <typename Idx, typename F>
 int run_sample_weighted(const dgla_csr* csc, const void* prob, const void* seeds, int64_t num_seeds,
                         int fanout, int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
-                        void* out_eids, char* ws, hipStream_t s, const int64_t* num_valid = nullptr,
-                        const int64_t* rng_counter = nullptr, int sinks = 0) {
-  Idx* counts = reinterpret_cast<Idx*>(ws);
-  void* temp = ws + align256(sizeof(Idx) * (num_seeds + 1));
-  size_t temp_bytes = scan_temp_bytes<Idx>(num_seeds + 1);
+                        void* out_eids, char* ws, const SampleLayout& L, hipStream_t s,
+                        const int64_t* num_valid = nullptr, const int64_t* rng_counter = nullptr, int sinks = 0) {
+  Idx* counts = reinterpret_cast<Idx*>(ws + L.counts);
   const unsigned blocks = static_cast<unsigned>((num_seeds + 1 + 3) / 4);  // 4 waves = 4 rows per block
   hipLaunchKernelGGL((weighted_count_kernel<Idx, F>), dim3(blocks), dim3(256), 0, s,
                      static_cast<const Idx*>(csc->indptr), static_cast<const Idx*>(csc->data),
                      static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, replace,
                      counts, num_valid);
-  if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, temp, s)) return -1;
+  if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, ws + L.scan, s)) return -1;
   if (out_src && num_seeds > 0)
     hipLaunchKernelGGL((weighted_pick_kernel<Idx, F>), dim3(static_cast<unsigned>((num_seeds + 3) / 4)),
                        dim3(256), 0, s, static_cast<const Idx*>(csc->indptr),
@@ -506,32 +519,25 @@ int run_sample_weighted(const dgla_csr* csc, const void* prob, const void* seeds
                        static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, replace,
                        rng_seed, static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_src),
                        static_cast<Idx*>(out_eids), rng_counter);
-  if (sinks > 0) {
-    const int64_t cap = num_seeds * fanout;
-    hipLaunchKernelGGL(pad_tail_kernel<Idx>, dim3(grid1(cap > sinks ? cap : sinks + 1)), dim3(256), 0, s,
-                       static_cast<Idx*>(out_indptr), num_seeds, cap, sinks, static_cast<const Idx*>(seeds),
-                       num_valid, static_cast<Idx*>(out_src), static_cast<Idx*>(out_eids));
-  }
+  if (sinks > 0) launch_pad_tail<Idx>(seeds, num_seeds, fanout, sinks, num_valid, out_indptr, out_src, out_eids, s);
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 template <typename Idx>
 int run_to_block(const void* seeds, int64_t num_seeds, const void* src, int64_t nnz, int32_t* node_map,
-                 void* local_src, void* src_nodes, int64_t* num_src_out, char* ws, hipStream_t s,
+                 void* local_src, void* src_nodes, int64_t* num_src_out, char* ws, const BlockLayout& L, hipStream_t s,
                  const int64_t* num_valid = nullptr, int key_bits = 0) {
-  const size_t a_sorted = align256(sizeof(Idx) * (nnz + 1));
-  const size_t a_flag = align256(sizeof(int32_t) * (nnz + 1));
-  Idx* sorted = reinterpret_cast<Idx*>(ws);
-  int32_t* flag = reinterpret_cast<int32_t*>(ws + a_sorted);
-  int32_t* rank = reinterpret_cast<int32_t*>(ws + a_sorted + a_flag);
-  void* temp = ws + a_sorted + 2 * a_flag;
+  Idx* sorted = reinterpret_cast<Idx*>(ws + L.sorted);
+  int32_t* flag = reinterpret_cast<int32_t*>(ws + L.flag);
+  int32_t* rank = reinterpret_cast<int32_t*>(ws + L.rank);
+  char* temp = ws + L.temp;
   hipLaunchKernelGGL(scatter_seed_ids_kernel<Idx>, dim3(grid1(num_seeds)), dim3(256), 0, s,
                      static_cast<const Idx*>(seeds), num_seeds, node_map, static_cast<Idx*>(src_nodes), num_valid);
   if (nnz > 0) {
     // (with a node count the sort looks at the bits the ids use: 3 passes at ogbn-products size; without one, at all
     // 31 / 63 value bits of the id type: 4 / 7 passes — no read-back either way)
-    if (msd::sort_keys<Idx>(static_cast<const Idx*>(src), sorted, nnz, key_bits, static_cast<char*>(temp), s)) return -1;
+    if (msd::sort_keys<Idx>(static_cast<const Idx*>(src), sorted, nnz, key_bits, temp, s)) return -1;
   }
   hipLaunchKernelGGL(flag_new_nodes_kernel<Idx>, dim3(grid1(nnz + 1)), dim3(256), 0, s, sorted, nnz, node_map,
                      flag);
@@ -547,12 +553,31 @@ int run_to_block(const void* seeds, int64_t num_seeds, const void* src, int64_t 
   return 0;
 }
 
-template <typename Idx>
-size_t to_block_ws(int64_t nnz) {
-  const size_t scan_b = msd::scan_temp_bytes(nnz + 1, sizeof(int32_t));
-  const size_t sort_b = nnz > 0 ? sort_keys_temp_bytes<Idx>(nnz) : 0;
-  return align256(sizeof(Idx) * (nnz + 1)) + 2 * align256(sizeof(int32_t) * (nnz + 1)) +
-         align256(scan_b > sort_b ? scan_b : sort_b);
+// the sampler for the call's id width and, when `weighted`, its probability type
+int dispatch_sample(bool weighted, const dgla_csr* csc, const void* prob, dgla_dtype prob_dtype, const void* seeds,
+                    int64_t num_seeds, int fanout, int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
+                    void* out_eids, char* ws, const SampleLayout& L, hipStream_t s, const int64_t* num_valid = nullptr,
+                    const int64_t* rng_counter = nullptr, int sinks = 0) {
+  return with_idx(csc->idtype_bits, [&](auto tag) {
+    using Idx = decltype(tag);
+    auto weighted_as = [&](auto f) {
+      return run_sample_weighted<Idx, decltype(f)>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
+                                                   out_src, out_eids, ws, L, s, num_valid, rng_counter, sinks);
+    };
+    if (!weighted)
+      return run_sample<Idx>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src, out_eids, ws, L, s,
+                             num_valid, rng_counter, sinks);
+    return prob_dtype == DGLA_F32 ? weighted_as(float{}) : weighted_as(double{});
+  });
+}
+
+int dispatch_to_block(int idtype_bits, const void* seeds, int64_t num_seeds, const void* src, int64_t nnz, void* node_map,
+                      void* local_src, void* src_nodes, int64_t* num_src_out, char* ws, const BlockLayout& L,
+                      hipStream_t s, const int64_t* num_valid = nullptr, int key_bits = 0) {
+  return with_idx(idtype_bits, [&](auto tag) {
+    return run_to_block<decltype(tag)>(seeds, num_seeds, src, nnz, static_cast<int32_t*>(node_map), local_src, src_nodes,
+                                       num_src_out, ws, L, s, num_valid, key_bits);
+  });
 }
 
 }  // namespace
@@ -563,76 +588,48 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_sample_neighbors_workspace_bytes(int idtype_bits, int64_t num_seeds) {
-  const size_t ib = idtype_bits / 8;
-  const size_t scan = idtype_bits == 32 ? scan_temp_bytes<int32_t>(num_seeds + 1)
-                                        : scan_temp_bytes<int64_t>(num_seeds + 1);
-  return align256(ib * (num_seeds + 1)) + align256(scan);
+  return sample_layout(idtype_bits, num_seeds).bytes;
 }
 
 int dgla_sample_neighbors(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fanout,
                           int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
                           void* out_eids, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !csc->indptr) return sfail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (num_seeds < 0) return sfail("negative number of seeds");
-  if (fanout > kMaxFanout) return sfail("fanout larger than " + std::to_string(kMaxFanout) + " is not supported");
-  if (fanout == 0 || fanout < -1) return sfail("fanout must be positive, or -1 for all neighbours");
-  if (!out_indptr) return sfail("out_indptr is null");
-  if (num_seeds > 0 && !seeds) return sfail("seeds is null");
+  if (!csc || !csc->indptr) return fail("csc is null");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (num_seeds < 0) return fail("negative number of seeds");
+  if (fanout > kMaxFanout) return fail("fanout larger than " + std::to_string(kMaxFanout) + " is not supported");
+  if (fanout == 0 || fanout < -1) return fail("fanout must be positive, or -1 for all neighbours");
+  if (!out_indptr) return fail("out_indptr is null");
+  if (num_seeds > 0 && !seeds) return fail("seeds is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
-  const size_t need = dgla_sample_neighbors_workspace_bytes(csc->idtype_bits, num_seeds);
-  void* owned = nullptr;
-  if (!workspace || workspace_bytes < need) {
-    DGLA_CHECK_HIP(hipMallocAsync(&owned, need, s));
-    workspace = owned;
-  }
-  const int rc = csc->idtype_bits == 32
-                     ? run_sample<int32_t>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                           out_src, out_eids, static_cast<char*>(workspace), s)
-                     : run_sample<int64_t>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                           out_src, out_eids, static_cast<char*>(workspace), s);
-  if (owned) (void)hipFreeAsync(owned, s);
-  return rc;
+  const SampleLayout L = sample_layout(csc->idtype_bits, num_seeds);
+  Scratch ws(s);
+  if (ws.take(workspace, workspace_bytes, L.bytes)) return -1;
+  return dispatch_sample(false, csc, nullptr, DGLA_F32, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src,
+                         out_eids, ws.p, L, s);
 }
 
 int dgla_sample_neighbors_weighted(const dgla_csr* csc, const void* prob, dgla_dtype prob_dtype,
                                    const void* seeds, int64_t num_seeds, int fanout, int replace,
                                    uint64_t rng_seed, void* out_indptr, void* out_src, void* out_eids,
                                    void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !csc->indptr) return sfail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return sfail("probabilities must be float32 or float64");
-  if (!prob && csc->nnz > 0) return sfail("prob is null");
-  if (num_seeds < 0) return sfail("negative number of seeds");
+  if (!csc || !csc->indptr) return fail("csc is null");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("probabilities must be float32 or float64");
+  if (!prob && csc->nnz > 0) return fail("prob is null");
+  if (num_seeds < 0) return fail("negative number of seeds");
   if (fanout < 1 || fanout > kMaxFanout)
-    return sfail("weighted sampling needs 1 <= fanout <= " + std::to_string(kMaxFanout));
-  if (!out_indptr) return sfail("out_indptr is null");
-  if (num_seeds > 0 && !seeds) return sfail("seeds is null");
+    return fail("weighted sampling needs 1 <= fanout <= " + std::to_string(kMaxFanout));
+  if (!out_indptr) return fail("out_indptr is null");
+  if (num_seeds > 0 && !seeds) return fail("seeds is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
-  const size_t need = dgla_sample_neighbors_workspace_bytes(csc->idtype_bits, num_seeds);
-  void* owned = nullptr;
-  if (!workspace || workspace_bytes < need) {
-    DGLA_CHECK_HIP(hipMallocAsync(&owned, need, s));
-    workspace = owned;
-  }
-  char* ws = static_cast<char*>(workspace);
-  int rc;
-  if (csc->idtype_bits == 32)
-    rc = prob_dtype == DGLA_F32
-             ? run_sample_weighted<int32_t, float>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed,
-                                                   out_indptr, out_src, out_eids, ws, s)
-             : run_sample_weighted<int32_t, double>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed,
-                                                    out_indptr, out_src, out_eids, ws, s);
-  else
-    rc = prob_dtype == DGLA_F32
-             ? run_sample_weighted<int64_t, float>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed,
-                                                   out_indptr, out_src, out_eids, ws, s)
-             : run_sample_weighted<int64_t, double>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed,
-                                                    out_indptr, out_src, out_eids, ws, s);
-  if (owned) (void)hipFreeAsync(owned, s);
-  return rc;
+  const SampleLayout L = sample_layout(csc->idtype_bits, num_seeds);
+  Scratch ws(s);
+  if (ws.take(workspace, workspace_bytes, L.bytes)) return -1;
+  return dispatch_sample(true, csc, prob, prob_dtype, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src,
+                         out_eids, ws.p, L, s);
 }
 
 int dgla_sample_neighbors_padded(const dgla_csr* csc, const void* prob, dgla_dtype prob_dtype, const void* seeds,
@@ -640,39 +637,24 @@ int dgla_sample_neighbors_padded(const dgla_csr* csc, const void* prob, dgla_dty
                                  uint64_t rng_seed, const int64_t* rng_counter, int sink_rows, void* out_indptr,
                                  void* out_src, void* out_eids, void* workspace, size_t workspace_bytes,
                                  void* hip_stream) {
-  if (sink_rows < 1 || sink_rows > 4096) return sfail("sink_rows must be in [1, 4096]");
-  if (prob && prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return sfail("probabilities must be float32 or float64");
-  if (!csc || !csc->indptr) return sfail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (num_seeds < 1) return sfail("the padded form needs at least one seed slot");
+  if (sink_rows < 1 || sink_rows > 4096) return fail("sink_rows must be in [1, 4096]");
+  if (prob && prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("probabilities must be float32 or float64");
+  if (!csc || !csc->indptr) return fail("csc is null");
+  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (num_seeds < 1) return fail("the padded form needs at least one seed slot");
   if (fanout < 1 || fanout > kMaxFanout)
-    return sfail("the padded form needs 1 <= fanout <= " + std::to_string(kMaxFanout));
-  if (!out_indptr || !out_src || !out_eids || !seeds) return sfail("seeds / output arrays are null");
+    return fail("the padded form needs 1 <= fanout <= " + std::to_string(kMaxFanout));
+  if (!out_indptr || !out_src || !out_eids || !seeds) return fail("seeds / output arrays are null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
-  const size_t need = dgla_sample_neighbors_workspace_bytes(csc->idtype_bits, num_seeds);
-  if (!workspace || workspace_bytes < need)  // no allocation here: the call must be capturable
-    return sfail("sample_neighbors_padded: workspace of " + std::to_string(need) + " bytes required");
-  char* ws = static_cast<char*>(workspace);
-  if (prob) {
-    if (csc->idtype_bits == 32)
-      return prob_dtype == DGLA_F32
-                 ? run_sample_weighted<int32_t, float>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                                       out_src, out_eids, ws, s, num_valid, rng_counter, sink_rows)
-                 : run_sample_weighted<int32_t, double>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                                        out_src, out_eids, ws, s, num_valid, rng_counter, sink_rows);
-    return prob_dtype == DGLA_F32
-               ? run_sample_weighted<int64_t, float>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                                     out_src, out_eids, ws, s, num_valid, rng_counter, sink_rows)
-               : run_sample_weighted<int64_t, double>(csc, prob, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
-                                                      out_src, out_eids, ws, s, num_valid, rng_counter, sink_rows);
-  }
-  return csc->idtype_bits == 32
-             ? run_sample<int32_t>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src,
-                                   out_eids, ws, s, num_valid, rng_counter, sink_rows)
-             : run_sample<int64_t>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src,
-                                   out_eids, ws, s, num_valid, rng_counter, sink_rows);
+  const SampleLayout L = sample_layout(csc->idtype_bits, num_seeds);
+  if (!workspace || workspace_bytes < L.bytes)  // no allocation here: the call must be capturable
+    return fail("sample_neighbors_padded: workspace of " + std::to_string(L.bytes) + " bytes required");
+  return dispatch_sample(prob != nullptr, csc, prob, prob_dtype, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
+                         out_src, out_eids, static_cast<char*>(workspace), L, s, num_valid, rng_counter, sink_rows);
 }
+
+size_t dgla_to_block_workspace_bytes(int idtype_bits, int64_t nnz) { return block_layout(idtype_bits, nnz).bytes; }
 
 int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, const int64_t* num_valid,
                          const void* src, int64_t nnz, int64_t num_nodes, void* node_map, void* local_src,
@@ -683,50 +665,36 @@ int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, 
     key_bits = 1;
     while ((int64_t(1) << key_bits) < num_nodes) ++key_bits;
   }
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (num_seeds < 1 || nnz < 0) return sfail("bad size");
-  if (!node_map || !src_nodes || !num_src_out || !seeds) return sfail("node_map / src_nodes / num_src_out / seeds is null");
-  if (nnz > 0 && (!src || !local_src)) return sfail("input arrays are null");
-  if (num_seeds + nnz > 0x7fffffffLL) return sfail("a block with more than 2^31-1 source nodes is not supported");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (num_seeds < 1 || nnz < 0) return fail("bad size");
+  if (!node_map || !src_nodes || !num_src_out || !seeds) return fail("node_map / src_nodes / num_src_out / seeds is null");
+  if (nnz > 0 && (!src || !local_src)) return fail("input arrays are null");
+  if (num_seeds + nnz > 0x7fffffffLL) return fail("a block with more than 2^31-1 source nodes is not supported");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, node_map);
-  const size_t need = dgla_to_block_workspace_bytes(idtype_bits, nnz);
-  if (!workspace || workspace_bytes < need)
-    return sfail("to_block_padded: workspace of " + std::to_string(need) + " bytes required");
-  return idtype_bits == 32
-             ? run_to_block<int32_t>(seeds, num_seeds, src, nnz, static_cast<int32_t*>(node_map), local_src,
-                                     src_nodes, num_src_out, static_cast<char*>(workspace), s, num_valid, key_bits)
-             : run_to_block<int64_t>(seeds, num_seeds, src, nnz, static_cast<int32_t*>(node_map), local_src,
-                                     src_nodes, num_src_out, static_cast<char*>(workspace), s, num_valid, key_bits);
-}
-
-size_t dgla_to_block_workspace_bytes(int idtype_bits, int64_t nnz) {
-  return idtype_bits == 32 ? to_block_ws<int32_t>(nnz) : to_block_ws<int64_t>(nnz);
+  const BlockLayout L = block_layout(idtype_bits, nnz);
+  if (!workspace || workspace_bytes < L.bytes)
+    return fail("to_block_padded: workspace of " + std::to_string(L.bytes) + " bytes required");
+  return dispatch_to_block(idtype_bits, seeds, num_seeds, src, nnz, node_map, local_src, src_nodes, num_src_out,
+                           static_cast<char*>(workspace), L, s, num_valid, key_bits);
 }
 
 int dgla_to_block(int idtype_bits, const void* seeds, int64_t num_seeds, const void* src, int64_t nnz,
                   void* node_map, void* local_src, void* src_nodes, int64_t* num_src_out,
                   void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (num_seeds < 0 || nnz < 0) return sfail("negative size");
-  if (!node_map || !src_nodes || !num_src_out) return sfail("node_map / src_nodes / num_src_out is null");
-  if ((num_seeds > 0 && !seeds) || (nnz > 0 && (!src || !local_src))) return sfail("input arrays are null");
-  if (num_seeds + nnz > 0x7fffffffLL) return sfail("a block with more than 2^31-1 source nodes is not supported");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (num_seeds < 0 || nnz < 0) return fail("negative size");
+  if (!node_map || !src_nodes || !num_src_out) return fail("node_map / src_nodes / num_src_out is null");
+  if ((num_seeds > 0 && !seeds) || (nnz > 0 && (!src || !local_src))) return fail("input arrays are null");
+  if (num_seeds + nnz > 0x7fffffffLL) return fail("a block with more than 2^31-1 source nodes is not supported");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, node_map);
-  const size_t need = dgla_to_block_workspace_bytes(idtype_bits, nnz);
-  void* owned = nullptr;
-  if (!workspace || workspace_bytes < need) {
-    DGLA_CHECK_HIP(hipMallocAsync(&owned, need, s));
-    workspace = owned;
-  }
-  const int rc = idtype_bits == 32
-                     ? run_to_block<int32_t>(seeds, num_seeds, src, nnz, static_cast<int32_t*>(node_map), local_src,
-                                             src_nodes, num_src_out, static_cast<char*>(workspace), s)
-                     : run_to_block<int64_t>(seeds, num_seeds, src, nnz, static_cast<int32_t*>(node_map), local_src,
-                                             src_nodes, num_src_out, static_cast<char*>(workspace), s);
-  if (owned) (void)hipFreeAsync(owned, s);
-  return rc;
+  const BlockLayout L = block_layout(idtype_bits, nnz);
+  Scratch ws(s);
+  if (ws.take(workspace, workspace_bytes, L.bytes)) return -1;
+  return dispatch_to_block(idtype_bits, seeds, num_seeds, src, nnz, node_map, local_src, src_nodes, num_src_out, ws.p, L,
+                           s);
 }
 
 }  // extern "C"
+

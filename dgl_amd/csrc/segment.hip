@@ -37,11 +37,6 @@ size_t spmm_csr_workspace_bf16(const SpmmLaunch&);
 
 namespace {
 
-int sfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
 int64_t row_len(const dgla_tensor* t) {
   int64_t n = 1;
   for (int i = 1; i < t->ndim; ++i) n *= t->shape[i];
@@ -271,16 +266,16 @@ int build_segment_launch(const char* reduce, int idbits, dgla_dtype dtype,
   if (reduce && !strcmp(reduce, "max")) red = kMax;
   if (reduce && !strcmp(reduce, "min")) red = kMin;
   if (red < 0)
-    return sfail(std::string("Unsupported reduce function ") + (reduce ? reduce : "(null)"));
-  if (idbits != 32 && idbits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
+    return fail(std::string("Unsupported reduce function ") + (reduce ? reduce : "(null)"));
+  if (idbits != 32 && idbits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
   if (!feat || !out || feat->ndim < 1 || out->ndim < 1 || !feat->shape || !out->shape)
-    return sfail("feat / out is null");
-  if (feat->ndim != out->ndim) return sfail("feat and out must have the same number of dimensions");
-  if (out->shape[0] != num_segments) return sfail("out has a different number of rows than segments");
-  if (row_len(feat) != row_len(out)) return sfail("feat and out have different feature shapes");
-  if (num_segments > 0 && !offsets) return sfail("offsets is null");
-  if (row_len(out) > 0x7fffffffLL / 4) return sfail("feature length too large");
+    return fail("feat / out is null");
+  if (feat->ndim != out->ndim) return fail("feat and out must have the same number of dimensions");
+  if (out->shape[0] != num_segments) return fail("out has a different number of rows than segments");
+  if (row_len(feat) != row_len(out)) return fail("feat and out have different feature shapes");
+  if (num_segments > 0 && !offsets) return fail("offsets is null");
+  if (row_len(out) > 0x7fffffffLL / 4) return fail("feature length too large");
   L->csr.num_rows = num_segments;
   L->csr.num_cols = 0;
   L->csr.nnz = feat->shape[0];
@@ -632,7 +627,7 @@ int dgla_segment_reduce(const char* reduce, int idtype_bits, dgla_dtype dtype,
   SpmmLaunch L{};
   if (build_segment_launch(reduce, idtype_bits, dtype, feat, offsets, num_segments, out, &L))
     return -1;
-  if (L.red != kSum && !arg) return sfail("arg is required for max/min");
+  if (L.red != kSum && !arg) return fail("arg is required for max/min");
   if (num_segments == 0 || L.out_len == 0) return 0;
   L.arg_u = nullptr;
   L.arg_e = arg;
@@ -675,71 +670,71 @@ int dgla_segment_reduce(const char* reduce, int idtype_bits, dgla_dtype dtype,
   }
   if (owned) {
     const hipError_t e = hipFreeAsync(owned, L.stream);
-    if (e != hipSuccess && rc == 0) return sfail(std::string("hipFreeAsync: ") + hipGetErrorString(e));
+    if (e != hipSuccess && rc == 0) return fail(std::string("hipFreeAsync: ") + hipGetErrorString(e));
   }
   return rc;
 }
 
 int dgla_scatter_add(int idtype_bits, dgla_dtype dtype, const dgla_tensor* feat, const void* idx,
                      const dgla_tensor* out, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
   if (!feat || !out || feat->ndim < 1 || out->ndim < 1 || !feat->shape || !out->shape)
-    return sfail("feat / out is null");
-  if (row_len(feat) != row_len(out)) return sfail("feat and out have different feature shapes");
+    return fail("feat / out is null");
+  if (row_len(feat) != row_len(out)) return fail("feat and out have different feature shapes");
   const int64_t n = feat->shape[0], dim = row_len(out);
   if (n == 0 || dim == 0) return 0;
-  if (!feat->data || !out->data || !idx) return sfail("feat / idx / out data is null");
-  if (dim > 0x7fffffffLL / 4) return sfail("feature length too large");
+  if (!feat->data || !out->data || !idx) return fail("feat / idx / out data is null");
+  if (dim > 0x7fffffffLL / 4) return fail("feature length too large");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   const int64_t out_rows = out->shape[0];
   if (n * dim >= kScatterSortMinElems && out_rows > 0) return scatter_add_sorted(idtype_bits, dtype, feat, idx, out, s);
   DGLA_IDX_DTYPE_SWITCH(idtype_bits, dtype, run_scatter_add, feat->data, idx, out->data, n, dim, s);
-  return sfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 int dgla_update_grad_minmax(int idtype_bits, dgla_dtype dtype, const dgla_tensor* feat,
                             const void* idx, const void* idx_type, int64_t type,
                             const dgla_tensor* out, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
   if (!feat || !out || feat->ndim < 1 || out->ndim < 1 || !feat->shape || !out->shape)
-    return sfail("feat / out is null");
-  if (row_len(feat) != row_len(out)) return sfail("feat and out have different feature shapes");
+    return fail("feat / out is null");
+  if (row_len(feat) != row_len(out)) return fail("feat and out have different feature shapes");
   const int64_t n = feat->shape[0], dim = row_len(out);
   if (n == 0 || dim == 0 || out->shape[0] == 0) return 0;
-  if (!feat->data || !out->data || !idx || !idx_type) return sfail("feat / idx / idx_type / out data is null");
+  if (!feat->data || !out->data || !idx || !idx_type) return fail("feat / idx / idx_type / out data is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   DGLA_IDX_DTYPE_SWITCH(idtype_bits, dtype, run_update_grad_minmax, feat->data, idx, idx_type, out->data,
                         n, dim, type, out->shape[0], s);
-  return sfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 int dgla_spmm_cmp_backward(int idtype_bits, dgla_dtype dtype, const dgla_tensor* dz, const void* arg,
                            const dgla_tensor* other, const void* arg_other, int64_t other_group,
                            const dgla_tensor* out, int atomic, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
-  if (!dz || !out || dz->ndim < 1 || out->ndim < 1 || !dz->shape || !out->shape) return sfail("dz / out is null");
-  if (row_len(dz) != row_len(out)) return sfail("dz and out have different feature shapes");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
+  if (!dz || !out || dz->ndim < 1 || out->ndim < 1 || !dz->shape || !out->shape) return fail("dz / out is null");
+  if (row_len(dz) != row_len(out)) return fail("dz and out have different feature shapes");
   const int64_t n = dz->shape[0], dim = row_len(out);
   if (n == 0 || dim == 0 || out->shape[0] == 0) return 0;
-  if (!dz->data || !out->data || !arg) return sfail("dz / arg / out data is null");
+  if (!dz->data || !out->data || !arg) return fail("dz / arg / out data is null");
   int64_t other_len = 1;
   if (other && other->data) {
-    if (!arg_other) return sfail("arg_other is required with `other`");
-    if (other->ndim < 1 || !other->shape) return sfail("other has no shape");
+    if (!arg_other) return fail("arg_other is required with `other`");
+    if (other->ndim < 1 || !other->shape) return fail("other has no shape");
     other_len = row_len(other);
-    if (other_group < 1 || other_group > dim || other_len < 1) return sfail("other_group out of range");
+    if (other_group < 1 || other_group > dim || other_len < 1) return fail("other_group out of range");
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   const void* od = (other && other->data) ? other->data : nullptr;
   DGLA_IDX_DTYPE_SWITCH(idtype_bits, dtype, run_spmm_cmp_backward, dz->data, arg, od, arg_other, out->data, n, dim,
                         other_len, other_group < 1 ? 1 : other_group, out->shape[0], atomic != 0, s);
-  return sfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 int64_t dgla_spmm_cmp_mask_words(dgla_dtype dtype, int64_t feat_len) {
@@ -758,38 +753,38 @@ size_t dgla_spmm_cmp_mask_bytes(dgla_dtype dtype, int64_t num_rows, int64_t nnz,
 
 int dgla_spmm_cmp_mask(const dgla_csr* csr, dgla_dtype dtype, const void* arg, int by_edge, const dgla_tensor* dz,
                        void* mask, const dgla_tensor* dx, void* hip_stream) {
-  if (!csr) return sfail("csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
-  if (!dz || !dx || dz->ndim < 1 || dx->ndim < 1 || !dz->shape || !dx->shape) return sfail("dz / dx is null");
-  if (row_len(dz) != row_len(dx)) return sfail("dz and dx have different feature shapes");
-  if (dz->shape[0] != csr->num_rows) return sfail("dz must have one row per row of the CSR");
+  if (!csr) return fail("csr is null");
+  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
+  if (!dz || !dx || dz->ndim < 1 || dx->ndim < 1 || !dz->shape || !dx->shape) return fail("dz / dx is null");
+  if (row_len(dz) != row_len(dx)) return fail("dz and dx have different feature shapes");
+  if (dz->shape[0] != csr->num_rows) return fail("dz must have one row per row of the CSR");
   const int64_t F = row_len(dz);
   if (csr->num_rows == 0 || F == 0 || dx->shape[0] == 0) return 0;
-  if (F > (1 << 20)) return sfail("feature rows too long");
+  if (F > (1 << 20)) return fail("feature rows too long");
   if (!csr->indptr || (csr->nnz && !csr->indices) || !arg || !dz->data || !dx->data || !mask)
-    return sfail("csr / arg / dz / dx / mask data is null");
+    return fail("csr / arg / dz / dx / mask data is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, dx->data);
   DGLA_IDX_DTYPE_SWITCH(csr->idtype_bits, dtype, run_spmm_cmp_mask, csr->indptr, csr->indices, csr->data, arg, by_edge,
                         csr->num_rows, csr->nnz, F, mask, dz->data, dx->data, dx->shape[0], s);
-  return sfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 int dgla_backward_segment_cmp(int idtype_bits, dgla_dtype dtype, const dgla_tensor* feat,
                               const void* arg, const dgla_tensor* out, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return sfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return sfail("unsupported feature dtype");
+  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
   if (!feat || !out || feat->ndim < 1 || out->ndim < 1 || !feat->shape || !out->shape)
-    return sfail("feat / out is null");
-  if (row_len(feat) != row_len(out)) return sfail("feat and out have different feature shapes");
+    return fail("feat / out is null");
+  if (row_len(feat) != row_len(out)) return fail("feat and out have different feature shapes");
   const int64_t n = feat->shape[0], dim = row_len(out);
   if (n == 0 || dim == 0) return 0;
-  if (!feat->data || !out->data || !arg) return sfail("feat / arg / out data is null");
+  if (!feat->data || !out->data || !arg) return fail("feat / arg / out data is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out->data);
   DGLA_IDX_DTYPE_SWITCH(idtype_bits, dtype, run_bwd_segment_cmp, feat->data, arg, out->data, n, dim, s);
-  return sfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 }  // extern "C"

@@ -36,11 +36,6 @@
 namespace dgla {
 namespace {
 
-int mfail(const std::string& m) {
-  last_error() = m;
-  return -1;
-}
-
 constexpr int BM = 128;
 constexpr int kFwdSlab = 128;   // forward: bytes of K per tile row and slab (pitch + 16: conflict-free ds_read_b128)
 constexpr int kBwdSlab = 64;    // weight gradient: 64-byte slabs
@@ -2095,7 +2090,6 @@ __global__ __launch_bounds__(256) void gather_mm_kernel(const DT* __restrict__ a
 }
 
 // ---- host side ------------------------------------------------------------------------------
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 constexpr size_t kWsProgWords = 16 * 1024;  // >= row chunks (<= CUs) x 8 waves x 4 words
 constexpr int kWsQueueSplit = 8;            // dynamic chunks per group (chunk queue of the weights-stationary kernels)
 constexpr size_t kWsQueueWords = 64;         // the queue's ticket, on a line of its own
@@ -2412,7 +2406,7 @@ int run_segment_mm(const void* a, const void* b, void* c, int64_t M, int64_t K, 
     const bool wide = N > 128;  // (fp32 too: 128-wide tiles measured 14.6 vs 11.6 ms at 10 M x 256 x 256)
     p.n_tiles = wide ? (N + 255) / 256 : 1;
     const int64_t blocks = max_tiles * p.n_tiles;
-    if (blocks > 0x7fffffffLL) return mfail("segment_mm: too many tiles");
+    if (blocks > 0x7fffffffLL) return fail("segment_mm: too many tiles");
     const dim3 grid(static_cast<unsigned>(blocks)), block(256);
     const bool vec = p.vec_a && p.vec_b && p.vec_c;
     {
@@ -3252,7 +3246,7 @@ int run_segment_mm_bwd_b(const void* a, const void* dc, void* db, int64_t M, int
     p.nan_flag = reinterpret_cast<uint32_t*>(const_cast<int64_t*>(plan) + 3 * num_rel + 2);
     const int64_t max_slabs = ((M + p.slab_rows - 1) / p.slab_rows + num_rel + 7) / 8 * 8;
     const int64_t blocks = max_slabs * p.tiles_i * p.tiles_j;
-    if (blocks >= (int64_t(1) << 24)) return mfail("segment_mm backward: too many tiles (" +
+    if (blocks >= (int64_t(1) << 24)) return fail("segment_mm backward: too many tiles (" +
                                                    std::to_string(blocks) + "); split the call");
     bool direct = false;
     if constexpr (sizeof(DT) == 2)
@@ -3331,7 +3325,7 @@ template <typename Idx, typename DT>
 int run_gather_mm(const void* a, const void* b, void* c, const void* ia, const void* ib,
                   const void* ic, int64_t rows, int64_t K, int64_t N, hipStream_t s) {
   const int64_t blocks = (rows * 64 + 255) / 256;
-  if (blocks > 0x7fffffffLL) return mfail("gather_mm: too many rows");
+  if (blocks > 0x7fffffffLL) return fail("gather_mm: too many rows");
   hipLaunchKernelGGL((gather_mm_kernel<Idx, DT>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s,
                      static_cast<const DT*>(a), static_cast<const DT*>(b), static_cast<DT*>(c),
                      static_cast<const Idx*>(ia), static_cast<const Idx*>(ib),
@@ -3341,10 +3335,10 @@ int run_gather_mm(const void* a, const void* b, void* c, const void* ia, const v
 }
 
 int check_mm_common(int idbits, dgla_dtype dtype, int64_t M, int64_t K, int64_t N, int64_t R) {
-  if (idbits != 32 && idbits != 64) return mfail("idtype must be int32 or int64");
-  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return mfail("unsupported feature dtype");
-  if (M < 0 || K < 0 || N < 0 || R < 0) return mfail("negative dimension");
-  if (K > 0x3fffffff || N > 0x3fffffff) return mfail("feature dimension too large");
+  if (idbits != 32 && idbits != 64) return fail("idtype must be int32 or int64");
+  if (dtype < DGLA_F32 || dtype > DGLA_BF16) return fail("unsupported feature dtype");
+  if (M < 0 || K < 0 || N < 0 || R < 0) return fail("negative dimension");
+  if (K > 0x3fffffff || N > 0x3fffffff) return fail("feature dimension too large");
   return 0;
 }
 
@@ -3366,7 +3360,7 @@ int dgla_segment_mm_indexed(int idtype_bits, dgla_dtype dtype, const void* a, co
                             void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (check_mm_common(idtype_bits, dtype, num_rows, k, n, num_rel)) return -1;
   if (num_rows == 0 || n == 0 || num_rel == 0) return 0;
-  if (!a || !b || !c || !seglen) return mfail("segment_mm: null operand");
+  if (!a || !b || !c || !seglen) return fail("segment_mm: null operand");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, c);
   const size_t elem = dtype == DGLA_F64 ? 8 : (dtype == DGLA_F32 ? 4 : 2);
@@ -3408,7 +3402,7 @@ int dgla_segment_mm_backward_b_indexed(int idtype_bits, dgla_dtype dtype, const 
                                        void* hip_stream) {
   if (check_mm_common(idtype_bits, dtype, num_rows, d1, d2, num_rel)) return -1;
   if (num_rel == 0 || d1 == 0 || d2 == 0) return 0;
-  if (!db || !seglen || (num_rows > 0 && (!a || !dc))) return mfail("segment_mm backward: null operand");
+  if (!db || !seglen || (num_rows > 0 && (!a || !dc))) return fail("segment_mm backward: null operand");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, db);
   const size_t elem = dtype == DGLA_F64 ? 8 : (dtype == DGLA_F32 ? 4 : 2);
@@ -3454,7 +3448,7 @@ int dgla_gather_mm(int idtype_bits, dgla_dtype dtype, const void* a, const void*
                    int64_t k, int64_t n, void* hip_stream) {
   if (check_mm_common(idtype_bits, dtype, num_rows, k, n, 0)) return -1;
   if (num_rows == 0 || n == 0) return 0;
-  if (!a || !b || !c) return mfail("gather_mm: null operand");
+  if (!a || !b || !c) return fail("gather_mm: null operand");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, c);
 #define DGLA_GMM(IDX)                                                                             \
@@ -3470,7 +3464,7 @@ int dgla_gather_mm(int idtype_bits, dgla_dtype dtype, const void* a, const void*
     DGLA_GMM(int64_t)
   }
 #undef DGLA_GMM
-  return mfail("unsupported feature dtype");
+  return fail("unsupported feature dtype");
 }
 
 }  // extern "C"

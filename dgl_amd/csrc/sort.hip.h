@@ -41,8 +41,6 @@ constexpr int kMaxNB = 1 << kMaxDigit;           // bins per level
 constexpr int kKeysDigit = 9;                    // bits per pass of the keys-only sort (small inputs: fused one-block scan)
 constexpr int kMaxLevels = 8;
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 inline int bits_for(int64_t n) {  // bits needed for values in [0, n)
   int b = 1;
   while ((int64_t(1) << b) < n) ++b;

@@ -29,6 +29,28 @@ NID = "_ID"   # dgl.NID / dgl.EID
 EID = "_ID"
 
 
+def _call_seed(seed):
+    """The seed of one call: ``seed=None`` draws it from torch's global CPU generator, an integer is taken as given."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+
+def _node_ids(nodes, device, idtype):
+    """``nodes`` (ids, a list or one id) as a contiguous 1-D tensor of the graph's id type on its device."""
+    return torch.as_tensor(nodes).reshape(-1).to(device=device, dtype=idtype).contiguous()
+
+
+def _relation_slot(rel, name, keyed_tensors, build):
+    """What ``build()`` returns, kept in ONE slot ``name`` on relation ``rel``: keyed by the address, ``_version``, shape,
+    dtype and device of ``keyed_tensors`` and checked at every use (as ``static_features`` checks its promise), so an
+    in-place write to one of them rebuilds it."""
+    key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device) for t in keyed_tensors)
+    slot = getattr(rel, name, None)
+    if slot is None or slot[0] != key:
+        slot = (key, build())
+        setattr(rel, name, slot)
+    return slot[1]
+
+
 def _csc_of(g):
     rel = g._graph.relations[0]
     indptr, indices, eids = rel.csc()
@@ -104,7 +126,7 @@ def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed):
             rels.append(Relation(rel.num_src, rel.num_dst, empty, empty, idtype=idt, device=dev))
             picked.append(empty)
             continue
-        seeds = torch.as_tensor(seeds).reshape(-1).to(device=dev, dtype=idt).contiguous()
+        seeds = _node_ids(seeds, dev, idt)
         fmt = rel.csc() if edge_dir == "in" else rel.csr()
         csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_src if edge_dir == "in" else rel.num_dst)
         p = _prob_of(prob, g._edge_frames[etid], rel, "sample_neighbors")
@@ -140,8 +162,7 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
     ``seed=None`` (default) draws a fresh stream for every call from torch's global CPU
     generator, like the reference's advancing global RNG (so ``torch.manual_seed`` makes a run
     reproducible); an explicit integer pins the picks of this call."""
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = _call_seed(seed)
     if edge_dir not in ("in", "out"):
         raise ValueError("edge_dir must be 'in' or 'out'")
     if len(g.canonical_etypes) != 1 or isinstance(nodes, dict) or isinstance(fanout, dict):
@@ -154,7 +175,7 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
         csr = _capi.make_csr(keep[0], keep[1], keep[2], rel.num_dst)
     if isinstance(prob, str):  # name of an edge feature, as in the reference
         prob = g.edata[prob]
-    nodes = torch.as_tensor(nodes).reshape(-1).to(device=rel.device, dtype=rel.idtype).contiguous()   # (ids, a list or one id)
+    nodes = _node_ids(nodes, rel.device, rel.idtype)
     if prob is None:
         indptr, nbr, eids = _capi.sample_neighbors(csr, nodes, int(fanout), replace, int(seed))
     else:
@@ -503,15 +524,11 @@ class NeighborSampler:
 
 # ---- random walks ------------------------------------------------------------------------------
 def _walk_cdf(rel, csr, w):
-    """The CDF of relation ``rel`` under the edge weights ``w``: built on first use and kept in ONE slot on the
-    relation, keyed by the weight tensor's address, ``_version``, shape, dtype and device and checked at every use (as
-    ``static_features`` checks its promise), so an in-place write to the weights rebuilds it."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), w.dtype, w.device)
-    slot = getattr(rel, "_walk_cdf", None)
-    if slot is None or slot[0] != key:
+    """The CDF of relation ``rel`` under the edge weights ``w``: one :func:`_relation_slot`, keyed by the weight tensor."""
+    def build():
         p = (w if w.dtype in (torch.float32, torch.float64) else w.float()).contiguous().reshape(-1)
-        slot = rel._walk_cdf = (key, _capi.random_walk_cdf(csr, p))
-    return slot[1]
+        return _capi.random_walk_cdf(csr, p)
+    return _relation_slot(rel, "_walk_cdf", (w,), build)
 
 
 def _walk_plan(g, metapath, length):
@@ -580,14 +597,13 @@ def random_walk(g, nodes, *, metapath=None, length=None, prob=None, restart_prob
                                 % (rel.num_edges, tuple(w.shape)))
             cdf = _walk_cdf(rel, csr, w.to(dev))
         table.append((csr, cdf))
-    nodes = torch.as_tensor(nodes).reshape(-1).to(device=dev, dtype=idt).contiguous()
+    nodes = _node_ids(nodes, dev, idt)
     if restart_steps is not None:
         restart_steps = restart_steps.to(dev)
         if restart_steps.dtype not in (torch.float32, torch.float64):
             restart_steps = restart_steps.float()
         restart_steps = restart_steps.contiguous()
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = _call_seed(seed)
     traces, eids = _capi.random_walk(table, [used.index(m) for m in metapath], nodes, restart_scalar, restart_steps,
                                      int(seed), return_eids)
     types = torch.tensor(types, dtype=idt, device=dev)
@@ -595,14 +611,9 @@ def random_walk(g, nodes, *, metapath=None, length=None, prob=None, restart_prob
 
 
 def _walk_members(rel, fmt, csr):
-    """The membership list of relation ``rel`` (every row's column ids ascending, what the node2vec step bisects): built
-    on first use and kept in ONE slot on the relation, keyed by the addresses and ``_version`` of the CSR's arrays and
-    checked at every use, like :func:`_walk_cdf`.  It costs ``nnz`` ids of device memory."""
-    key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device) for t in fmt[:2])
-    slot = getattr(rel, "_walk_members", None)
-    if slot is None or slot[0] != key:
-        slot = rel._walk_members = (key, _capi.csr_sorted_columns(csr))
-    return slot[1]
+    """The membership list of relation ``rel`` (every row's column ids ascending, what the node2vec step bisects): one
+    :func:`_relation_slot`, keyed by the CSR's arrays.  It costs ``nnz`` ids of device memory."""
+    return _relation_slot(rel, "_walk_members", fmt[:2], lambda: _capi.csr_sorted_columns(csr))
 
 
 def node2vec_random_walk(g, nodes, p, q, walk_length, prob=None, return_eids=False, seed=None):
@@ -636,9 +647,8 @@ def node2vec_random_walk(g, nodes, p, q, walk_length, prob=None, return_eids=Fal
     csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst)    # (refuses a CPU graph: no CPU fallback)
     cdf = None if w is None else _walk_cdf(rel, csr, w.to(dev))   # the slot random_walk uses
     member = _walk_members(rel, fmt, csr)
-    nodes = torch.as_tensor(nodes).reshape(-1).to(device=dev, dtype=idt).contiguous()
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    nodes = _node_ids(nodes, dev, idt)
+    seed = _call_seed(seed)
     traces, eids = _capi.node2vec_walk(csr, cdf, member, nodes, walk_length, p, q, int(seed), return_eids)
     return (traces, eids) if return_eids else traces
 
@@ -664,11 +674,9 @@ def _relation_lookup(rel):
     """``(dgla_csr, membership list)`` of relation ``rel``: the list is the slot :func:`node2vec_random_walk` uses; the
     struct is kept next to it under the same key, so a small lookup does not pay for building it on every call."""
     fmt = rel.csr()
-    key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device) for t in fmt[:2])
-    slot = getattr(rel, "_walk_csr", None)
-    if slot is None or slot[0] != key:
-        slot = rel._walk_csr = (key, _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst))    # (refuses a CPU graph)
-    return slot[1], _walk_members(rel, fmt, slot[1])
+    csr = _relation_slot(rel, "_walk_csr", fmt[:2],
+                         lambda: _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_dst))    # (refuses a CPU graph)
+    return csr, _walk_members(rel, fmt, csr)
 
 
 def _has_edges(rel, u, v):
@@ -727,8 +735,7 @@ def global_uniform_negative_sampling(g, num_samples, exclude_self_loops=True, re
         src = torch.full((num_samples if padded else 0,), -1, dtype=idt, device=dev)
         return (src, src.clone(), torch.zeros(1, dtype=torch.int64, device=dev)) if padded else (src, src.clone())
     csr, member = _relation_lookup(rel)
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = _call_seed(seed)
     src, dst, count = _capi.negative_sample(csr, member, n_slots, num_samples, NEGATIVE_SAMPLING_TRIALS,
                                             exclude_self_loops, replace, int(seed))
     if padded:
