@@ -22,7 +22,7 @@ from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, ad
 from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401
-from .sampling import (EID, NID, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
+from .sampling import (EID, NID, LaborSampler, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
                        global_uniform_negative_sampling, node2vec_random_walk, to_block)
 from . import negative_sampler  # noqa: E402,F401
 from .mm import gather_mm, segment_mm  # noqa: E402,F401

@@ -831,6 +831,87 @@ def csr_has_edges_host(csr, member, u, v):
     return out.view(torch.bool)
 
 
+def _labor_rel(csr, prob, seeds, c=None):
+    """The leading arguments the layer-neighbour entry points share: (csr, prob, prob_dtype)."""
+    if prob is not None:
+        _prob_ok(prob)
+        if prob.shape[0] != csr.nnz:
+            raise _lib.DGLAMDError("prob must hold one value per edge (%d), got %d" % (csr.nnz, prob.shape[0]))
+    if seeds.dim() != 1 or not seeds.is_contiguous() or _idbits(seeds) != csr.idtype_bits:
+        raise _lib.DGLAMDError("seeds must be a contiguous 1-D tensor of the csr's id type")
+    if c is not None and (c.dtype != torch.float64 or c.shape != seeds.shape or not c.is_contiguous()):
+        raise _lib.DGLAMDError("c must be a contiguous float64 tensor with one entry per seed")
+    if prob is not None and c is not None and c.device != prob.device:
+        raise _lib.DGLAMDError("c and prob must be on one device")
+    return [ctypes.byref(csr), _ptr(prob), _DTYPES[prob.dtype] if prob is not None else 0]
+
+
+def labor_scale(csr, prob, seeds, fanout):
+    """The per-seed scale ``c`` of weighted layer-neighbour sampling (dgla_labor_scale; the rule: include/dgl_amd.h):
+    float64 [len(seeds)], the solution of ``sum min(1, c w') = fanout`` over each seed's row.  Nothing is read back."""
+    _all_on(True, "labor_scale", csr._keep[0], prob, seeds)
+    rel = _labor_rel(csr, prob, seeds)
+    c = torch.empty(seeds.shape[0], dtype=torch.float64, device=seeds.device)
+    check_call(LIB.dgla_labor_scale(*rel, _ptr(seeds), seeds.shape[0], int(fanout), _ptr(c), _stream(seeds)))
+    return c
+
+
+def labor_scale_host(csr, prob, seeds, fanout):
+    """:func:`labor_scale` run by the CPU on CPU tensors (dgla_labor_scale_host; `csr` built with :func:`host_csr`).
+    Needs no GPU."""
+    _all_on(False, "labor_scale_host", prob, seeds)
+    rel = _labor_rel(csr, prob, seeds)
+    c = torch.empty(seeds.shape[0], dtype=torch.float64)
+    check_call(LIB.dgla_labor_scale_host(*rel, _ptr(seeds), seeds.shape[0], int(fanout), _ptr(c)))
+    return c
+
+
+def labor_sample(csr, seeds, fanout, rng_seed=0, prob=None, c=None):
+    """Layer-neighbour sampling over the CSR `csr` whose rows are the seed side (dgla_labor_count + dgla_labor_fill):
+    returns ``(indptr, nbr, eids, importances)``, a CSR over the seeds with GLOBAL neighbour / edge ids; `importances`
+    (prob's dtype) is None without `prob`.  `c` from :func:`labor_scale` (computed here when None).  Reading the total
+    is the one host synchronisation."""
+    _all_on(True, "labor_sample", csr._keep[0], prob, seeds, c)
+    if prob is not None and c is None:
+        c = labor_scale(csr, prob, seeds, fanout)
+    rel = _labor_rel(csr, prob, seeds, c)
+    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
+    need = LIB.dgla_labor_workspace_bytes(csr.idtype_bits, n)
+    ws = _workspace(need, dev)
+    indptr = torch.empty(n + 1, dtype=dt, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    st = _stream(seeds)
+    args = rel + [_ptr(c), _ptr(seeds), n, int(fanout), _u64(rng_seed)]
+    check_call(LIB.dgla_labor_count(*args, _ptr(indptr), _ptr(total), _ptr(ws), need, st))
+    cap = int(total.item())
+    if csr.idtype_bits == 32 and cap >= 2 ** 31:
+        raise _lib.DGLAMDError("labor_sample: %d picked edges do not fit int32 ids; use int64 ids" % cap)
+    nbr = torch.empty(cap, dtype=dt, device=dev)
+    eids = torch.empty(cap, dtype=dt, device=dev)
+    imp = torch.empty(cap, dtype=prob.dtype, device=dev) if prob is not None else None
+    check_call(LIB.dgla_labor_fill(*args, cap, _ptr(nbr), _ptr(eids), _ptr(imp), _ptr(ws), need, st))
+    return indptr, nbr, eids, imp
+
+
+def labor_pick_host(csr, seeds, fanout, rng_seed=0, prob=None, c=None):
+    """:func:`labor_sample` run by the CPU on CPU tensors (dgla_labor_pick_host; `csr` built with :func:`host_csr`): the
+    same rule compiled for the host, bit for bit what the kernels write from the same `c`.  Needs no GPU."""
+    _all_on(False, "labor_pick_host", prob, seeds, c)
+    if prob is not None and c is None:
+        c = labor_scale_host(csr, prob, seeds, fanout)
+    rel = _labor_rel(csr, prob, seeds, c)
+    n, dt = seeds.shape[0], seeds.dtype
+    indptr = torch.empty(n + 1, dtype=dt)
+    args = rel + [_ptr(c), _ptr(seeds), n, int(fanout), _u64(rng_seed)]
+    check_call(LIB.dgla_labor_pick_host(*args, _ptr(indptr), None, None, None))       # the sizes
+    cap = int(indptr[-1])
+    nbr, eids = torch.empty(cap, dtype=dt), torch.empty(cap, dtype=dt)
+    imp = torch.empty(cap, dtype=prob.dtype) if prob is not None else None
+    if cap:     # (an empty tensor has no address to hand over)
+        check_call(LIB.dgla_labor_pick_host(*args, _ptr(indptr), _ptr(nbr), _ptr(eids), _ptr(imp)))
+    return indptr, nbr, eids, imp
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

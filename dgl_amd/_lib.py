@@ -259,6 +259,23 @@ LIB.dgla_csr_has_edges.restype = c_int
 LIB.dgla_csr_has_edges.argtypes = [P(CSR), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
 LIB.dgla_csr_has_edges_host.restype = c_int
 LIB.dgla_csr_has_edges_host.argtypes = [P(CSR), c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+# csr, prob, prob_dtype  /  seeds, num_seeds, fanout
+_LABOR_REL, _LABOR_SEEDS = [P(CSR), c_void_p, c_int], [c_void_p, c_int64, c_int64]
+LIB.dgla_labor_workspace_bytes.restype = c_size_t
+LIB.dgla_labor_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_labor_scale.restype = c_int
+LIB.dgla_labor_scale.argtypes = _LABOR_REL + _LABOR_SEEDS + [c_void_p, c_void_p]
+LIB.dgla_labor_scale_host.restype = c_int
+LIB.dgla_labor_scale_host.argtypes = _LABOR_REL + _LABOR_SEEDS + [c_void_p]
+LIB.dgla_labor_count.restype = c_int
+LIB.dgla_labor_count.argtypes = _LABOR_REL + [c_void_p] + _LABOR_SEEDS + [ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
+                                                                         c_size_t, c_void_p]
+LIB.dgla_labor_fill.restype = c_int
+LIB.dgla_labor_fill.argtypes = _LABOR_REL + [c_void_p] + _LABOR_SEEDS + [ctypes.c_uint64, c_int64, c_void_p, c_void_p,
+                                                                        c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_labor_pick_host.restype = c_int
+LIB.dgla_labor_pick_host.argtypes = _LABOR_REL + [c_void_p] + _LABOR_SEEDS + [ctypes.c_uint64, c_void_p, c_void_p,
+                                                                             c_void_p, c_void_p]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -14,7 +14,9 @@ block keeps one source and one destination node set per node type (R-GCN mini-ba
 ``RandomWalkNeighborSampler`` / ``PinSAGESampler`` mirror python/dgl/sampling/pinsage.py:27-272: those walks followed by
 the visit-count top-k of csrc/pinsage.hip.  ``node2vec_random_walk`` mirrors python/dgl/sampling/node2vec_randomwalk.py
 over csrc/node2vec.hip: the bounded second-order step of csrc/node2vec_step.h.  ``global_uniform_negative_sampling`` mirrors
-python/dgl/sampling/negative.py over csrc/negative_sampling.hip (the rule: csrc/negative_sample_step.h).
+python/dgl/sampling/negative.py over csrc/negative_sampling.hip (the rule: csrc/negative_sample_step.h).  ``sample_labors`` /
+``LaborSampler`` mirror python/dgl/sampling/labor.py and python/dgl/dataloading/labor_sampler.py over csrc/labor.hip:
+layer-neighbour sampling, one variate per source node (the rule: csrc/labor_step.h).
 """
 import math
 
@@ -520,6 +522,177 @@ class NeighborSampler:
             seeds, nv = src_nodes, num_src
         self.counter += 1
         return seeds, nv, output_nodes, blocks
+
+
+# ---- layer-neighbour (LABOR) sampling ------------------------------------------------------------
+def _labor_seed(random_seed):
+    """``random_seed`` of :func:`sample_labors`: an int, a one-element int64 tensor, or None (drawn like every call seed)."""
+    if torch.is_tensor(random_seed):
+        if random_seed.numel() != 1:
+            raise _DGLError("sample_labors: random_seed must be an int or a tensor with one element")
+        random_seed = int(random_seed.reshape(-1)[0].item())
+    return _call_seed(random_seed)
+
+
+def _per_etype_ids(g, value):
+    """``value`` (ids, or a dict keyed by edge type) -> one id tensor or None per relation."""
+    if value is None:
+        return [None] * len(g.canonical_etypes)
+    if not isinstance(value, dict):
+        if len(g.canonical_etypes) > 1:
+            raise _DGLError("Must specify etype when the graph is not homogeneous.")
+        value = {g.canonical_etypes[0]: value}
+    out = [None] * len(g.canonical_etypes)
+    for e, ids in value.items():
+        out[g.get_etype_id(e)] = ids
+    return out
+
+
+def sample_labors(g, nodes, fanout, edge_dir="in", prob=None, importance_sampling=0, random_seed=None,
+                  seed2_contribution=0, copy_ndata=True, copy_edata=True, exclude_edges=None, output_device=None):
+    """``dgl.sampling.sample_labors`` (python/dgl/sampling/labor.py): layer-neighbour sampling (LABOR-0, Balin and
+    Catalyurek, arXiv:2210.13339).  Every node in ``nodes`` keeps about ``fanout`` of its inbound (``edge_dir="out"``:
+    outbound) edges per edge type, all of them when it has no more or ``fanout == -1``; the random variate belongs to
+    the NEIGHBOUR node, not to the edge, so seeds that share a neighbour keep or drop it together and the set of distinct
+    neighbours comes out much smaller than :func:`sample_neighbors`' at the same fanout.
+
+    ``nodes`` is an id tensor or a dict per node type, ``fanout`` an int or a dict per edge type, ``prob`` the name of an
+    edge feature of unnormalised weights (relations that lack it sample uniformly; zero, negative and NaN weights are
+    never kept).  ``random_seed`` (an int or a one-element int64 tensor; None draws one from torch's generator) fixes the
+    variates: ALL relations of a call share it, so a node keeps its variate across edge types, and calls that belong to
+    one batch should pass the same seed.  ``exclude_edges`` (ids, or a dict per edge type) drops those edges from the
+    result after sampling, as the reference does on a GPU graph.
+
+    Returns ``(frontier, importances)``: the frontier holds all nodes of ``g`` and the sampled edges, the original edge
+    ids in ``edata[dgl.EID]``, the node features of ``g`` (the same tensors, ``copy_ndata``) and its edge features at the
+    sampled edges (``copy_edata``); ``importances`` has one tensor per edge type with one weight per frontier edge,
+    averaging 1 over the edges of a seed, such that ``fn.mean`` over the frontier is unbiased.  It is empty for a
+    relation sampled uniformly, as in the reference.
+
+    The picks run on the device (csrc/labor.hip; the rule: include/dgl_amd.h "Layer-neighbour sampling") and are a pure
+    function of the arguments.  With weights the expected number of kept edges per seed is ``fanout``, the definition of
+    the paper; the reference matches a variance target instead and keeps more.  Not supported, and refused:
+    ``importance_sampling != 0`` (LABOR-i) and ``seed2_contribution != 0``."""
+    if importance_sampling != 0:
+        raise _DGLError("sample_labors: importance_sampling = %r is not supported: LABOR-i needs a per-neighbour maximum "
+                        "over the seeds; only importance_sampling = 0 (LABOR-0) runs here" % (importance_sampling,))
+    if seed2_contribution != 0:
+        raise _DGLError("sample_labors: seed2_contribution = %r is not supported: the variates come from one seed; pass "
+                        "seed2_contribution = 0" % (seed2_contribution,))
+    if edge_dir not in ("in", "out"):
+        raise ValueError("edge_dir must be 'in' or 'out'")
+    if g.device.type != "cuda":
+        raise _DGLError("sample_labors runs on a ROCm GPU; the graph is on %s (no CPU fallback)" % g.device)
+    seed = _labor_seed(random_seed)
+    if not isinstance(nodes, dict):
+        if len(g.ntypes) != 1:
+            raise _DGLError("Must specify node type when the graph is not homogeneous.")
+        nodes = {g.ntypes[0]: nodes}
+    for n in nodes:
+        if n not in g.ntypes:
+            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    fanouts = _per_etype(g, fanout, "fanout")
+    excluded = _per_etype_ids(g, exclude_edges)
+    rels, picked, importances = [], [], []
+    for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
+        rel = g._graph.relations[etid]
+        dev, idt = rel.device, rel.idtype
+        frame = g._edge_frames[etid]
+        p = _prob_of(prob, frame, rel, "sample_labors") if prob is not None and (not isinstance(prob, str) or prob in frame) \
+            else None
+        seeds = nodes.get(d_t if edge_dir == "in" else s_t)
+        f = int(fanouts[etid])
+        if seeds is None or f == 0 or rel.num_edges == 0 or torch.as_tensor(seeds).numel() == 0:
+            own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
+            imp = torch.empty(0, dtype=torch.float32 if p is None else p.dtype, device=dev)
+        else:
+            seeds = _node_ids(seeds, dev, idt)
+            fmt = rel.csc() if edge_dir == "in" else rel.csr()
+            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_src if edge_dir == "in" else rel.num_dst)
+            # the SAME seed for every relation: a node's variate is shared across edge types (labor.py:101-112)
+            indptr, nbr, eids, imp = _capi.labor_sample(csr, seeds, f, seed, prob=p)
+            own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=int(eids.shape[0]))
+            if imp is None:
+                imp = torch.empty(0, dtype=torch.float32, device=dev)
+            if excluded[etid] is not None:
+                keep_e = ~torch.isin(eids, _node_ids(excluded[etid], dev, idt))
+                own, nbr, eids = own[keep_e], nbr[keep_e], eids[keep_e]
+                if p is not None:
+                    imp = imp[keep_e]
+        src, dst = (nbr.contiguous(), own) if edge_dir == "in" else (own, nbr.contiguous())
+        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev))
+        picked.append(eids)
+        importances.append(imp)
+    gi = g._graph
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
+                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
+    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
+        for i, fr in enumerate(g._node_frames):
+            for key, val in fr.items():
+                out._node_frames[i][key] = val
+    for etid, e in enumerate(picked):
+        if copy_edata:
+            for key, val in g._edge_frames[etid].items():
+                if key != EID:
+                    out._edge_frames[etid][key] = val[e.long()]
+        out._edge_frames[etid][EID] = e
+    if output_device is not None:
+        out = out.to(output_device)
+        importances = [w.to(output_device) for w in importances]
+    return out, importances
+
+
+DGLGraph.sample_labors = sample_labors
+
+
+class LaborSampler:
+    """``dgl.dataloading.LaborSampler`` (python/dgl/dataloading/labor_sampler.py): one block per layer, built from the
+    output nodes inwards; a layer is :func:`sample_labors` followed by :func:`to_block` on the seeds.
+    ``sample_blocks(g, seed_nodes)`` returns ``(input_nodes, output_nodes, blocks)``; ``blocks[i].srcdata[dgl.NID]`` /
+    ``dstdata[dgl.NID]`` / ``edata[dgl.EID]`` hold the original ids and, when ``prob`` names an edge feature,
+    ``edata["edge_weights"]`` the importances.  ``layer_dependency=True`` samples every layer of a batch with one seed, so
+    a node keeps its variate from layer to layer and the layers overlap more; ``False`` gives each layer its own seed.
+    Successive calls advance the seeds, like :class:`NeighborSampler`; two samplers with the same ``seed`` agree."""
+
+    def __init__(self, fanouts, edge_dir="in", prob=None, importance_sampling=0, layer_dependency=False, seed=0):
+        if edge_dir != "in":
+            raise _DGLError("LaborSampler: only inbound sampling yields blocks whose destinations are the seeds")
+        self.fanouts = [f if isinstance(f, dict) else int(f) for f in fanouts]
+        self.edge_dir = edge_dir
+        self.prob = prob
+        self.importance_sampling = importance_sampling
+        self.layer_dependency = bool(layer_dependency)
+        self.seed = int(seed)
+        self._calls = 0
+
+    def sample_blocks(self, g, seed_nodes):
+        as_dict = isinstance(seed_nodes, dict)
+        if not as_dict:
+            if len(g.ntypes) != 1:
+                raise _DGLError("seed_nodes must be a dict of node type -> ids on a graph with several node types")
+            seed_nodes = {g.ntypes[0]: seed_nodes}
+        seeds = {n: torch.as_tensor(v).to(device=g.device, dtype=g.idtype).contiguous() for n, v in seed_nodes.items()}
+        output_nodes = dict(seeds)
+        blocks = []
+        for layer, fanout in enumerate(reversed(self.fanouts)):
+            rng = (self.seed * 1000003 + self._calls) * 64 + (0 if self.layer_dependency else layer)
+            frontier, imps = sample_labors(g, seeds, fanout, edge_dir=self.edge_dir, prob=self.prob,
+                                           importance_sampling=self.importance_sampling, random_seed=rng,
+                                           copy_ndata=False, copy_edata=False)
+            blk = to_block(frontier, seeds)
+            for etid in range(len(g.canonical_etypes)):          # ids of the ORIGINAL graph (labor_sampler.py)
+                fe = frontier._edge_frames[etid][EID]
+                at = blk._edge_frames[etid][EID].long()
+                blk._edge_frames[etid][EID] = fe[at]
+                if self.prob is not None and imps[etid].shape[0] == fe.shape[0]:
+                    blk._edge_frames[etid]["edge_weights"] = imps[etid][at]
+            blocks.insert(0, blk)
+            seeds = {n: blk.srcnodes[n].data[NID] for n in g.ntypes}
+        self._calls += 1
+        if as_dict:
+            return seeds, output_nodes, blocks
+        n = g.ntypes[0]
+        return seeds[n], output_nodes[n], blocks
 
 
 # ---- random walks ------------------------------------------------------------------------------

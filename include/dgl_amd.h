@@ -753,6 +753,82 @@ int dgla_csr_has_edges(const dgla_csr* csr, const void* member, const void* u, c
                        void* hip_stream);
 int dgla_csr_has_edges_host(const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n, uint8_t* out);
 
+/* ---- Layer-neighbour sampling: LABOR-0 over whole rows (csrc/labor.hip) -----------------------------
+ * Replace CSRLaborSampling<kDGLCUDA> (src/array/cuda/labor_sampling.cu over src/array/labor_pick.h, behind
+ * dgl.sampling.sample_labors and dgl.dataloading.LaborSampler, python/dgl/sampling/labor.py): layer-neighbour sampling
+ * of Balin and Catalyurek (arXiv:2210.13339) with importance_sampling = 0.  One random variate per SOURCE NODE instead
+ * of one per edge, so seeds that share a neighbour keep or drop it together.  The generator and the draws are those of
+ * "Random walks" above.  The rule (ONE definition for device and host, csrc/labor_step.h):
+ *
+ * Setting.  One relation as a CSR whose rows are the seed side (the in-edge CSR for edge_dir = "in", the out-edge CSR
+ * for "out"): indptr, indices (neighbour ids), data (the edge-id map or NULL).  Parameters: seeds[n], a fanout k (an
+ * int >= 0, or negative for "all"), a 64-bit seed and optionally prob, indexed by EDGE ID (fp32 or fp64).  A seed
+ * outside [0, num_rows) is a row of degree 0 and touches no memory through that id.
+ *
+ * Variate.  r(t) = rw_draw(rw_step_key(rw_walk_key(seed, t), 0), 0) for neighbour node id t: a function of (seed, t)
+ * only.  The seed row, the relation, the layer and the position in `seeds` do not enter it.
+ *
+ * Uniform rule (no prob).  Row i with lo = indptr[seeds[i]], hi = indptr[seeds[i] + 1], d = hi - lo.  If k < 0 or
+ * d <= k every position is kept.  Otherwise position q is kept iff rw_index(r(indices[q]), d) < k (integers only; the
+ * inclusion probability is k / d to within 2^-64).
+ *
+ * Weighted rule.  w'(q) = rw_weight(prob[data ? data[q] : q]) (negative and NaN weights count as 0).  P = the number of
+ * positions of the row with w' > 0, W = their sum.  With the row's scale c_i, p(q) = min(1, c_i * w'(q)), ONE fp64
+ * multiply, and q is kept iff c_i > 0, w'(q) > 0 and rw_uniform(r(indices[q])) < p(q).  The scale carries the special rows:
+ *   W not finite -> c_i = 0 (nothing is kept);  else k < 0 or P <= k -> c_i = +inf (p = 1 exactly where w' > 0);
+ *   else c_i finite, by the iteration below.
+ *
+ * Scale.  c_i solves sum_q min(1, c * w'(q)) = k (the paper's definition: the expected number of kept edges is k), by
+ * the finite saturation iteration:  c <- k / W;  repeat  m = #{q: c * w'(q) >= 1},  U = sum of w'(q) over
+ * c * w'(q) < 1,  c <- (k - m) / U;  stop when m no longer changes.  c only rises and m < k holds throughout.  At most
+ * kLaborMaxPasses = 64 passes; when the bound is reached the current c is used.  The law stays exact for any c: the
+ * importances use the actual p, only the expected count drifts.  The order of the additions is free, so the scale is a
+ * separate step with its own output double c[n] (device and host agree to rounding), and the pick takes c as an input.
+ * (The reference instead matches a variance target, equation 22 of the paper, labor_pick.h:122-152, and so samples
+ * more than k edges per seed on a weighted graph.)
+ *
+ * Importances (weighted form only).  For a kept q, a(q) = w'(q) / p(q); the output is a(q) * (n_i / S_i) in prob's
+ * dtype, n_i the row's kept count and S_i the sum of a over the row's kept positions, computed in fp64 in the fixed
+ * order csrc/labor_step.h states (64 position classes, then a tree).  A row's importances sum to n_i.
+ *
+ * Order.  Output goes seed by seed in the given order and, within a seed, in ascending CSR position.  For every kept
+ * edge: the neighbour id indices[q], the edge id (data[q], or q) and, weighted, the importance.
+ *
+ * The result is a pure function of (graph, seeds, k, seed, prob, c), whatever the launch geometry; pick on the device
+ * and pick on the host agree bit for bit from the same c.  No atomics.
+ *
+ * dgla_labor_workspace_bytes: the workspace dgla_labor_count and dgla_labor_fill share, 16 bytes per seed plus the
+ *   scan's scratch; 0 for num_seeds <= 0 or another id width.  Nothing is sized by the graph.
+ * dgla_labor_scale: c[num_seeds] (device) for a weighted call; csr->indptr, csr->data, prob, seeds are device memory,
+ *   csr->indices is not read.  One launch, a group of lanes per row, up to 64 passes over the row.
+ * dgla_labor_count: out_indptr[num_seeds + 1] (the CSR's id type) and *total (one int64), both device memory; prob
+ *   NULL = uniform (c is then ignored), else c from dgla_labor_scale.  Offsets by the library's own scan; stream-ordered,
+ *   no allocation, nothing read back.  It leaves the offsets and the rows' importance sums in the workspace.
+ * dgla_labor_fill: with the same arguments and the workspace count left, writes out_nbr / out_eid (the id type) and,
+ *   weighted, out_imp (prob's dtype), each of `capacity` >= total entries; no write goes past capacity.
+ * A group of 16 lanes serves a row when csr->nnz / csr->num_rows <= 32, a wavefront of 64 otherwise; the bits written
+ *   do not depend on it.
+ * dgla_labor_scale_host / dgla_labor_pick_host: the same rule run by the CPU on HOST pointers, no workspace and no
+ *   stream.  pick_host with out_nbr == NULL writes out_indptr only (the sizes); otherwise out_nbr / out_eid / out_imp
+ *   must hold out_indptr[num_seeds] entries.  Host-only: need no GPU.
+ * All fail with -1 and a message, before any launch, for a NULL csr / indptr / indices / seeds / output, an id width
+ *   other than 32 / 64, negative sizes, num_seeds >= 2^31, a prob dtype other than fp32 (0) / fp64 (1), a weighted call
+ *   without c and a workspace that is too small.  num_seeds == 0 and nnz == 0 are valid and read no graph memory. */
+size_t dgla_labor_workspace_bytes(int idtype_bits, int64_t num_seeds);
+int dgla_labor_scale(const dgla_csr* csr, const void* prob, int prob_dtype, const void* seeds, int64_t num_seeds,
+                     int64_t fanout, double* c, void* hip_stream);
+int dgla_labor_count(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
+                     int64_t num_seeds, int64_t fanout, uint64_t seed, void* out_indptr, int64_t* total, void* workspace,
+                     size_t workspace_bytes, void* hip_stream);
+int dgla_labor_fill(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
+                    int64_t num_seeds, int64_t fanout, uint64_t seed, int64_t capacity, void* out_nbr, void* out_eid,
+                    void* out_imp, const void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_labor_scale_host(const dgla_csr* csr, const void* prob, int prob_dtype, const void* seeds, int64_t num_seeds,
+                          int64_t fanout, double* c);
+int dgla_labor_pick_host(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
+                         int64_t num_seeds, int64_t fanout, uint64_t seed, void* out_indptr, void* out_nbr, void* out_eid,
+                         void* out_imp);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
