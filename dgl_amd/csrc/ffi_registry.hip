@@ -14,6 +14,14 @@
 // of it are used on this path, src/array/kernel.cc:20-44,224-248).  It is built through the
 // `dgl_amd._CAPI_UnitGraph*` functions, which have no counterpart in the reference (there the
 // graph engine owns the index arrays; here PyTorch does and the handle only borrows pointers).
+//
+// Every fixed-length entry reads its arguments with ONE call, `unpack(a, &x0, &x1, ...)`: positions 0, 1, 2, ... in
+// order, the kind of each chosen by the destination's type, trailing optional ones wrapped in `opt(&x)`.  A
+// `UnitGraph**` / `HeteroGraphObj**` destination also checks the tag every object handle starts with, so no entry
+// casts a handle it has not checked; a handle of the wrong kind is refused with "argument i: not a unit graph".
+// `check_arrays` is the one placement / contiguity / element-type check of array operands; each call site passes the
+// words of its own messages.  DGLFuncCall presets the return type code to kNull; entries that return a number use
+// `ret_int`.
 #include "../../include/dgl_amd.h"
 
 #include <atomic>
@@ -146,6 +154,60 @@ static void to_tensor(const DGLArray* a, TensorArg* out) {
   out->t.shape = out->shape.data();
 }
 
+static void* ptr_or_null(const DGLArray* t) { return null_array(t) ? nullptr : data_ptr(t); }
+
+// An EMPTY array that was given (a block side without nodes, a product without entries) has no data but keeps its
+// shape: `data_or_null` / `shaped_tensor` are ptr_or_null / to_tensor for operands where that shape matters.
+static void* data_or_null(const DGLArray* t) { return t->data ? data_ptr(t) : nullptr; }
+static void shaped_tensor(const DGLArray* a, TensorArg* out) {
+  out->shape.assign(a->shape, a->shape + a->ndim);
+  out->t.data = data_or_null(a);
+  out->t.ndim = a->ndim;
+  out->t.shape = out->shape.data();
+}
+
+// The one check of array operands (CheckCtx / CheckContiguous of src/array/kernel.cc:483-497 and the dtype rules
+// next to them): every array of `arrs` that is present is on a GPU (else `not_gpu`, the call site's full sentence)
+// and contiguous ("<noun> must be contiguous"); with `same`, it also has a float element type, and that one.
+// Absent means null_array(); with `empty_counts` only a missing array (none given, or 0-d) is absent and an empty
+// one is checked like any other, as the segment, GAT and spgemm entries always did.
+static int check_arrays(std::initializer_list<const DGLArray*> arrs, const char* noun, const char* not_gpu,
+                        const dgla_dtype* same = nullptr, bool empty_counts = false) {
+  for (const DGLArray* t : arrs) {
+    if (empty_counts ? (!t || t->ndim == 0) : null_array(t)) continue;
+    if (!on_gpu(t)) return fail(not_gpu);
+    if (check_contiguous(t, noun)) return -1;
+    dgla_dtype d;
+    if (!same) continue;
+    if (float_dtype(t, &d)) return -1;
+    if (d != *same) return fail("operand and output dtypes differ");
+  }
+  return 0;
+}
+constexpr const char* kNotOnGraphGpu = "array is not on the GPU device of the graph";
+constexpr const char* kNotOnGpu = "array is not on a GPU device";
+
+// scratch handed over as a uint8 array (or nothing)
+struct Workspace {
+  void* p;
+  size_t bytes;
+};
+static Workspace workspace_of(const DGLArray* ws) {
+  return {ptr_or_null(ws), null_array(ws) ? 0 : static_cast<size_t>(ws->shape[0])};
+}
+
+// entries that return a count or a size (every other entry returns kNull, which DGLFuncCall presets)
+static int ret_int(DGLValue* ret, int* rtc, int64_t v) {
+  *rtc = kObjectInt;
+  ret->v_int64 = v;
+  return 0;
+}
+// ... a size that was computed after last_error().clear() by a function that reports problems only there
+static int ret_size(DGLValue* ret, int* rtc, size_t v) {
+  ret_int(ret, rtc, static_cast<int64_t>(v));
+  return last_error().empty() ? 0 : -1;
+}
+
 // ---- the unit graph handle ----------------------------------------------------------
 struct SparseFmt {
   bool present = false;
@@ -156,11 +218,19 @@ struct SparseFmt {
 };
 
 // Every object handed to Python as an opaque handle starts with a tag, so a function that is
-// given the wrong kind of handle fails with a message instead of reading garbage.
+// given the wrong kind of handle fails with a message instead of reading garbage (the argument
+// reader below checks it for every typed handle it hands out).
 constexpr uint32_t kMagicUnit = 0x554e4954u, kMagicList = 0x4c495354u, kMagicValue = 0x56414c55u,
                    kMagicHetero = 0x48455445u;
+static uint32_t magic_of(const void* h) { return h ? *static_cast<const uint32_t*>(h) : 0; }
 
 struct UnitGraph {
+  UnitGraph() = default;
+  UnitGraph(const UnitGraph&) = delete;
+  ~UnitGraph() {  // the graph owns only the position-ordered edge-operand copy and its hashes
+    if (eord) (void)hipFree(eord);
+    if (eord_hash) (void)hipFree(eord_hash);
+  }
   uint32_t magic = kMagicUnit;
   int64_t num_src = 0, num_dst = 0, num_edges = 0;
   int idbits = 64;
@@ -204,6 +274,93 @@ struct UnitGraph {
   size_t esm_ws_bytes = 0;
   bool esm_plan_valid = false;
 };
+
+// Lists of values and the heterograph handle: what sparse._CAPI_DGLKernelSpMMHetero / SDDMMHetero need
+// (src/array/kernel.cc:563-601,628-656).  The reference boxes Python lists as List<Value> objects through
+// `_List` / `_Value` (python/dgl/_ffi/object_generic.py:27-59, src/api/api_container.cc); the same two global
+// names exist here with the same meaning.
+struct ObjValue {
+  uint32_t magic = kMagicValue;
+  DGLValue v;
+  int tc = kNull;
+};
+struct ObjList {
+  uint32_t magic = kMagicList;
+  std::vector<ObjValue> items;
+};
+struct HeteroGraphObj {
+  uint32_t magic = kMagicHetero;
+  int num_ntypes = 0;
+  std::vector<UnitGraph*> rel;  // borrowed: the unit graphs outlive this object
+  std::vector<int> src, dst;    // metagraph: etype -> (src ntype, dst ntype)
+};
+
+static int get_list(const FfiArgs& a, int i, const ObjList** out) {
+  void* h = nullptr;
+  if (i < a.n && a.tc[i] == kNull) {
+    static const ObjList empty;
+    *out = &empty;
+    return 0;
+  }
+  if (get_handle(a, i, &h) || magic_of(h) != kMagicList)
+    return fail("argument " + std::to_string(i) + ": expected a list (see _List)");
+  *out = static_cast<const ObjList*>(h);
+  return 0;
+}
+
+// ---- the argument reader ---------------------------------------------------------------
+// unpack(a, &x0, &x1, ...) reads positions 0, 1, 2, ... into its destinations and refuses the call at the first one
+// whose type code is wrong or that is missing.  A handle of the wrong KIND (its tag) is refused once every position
+// has the right type code, as the heterograph entries always did.  Nothing is allocated unless the call is refused.
+struct BadTag {
+  int pos = -1;  // first position whose handle is of the wrong kind
+  const char* what = nullptr;
+  int refuse() const { return pos < 0 ? 0 : fail("argument " + std::to_string(pos) + what); }
+};
+static int read_arg(const FfiArgs& a, int i, int64_t* out, BadTag*) { return get_int(a, i, out); }
+static int read_arg(const FfiArgs& a, int i, double* out, BadTag*) { return get_float(a, i, out); }
+static int read_arg(const FfiArgs& a, int i, const char** out, BadTag*) { return get_str(a, i, out); }
+static int read_arg(const FfiArgs& a, int i, DGLArray** out, BadTag*) { return get_array(a, i, out); }
+static int read_arg(const FfiArgs& a, int i, const ObjList** out, BadTag*) { return get_list(a, i, out); }
+template <typename Obj>
+static int read_handle(const FfiArgs& a, int i, uint32_t magic, const char* what, Obj** out, BadTag* bad) {
+  void* h;
+  if (get_handle(a, i, &h)) return -1;
+  if (magic_of(h) != magic && bad->pos < 0) *bad = BadTag{i, what};
+  *out = static_cast<Obj*>(h);  // not handed out when the tag is wrong: unpack() refuses the call
+  return 0;
+}
+static int read_arg(const FfiArgs& a, int i, UnitGraph** out, BadTag* bad) {
+  return read_handle(a, i, kMagicUnit, ": not a unit graph", out, bad);
+}
+static int read_arg(const FfiArgs& a, int i, HeteroGraphObj** out, BadTag* bad) {
+  return read_handle(a, i, kMagicHetero, ": expected a heterograph handle", out, bad);
+}
+// opt(&x): a trailing argument that may be left out; `x` then keeps the value it had
+template <typename T>
+struct Opt {
+  T* p;
+};
+template <typename T>
+static Opt<T> opt(T* p) {
+  return Opt<T>{p};
+}
+template <typename T>
+static int read_arg(const FfiArgs& a, int i, Opt<T> out, BadTag* bad) {
+  return i < a.n ? read_arg(a, i, out.p, bad) : 0;
+}
+template <typename... T>
+static int unpack(const FfiArgs& a, T... dst) {
+  BadTag bad;
+  int i = 0;
+  if ((... || read_arg(a, i++, dst, &bad))) return -1;
+  return bad.refuse();
+}
+// one unit graph at position i, for the entries whose argument list has a variable length
+static int unit_graph_at(const FfiArgs& a, int i, UnitGraph** out) {
+  BadTag bad;
+  return read_arg(a, i, out, &bad) ? -1 : bad.refuse();
+}
 
 // Is the merge plan in g->ws still the one the NEXT call expects?  The tuning bits that decide
 // the workspace layout (the split layouts) are
@@ -249,11 +406,9 @@ static dgla_coo coo_of(const UnitGraph* g) {
 }
 
 static int set_format(const FfiArgs& a, int which) {
-  void* h;
+  UnitGraph* g;
   DGLArray *x, *y, *d;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &x) || get_array(a, 2, &y) || get_array(a, 3, &d))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (unpack(a, &g, &x, &y, &d)) return -1;
   if (!x || !y) return fail("index arrays are required");
   int bx, by;
   if (idbits_of(x, &bx) || idbits_of(y, &by)) return -1;
@@ -267,8 +422,8 @@ static int set_format(const FfiArgs& a, int which) {
   SparseFmt f;
   f.present = true;
   f.a = data_ptr(x);
-  f.b = null_array(y) ? nullptr : data_ptr(y);
-  f.data = null_array(d) ? nullptr : data_ptr(d);
+  f.b = ptr_or_null(y);
+  f.data = ptr_or_null(d);
   f.nnz = y->ndim ? y->shape[0] : 0;
   if (which == 0) {
     if (x->shape[0] != f.nnz) return fail("row and col must have the same length");
@@ -290,7 +445,7 @@ static int set_format(const FfiArgs& a, int which) {
 
 static Registrar r_create("dgl_amd._CAPI_UnitGraphCreate", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   int64_t ns, nd, bits;
-  if (get_int(a, 0, &ns) || get_int(a, 1, &nd) || get_int(a, 2, &bits)) return -1;
+  if (unpack(a, &ns, &nd, &bits)) return -1;
   if (bits != 32 && bits != 64) return fail("idtype bits must be 32 or 64");
   UnitGraph* g = new UnitGraph();
   g->num_src = ns;
@@ -300,56 +455,39 @@ static Registrar r_create("dgl_amd._CAPI_UnitGraphCreate", [](const FfiArgs& a, 
   *rtc = kObjectHandle;
   return 0;
 });
-static Registrar r_free("dgl_amd._CAPI_UnitGraphFree", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  void* h;
-  if (get_handle(a, 0, &h)) return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (g->eord) (void)hipFree(g->eord);
-  if (g->eord_hash) (void)hipFree(g->eord_hash);
+static Registrar r_free("dgl_amd._CAPI_UnitGraphFree", [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph* g;
+  if (unpack(a, &g)) return -1;
   delete g;
-  *rtc = kNull;
   return 0;
 });
-static Registrar r_coo("dgl_amd._CAPI_UnitGraphSetCOO", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return set_format(a, 0);
-});
-static Registrar r_csr("dgl_amd._CAPI_UnitGraphSetCSR", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return set_format(a, 1);
-});
-static Registrar r_csc("dgl_amd._CAPI_UnitGraphSetCSC", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return set_format(a, 2);
-});
-// (g, uint8 NDArray) — scratch the SpMM may use; replaces the reference's AllocWorkspace
-// through the tensoradapter (src/runtime/cuda/cuda_device_api.cc:312-331): the caller
-// allocates with torch so the memory is stream-ordered and cached.
-static Registrar r_ws("dgl_amd._CAPI_UnitGraphSetWorkspace", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  void* h;
-  DGLArray* w;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &w)) return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  g->ws = null_array(w) ? nullptr : data_ptr(w);
-  g->ws_bytes = null_array(w) ? 0 : static_cast<size_t>(w->shape[0]) * ((w->dtype.bits + 7) / 8);
-  g->plan_valid = false;
-  g->split_key = UnitGraph::SplitKey();
-  *rtc = kNull;
-  return 0;
-});
+static Registrar r_coo("dgl_amd._CAPI_UnitGraphSetCOO", [](const FfiArgs& a, DGLValue*, int*) { return set_format(a, 0); });
+static Registrar r_csr("dgl_amd._CAPI_UnitGraphSetCSR", [](const FfiArgs& a, DGLValue*, int*) { return set_format(a, 1); });
+static Registrar r_csc("dgl_amd._CAPI_UnitGraphSetCSC", [](const FfiArgs& a, DGLValue*, int*) { return set_format(a, 2); });
 
-static Registrar r_ws2("dgl_amd._CAPI_UnitGraphSetSoftmaxWorkspace",
-                       [](const FfiArgs& a, DGLValue*, int* rtc) {
-  void* h;
+// (g, NDArray | null): the scratch of the SpMM (softmax = false) or of the merge-path edge softmax.  Replaces the
+// reference's AllocWorkspace through the tensoradapter (src/runtime/cuda/cuda_device_api.cc:312-331): the caller
+// allocates with torch so the memory is stream-ordered and cached.  Whatever plan the old scratch held is gone.
+static int set_workspace(const FfiArgs& a, bool softmax) {
+  UnitGraph* g;
   DGLArray* w;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &w)) return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  g->esm_ws = null_array(w) ? nullptr : data_ptr(w);
-  g->esm_ws_bytes = null_array(w) ? 0 : static_cast<size_t>(w->shape[0]) * ((w->dtype.bits + 7) / 8);
-  g->esm_plan_valid = false;
-  *rtc = kNull;
+  if (unpack(a, &g, &w)) return -1;
+  void* p = ptr_or_null(w);
+  const size_t bytes = null_array(w) ? 0 : static_cast<size_t>(w->shape[0]) * ((w->dtype.bits + 7) / 8);
+  if (softmax) {
+    g->esm_ws = p;
+    g->esm_ws_bytes = bytes;
+    g->esm_plan_valid = false;
+  } else {
+    g->ws = p;
+    g->ws_bytes = bytes;
+    g->plan_valid = false;
+    g->split_key = UnitGraph::SplitKey();
+  }
   return 0;
-});
+}
+static Registrar r_ws("dgl_amd._CAPI_UnitGraphSetWorkspace", [](const FfiArgs& a, DGLValue*, int*) { return set_workspace(a, false); });
+static Registrar r_ws2("dgl_amd._CAPI_UnitGraphSetSoftmaxWorkspace", [](const FfiArgs& a, DGLValue*, int*) { return set_workspace(a, true); });
 
 // ---- sparse._CAPI_DGLKernel* ----------------------------------------------------------
 struct SpmmCall {
@@ -362,30 +500,17 @@ struct SpmmCall {
 };
 
 static int unpack_spmm(const FfiArgs& a, SpmmCall* c) {
-  void* h;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &c->op) || get_str(a, 2, &c->reduce) ||
-      get_array(a, 3, &c->U) || get_array(a, 4, &c->E) || get_array(a, 5, &c->V))
-    return -1;
   c->ArgU = c->ArgE = nullptr;
-  if (a.n > 6 && get_array(a, 6, &c->ArgU)) return -1;
-  if (a.n > 7 && get_array(a, 7, &c->ArgE)) return -1;
-  c->g = static_cast<UnitGraph*>(h);
+  if (unpack(a, &c->g, &c->op, &c->reduce, &c->U, &c->E, &c->V, opt(&c->ArgU), opt(&c->ArgE))) return -1;
   if (null_array(c->V)) return fail("out array is empty");
-  // CheckCtx / CheckContiguous (src/array/kernel.cc:483-497)
-  const DGLArray* arrs[5] = {c->U, c->E, c->V, c->ArgU, c->ArgE};
-  const char* names[5] = {"U_data", "E_data", "out", "Arg_U", "Arg_E"};
-  for (int i = 0; i < 5; ++i) {
-    if (null_array(arrs[i])) continue;
-    if (!on_gpu(arrs[i])) return fail(std::string(names[i]) + " is not on the GPU device of the graph");
-    if (check_contiguous(arrs[i], names[i])) return -1;
-  }
-  if (float_dtype(c->V, &c->dtype)) return -1;
-  for (const DGLArray* t : {c->U, c->E}) {
-    dgla_dtype d;
-    if (null_array(t)) continue;
-    if (float_dtype(t, &d)) return -1;
-    if (d != c->dtype) return fail("operand and output dtypes differ");
-  }
+  // placement of all five under their own names first, then the element types of U and E against the output's
+  if (check_arrays({c->U}, "U_data", "U_data is not on the GPU device of the graph") ||
+      check_arrays({c->E}, "E_data", "E_data is not on the GPU device of the graph") ||
+      check_arrays({c->V}, "out", "out is not on the GPU device of the graph") ||
+      check_arrays({c->ArgU}, "Arg_U", "Arg_U is not on the GPU device of the graph") ||
+      check_arrays({c->ArgE}, "Arg_E", "Arg_E is not on the GPU device of the graph"))
+    return -1;
+  if (float_dtype(c->V, &c->dtype) || check_arrays({c->U, c->E}, "operand", kNotOnGraphGpu, &c->dtype)) return -1;
   to_tensor(c->U, &c->u);
   to_tensor(c->E, &c->e);
   to_tensor(c->V, &c->v);
@@ -396,15 +521,23 @@ static Registrar r_spmm_ws("sparse._CAPI_DGLKernelSpMMWorkspaceBytes",
                            [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
-  *rtc = kObjectInt;
-  ret->v_int64 = 0;
-  if (!c.g->csc.present) return 0;  // COO path needs no scratch
+  if (!c.g->csc.present) return ret_int(ret, rtc, 0);  // COO path needs no scratch
   const dgla_csr csc = csr_of(c.g, c.g->csc, true);
   last_error().clear();
-  ret->v_int64 = static_cast<int64_t>(
-      dgla_spmm_csr_workspace_bytes(c.op, c.reduce, &csc, c.dtype, &c.u.t, &c.e.t, &c.v.t));
-  return last_error().empty() ? 0 : -1;
+  return ret_size(ret, rtc, dgla_spmm_csr_workspace_bytes(c.op, c.reduce, &csc, c.dtype, &c.u.t, &c.e.t, &c.v.t));
 });
+
+// What a dgla_spmm_csr* call on g->ws leaves behind; returns rc.  Two rules, each kept as its callers had it:
+//  - SpMM / SpMMMean pass the `key` of static_split_flags(): the call decides the plan (plan_valid = rc == 0), and
+//    the split copy in the scratch is *key's on success and nobody's on failure;
+//  - SpMMAccumulate, both stacked forms and spmm_unit pass none: the call may have re-laid ITS operand into the
+//    scratch, so the split copy is nobody's either way, and a success only ever raises plan_valid.
+// (SpMMAccumulate also clears both pending static tokens; that stays at its call.)
+static int spmm_done(UnitGraph* g, int rc, const UnitGraph::SplitKey* key = nullptr) {
+  if (key || rc == 0) g->plan_valid = rc == 0;
+  g->split_key = key && rc == 0 ? *key : UnitGraph::SplitKey();
+  return rc;
+}
 
 // Static source features: turns the token announced for this call into DGLA_SPLIT_KEEP /
 // DGLA_SPLIT_VALID and returns what the workspace's split copy will describe afterwards.
@@ -427,14 +560,12 @@ static UnitGraph::SplitKey static_split_flags(UnitGraph* g, const SpmmCall& c, u
 // owner declared static (dgl_amd.static_features); `token` identifies that tensor for as long
 // as it lives.  One-shot: the SpMM consumes it.
 static Registrar r_static("dgl_amd._CAPI_UnitGraphStaticOperand",
-                          [](const FfiArgs& a, DGLValue*, int* rtc) {
-  void* h;
+                          [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph* g;
   int64_t tok, tok_e = 0;
-  if (get_handle(a, 0, &h) || get_int(a, 1, &tok)) return -1;
-  if (a.n > 2 && get_int(a, 2, &tok_e)) return -1;
-  static_cast<UnitGraph*>(h)->pending_static = tok;
-  static_cast<UnitGraph*>(h)->pending_static_e = tok_e;
-  *rtc = kNull;
+  if (unpack(a, &g, &tok, opt(&tok_e))) return -1;
+  g->pending_static = tok;
+  g->pending_static_e = tok_e;
   return 0;
 });
 
@@ -537,11 +668,10 @@ static int64_t eord_default_min_edges() {
 static int64_t g_eord_auto_min_edges = eord_default_min_edges();
 // (n): graphs with at least n edges keep narrow edge operands by content; n < 0 switches it off
 static Registrar r_eord_min("dgl_amd._CAPI_SetAutoEdgeOperandMinEdges",
-                            [](const FfiArgs& a, DGLValue*, int* rtc) {
+                            [](const FfiArgs& a, DGLValue*, int*) {
   int64_t n;
-  if (get_int(a, 0, &n)) return -1;
+  if (unpack(a, &n)) return -1;
   g_eord_auto_min_edges = n < 0 ? INT64_MAX : n;
-  *rtc = kNull;
   return 0;
 });
 constexpr int64_t kEordAutoMaxRowBytes = 16;             // scalar weights .. 4 floats per edge
@@ -656,75 +786,55 @@ static int static_edge_operand(UnitGraph* g, const SpmmCall& c, dgla_csr* csc, d
   return 0;
 }
 
-static Registrar r_spmm("sparse._CAPI_DGLKernelSpMM", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+// The CSC path of SpMM and SpMMMean (`mean` = DGLA_MEAN or 0): static operands resolved, plan and split copy kept.
+// `V` arrives zero-filled (python/dgl/_sparse_ops.py:227) so writing rows instead of accumulating into them gives
+// the same result for the single-relation call.
+static int spmm_csc(const SpmmCall& c, uint32_t mean, void* arg_u, void* arg_e) {
+  UnitGraph* g = c.g;
+  dgla_csr csc = csr_of(g, g->csc, true);
+  uint32_t flags = (plan_ok(g) ? DGLA_PLAN_VALID : 0) | mean;
+  const UnitGraph::SplitKey key = static_split_flags(g, c, &flags);
+  dgla_tensor e_op = c.e.t;
+  if (static_edge_operand(g, c, &csc, &e_op)) return -1;
+  return spmm_done(g, dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &e_op, &c.v.t, arg_u, arg_e, g->ws,
+                                    g->ws_bytes, flags, tls_stream), &key);
+}
+
+static Registrar r_spmm("sparse._CAPI_DGLKernelSpMM", [](const FfiArgs& a, DGLValue*, int*) {
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
-  UnitGraph* g = c.g;
   // aten::SpMM: CSC (in-edge CSR) preferred, else COO (src/array/kernel.cc:26-43)
-  if (g->csc.present) {
-    dgla_csr csc = csr_of(g, g->csc, true);
-    uint32_t flags = plan_ok(g) ? DGLA_PLAN_VALID : 0;
-    const UnitGraph::SplitKey key = static_split_flags(g, c, &flags);
-    dgla_tensor e_op = c.e.t;
-    if (static_edge_operand(g, c, &csc, &e_op)) return -1;
-    // `V` arrives zero-filled (python/dgl/_sparse_ops.py:227) so writing rows instead of
-    // accumulating into them gives the same result for the single-relation call.
-    const int rc = dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &e_op, &c.v.t,
-                                 null_array(c.ArgU) ? nullptr : data_ptr(c.ArgU),
-                                 null_array(c.ArgE) ? nullptr : data_ptr(c.ArgE), g->ws,
-                                 g->ws_bytes, flags, tls_stream);
-    g->plan_valid = rc == 0;
-    g->split_key = rc == 0 ? key : UnitGraph::SplitKey();
-    return rc;
-  }
-  if (g->coo.present) {
-    const dgla_coo coo = coo_of(g);
-    return dgla_spmm_coo(c.op, c.reduce, &coo, c.dtype, &c.u.t, &c.e.t, &c.v.t,
-                         null_array(c.ArgU) ? nullptr : data_ptr(c.ArgU),
-                         null_array(c.ArgE) ? nullptr : data_ptr(c.ArgE), tls_stream);
+  if (c.g->csc.present) return spmm_csc(c, 0, ptr_or_null(c.ArgU), ptr_or_null(c.ArgE));
+  if (c.g->coo.present) {
+    const dgla_coo coo = coo_of(c.g);
+    return dgla_spmm_coo(c.op, c.reduce, &coo, c.dtype, &c.u.t, &c.e.t, &c.v.t, ptr_or_null(c.ArgU),
+                         ptr_or_null(c.ArgE), tls_stream);
   }
   return fail("SpMM only supports CSC and COO formats");  // kernel.cc:41
 });
 
 // reduce "sum" followed by / clamp(in_degree, 1), fused (the `mean` reducer of dgl.ops.gspmm,
 // python/dgl/ops/spmm.py:109-114): same arguments as SpMM, reduce must be "sum".
-static Registrar r_spmm_mean("sparse._CAPI_DGLKernelSpMMMean",
-                             [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_spmm_mean("sparse._CAPI_DGLKernelSpMMMean", [](const FfiArgs& a, DGLValue*, int*) {
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
-  UnitGraph* g = c.g;
-  if (!g->csc.present) return fail("SpMMMean needs the CSC format");
-  dgla_csr csc = csr_of(g, g->csc, true);
-  uint32_t flags = (plan_ok(g) ? DGLA_PLAN_VALID : 0) | DGLA_MEAN;
-  const UnitGraph::SplitKey key = static_split_flags(g, c, &flags);
-  dgla_tensor e_op = c.e.t;
-  if (static_edge_operand(g, c, &csc, &e_op)) return -1;
-  const int rc = dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &e_op, &c.v.t, nullptr,
-                               nullptr, g->ws, g->ws_bytes, flags, tls_stream);
-  g->plan_valid = rc == 0;
-  g->split_key = rc == 0 ? key : UnitGraph::SplitKey();
-  return rc;
+  if (!c.g->csc.present) return fail("SpMMMean needs the CSC format");
+  return spmm_csc(c, DGLA_MEAN, nullptr, nullptr);
 });
 
-// Same as above but `out += result` — what the reference's per-relation loop relies on
+// Same as SpMM but `out += result` — what the reference's per-relation loop relies on
 // (src/array/cuda/spmm_hetero.cu:150-158, spmm.cuh:528-534).
-static Registrar r_spmm_acc("sparse._CAPI_DGLKernelSpMMAccumulate",
-                            [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_spmm_acc("sparse._CAPI_DGLKernelSpMMAccumulate", [](const FfiArgs& a, DGLValue*, int*) {
   SpmmCall c;
   if (unpack_spmm(a, &c)) return -1;
   UnitGraph* g = c.g;
   if (!g->csc.present) return fail("SpMMAccumulate needs the CSC format");  // kernel.cc:212-217
   const dgla_csr csc = csr_of(g, g->csc, true);
   const uint32_t flags = (plan_ok(g) ? DGLA_PLAN_VALID : 0) | DGLA_ACCUMULATE;
-  const int rc = dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &c.e.t, &c.v.t, nullptr,
-                               nullptr, g->ws, g->ws_bytes, flags, tls_stream);
+  const int rc = dgla_spmm_csr(c.op, c.reduce, &csc, c.dtype, &c.u.t, &c.e.t, &c.v.t, nullptr, nullptr, g->ws,
+                               g->ws_bytes, flags, tls_stream);
   g->pending_static = g->pending_static_e = 0;
-  g->split_key = UnitGraph::SplitKey();  // the call may have re-laid ITS operand into the scratch
-  if (rc == 0) g->plan_valid = true;
-  return rc;
+  return spmm_done(g, rc);
 });
 
 // Fused sum over the relations sharing one destination node type (SpMMCsrHetero,
@@ -733,48 +843,41 @@ static Registrar r_spmm_acc("sparse._CAPI_DGLKernelSpMMAccumulate",
 // g_stacked: unit graph whose CSC is the row-wise concatenation of the relations' CSCs
 // (dgl_amd/graph_index.py:stack_csc); U0 / E0: relation 0's operands (shapes); Utab / Etab:
 // int64 arrays of each relation's operand device pointers; rel: uint8 relation id per edge.
-static int spmm_stacked_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool want_bytes) {
-  void* h;
+struct StackedCall {  // what both stacked forms read first
+  UnitGraph* g;
   const char* op;
   DGLArray *U0, *E0, *Ut, *Et, *V, *rel;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_array(a, 2, &U0) || get_array(a, 3, &E0) ||
-      get_array(a, 4, &Ut) || get_array(a, 5, &Et) || get_array(a, 6, &V) || get_array(a, 7, &rel))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return fail("stacked SpMM needs the CSC format");
-  if (null_array(V)) return fail("out array is empty");
   dgla_dtype dt;
-  if (float_dtype(V, &dt)) return -1;
-  for (const DGLArray* t : {U0, E0}) {
-    dgla_dtype d;
-    if (null_array(t)) continue;
-    if (!on_gpu(t)) return fail("operand is not on the GPU device of the graph");
-    if (check_contiguous(t, "operand") || float_dtype(t, &d)) return -1;
-    if (d != dt) return fail("operand and output dtypes differ");
-  }
   TensorArg u, e, v;
-  to_tensor(U0, &u);
-  to_tensor(E0, &e);
-  to_tensor(V, &v);
-  const dgla_csr csc = csr_of(g, g->csc, true);
+  dgla_csr csc;
+};
+// the checks both forms make once their arguments are read
+static int stacked_operands(StackedCall* c) {
+  if (!c->g->csc.present) return fail("stacked SpMM needs the CSC format");
+  if (null_array(c->V)) return fail("out array is empty");
+  if (float_dtype(c->V, &c->dt) ||
+      check_arrays({c->U0, c->E0}, "operand", "operand is not on the GPU device of the graph", &c->dt))
+    return -1;
+  to_tensor(c->U0, &c->u);
+  to_tensor(c->E0, &c->e);
+  to_tensor(c->V, &c->v);
+  c->csc = csr_of(c->g, c->g->csc, true);
+  return 0;
+}
+static const void* const* pointer_table(const DGLArray* t) { return static_cast<const void* const*>(ptr_or_null(t)); }
+
+static int spmm_stacked_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool want_bytes) {
+  StackedCall c;
+  if (unpack(a, &c.g, &c.op, &c.U0, &c.E0, &c.Ut, &c.Et, &c.V, &c.rel) || stacked_operands(&c)) return -1;
   if (want_bytes) {
-    *rtc = kObjectInt;
     last_error().clear();
-    ret->v_int64 = static_cast<int64_t>(
-        dgla_spmm_csr_stacked_workspace_bytes(op, &csc, dt, &u.t, &e.t, &v.t));
-    return last_error().empty() ? 0 : -1;
+    return ret_size(ret, rtc, dgla_spmm_csr_stacked_workspace_bytes(c.op, &c.csc, c.dt, &c.u.t, &c.e.t, &c.v.t));
   }
-  *rtc = kNull;
-  if (null_array(rel) || rel->dtype.bits != 8) return fail("rel must be a uint8 array");
-  const int64_t n_rel = !null_array(Ut) ? Ut->shape[0] : (!null_array(Et) ? Et->shape[0] : 0);
-  const int rc = dgla_spmm_csr_stacked(
-      op, &csc, data_ptr(rel), static_cast<int>(n_rel), dt, &u.t, &e.t,
-      null_array(Ut) ? nullptr : static_cast<const void* const*>(data_ptr(Ut)),
-      null_array(Et) ? nullptr : static_cast<const void* const*>(data_ptr(Et)), &v.t, g->ws,
-      g->ws_bytes, plan_ok(g) ? DGLA_PLAN_VALID : 0, tls_stream);
-  g->split_key = UnitGraph::SplitKey();
-  if (rc == 0) g->plan_valid = true;
-  return rc;
+  if (null_array(c.rel) || c.rel->dtype.bits != 8) return fail("rel must be a uint8 array");
+  const int64_t n_rel = !null_array(c.Ut) ? c.Ut->shape[0] : (!null_array(c.Et) ? c.Et->shape[0] : 0);
+  return spmm_done(c.g, dgla_spmm_csr_stacked(c.op, &c.csc, data_ptr(c.rel), static_cast<int>(n_rel), c.dt, &c.u.t,
+                                              &c.e.t, pointer_table(c.Ut), pointer_table(c.Et), &c.v.t, c.g->ws,
+                                              c.g->ws_bytes, plan_ok(c.g) ? DGLA_PLAN_VALID : 0, tls_stream));
 }
 static Registrar r_stk("sparse._CAPI_DGLKernelSpMMStacked",
                        [](const FfiArgs& a, DGLValue* ret, int* rtc) {
@@ -791,60 +894,31 @@ static Registrar r_stkw("sparse._CAPI_DGLKernelSpMMStackedWorkspaceBytes",
 //   (g_stacked, op, reduce, U0, E0, Utab, Etab, V, rel, types, ArgU, ArgE, ArgU_ntype, ArgE_etype)
 // types: HOST int32 array [2, num_rel] = source node type, edge type of every stacked relation.
 static int spmm_stacked_cmp_ffi(const FfiArgs& a, DGLValue* ret, int* rtc, bool want_bytes) {
-  void* h;
-  const char *op, *reduce;
-  DGLArray *U0, *E0, *Ut, *Et, *V, *rel, *types, *AU, *AE, *UT, *ET;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_str(a, 2, &reduce) || get_array(a, 3, &U0) ||
-      get_array(a, 4, &E0) || get_array(a, 5, &Ut) || get_array(a, 6, &Et) || get_array(a, 7, &V) ||
-      get_array(a, 8, &rel) || get_array(a, 9, &types) || get_array(a, 10, &AU) || get_array(a, 11, &AE) ||
-      get_array(a, 12, &UT) || get_array(a, 13, &ET))
+  StackedCall c;
+  const char* reduce;
+  DGLArray *types, *AU, *AE, *UT, *ET;
+  if (unpack(a, &c.g, &c.op, &reduce, &c.U0, &c.E0, &c.Ut, &c.Et, &c.V, &c.rel, &types, &AU, &AE, &UT, &ET) ||
+      stacked_operands(&c))
     return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return fail("stacked SpMM needs the CSC format");
-  if (null_array(V)) return fail("out array is empty");
-  dgla_dtype dt;
-  if (float_dtype(V, &dt)) return -1;
-  for (const DGLArray* t : {U0, E0}) {
-    dgla_dtype d;
-    if (null_array(t)) continue;
-    if (!on_gpu(t)) return fail("operand is not on the GPU device of the graph");
-    if (check_contiguous(t, "operand") || float_dtype(t, &d)) return -1;
-    if (d != dt) return fail("operand and output dtypes differ");
-  }
-  TensorArg u, e, v;
-  to_tensor(U0, &u);
-  to_tensor(E0, &e);
-  to_tensor(V, &v);
-  const dgla_csr csc = csr_of(g, g->csc, true);
   if (want_bytes) {
-    *rtc = kObjectInt;
     last_error().clear();
-    ret->v_int64 = static_cast<int64_t>(
-        dgla_spmm_csr_stacked_cmp_workspace_bytes(op, reduce, &csc, dt, &u.t, &e.t, &v.t));
-    return last_error().empty() ? 0 : -1;
+    return ret_size(ret, rtc,
+                    dgla_spmm_csr_stacked_cmp_workspace_bytes(c.op, reduce, &c.csc, c.dt, &c.u.t, &c.e.t, &c.v.t));
   }
-  *rtc = kNull;
-  if (null_array(rel) || rel->dtype.bits != 8) return fail("rel must be a uint8 array");
+  if (null_array(c.rel) || c.rel->dtype.bits != 8) return fail("rel must be a uint8 array");
   if (null_array(types) || on_gpu(types) || types->dtype.bits != 32 || types->ndim != 2 || types->shape[0] != 2)
     return fail("types must be a host int32 array of shape [2, num_rel]");
   const int64_t n_rel = types->shape[1];
   for (const DGLArray* t : {AU, AE, UT, ET}) {
-    if (null_array(t)) continue;
-    if (!on_gpu(t)) return fail("arg array is not on the GPU device of the graph");
-    if (check_contiguous(t, "arg array")) return -1;
-    if (t->dtype.bits != g->idbits) return fail("arg arrays must have the graph's id type");
+    if (check_arrays({t}, "arg array", "arg array is not on the GPU device of the graph")) return -1;
+    if (!null_array(t) && t->dtype.bits != c.g->idbits) return fail("arg arrays must have the graph's id type");
   }
   const int32_t* tp = static_cast<const int32_t*>(data_ptr(types));
-  const int rc = dgla_spmm_csr_stacked_cmp(
-      op, reduce, &csc, data_ptr(rel), static_cast<int>(n_rel), tp, tp + n_rel, dt, &u.t, &e.t,
-      null_array(Ut) ? nullptr : static_cast<const void* const*>(data_ptr(Ut)),
-      null_array(Et) ? nullptr : static_cast<const void* const*>(data_ptr(Et)), &v.t,
-      null_array(AU) ? nullptr : data_ptr(AU), null_array(AE) ? nullptr : data_ptr(AE),
-      null_array(UT) ? nullptr : data_ptr(UT), null_array(ET) ? nullptr : data_ptr(ET), g->ws, g->ws_bytes,
-      plan_ok(g) ? DGLA_PLAN_VALID : 0, tls_stream);
-  g->split_key = UnitGraph::SplitKey();
-  if (rc == 0) g->plan_valid = true;
-  return rc;
+  return spmm_done(c.g, dgla_spmm_csr_stacked_cmp(
+                            c.op, reduce, &c.csc, data_ptr(c.rel), static_cast<int>(n_rel), tp, tp + n_rel, c.dt,
+                            &c.u.t, &c.e.t, pointer_table(c.Ut), pointer_table(c.Et), &c.v.t, ptr_or_null(AU),
+                            ptr_or_null(AE), ptr_or_null(UT), ptr_or_null(ET), c.g->ws, c.g->ws_bytes,
+                            plan_ok(c.g) ? DGLA_PLAN_VALID : 0, tls_stream));
 }
 static Registrar r_stkc("sparse._CAPI_DGLKernelSpMMStackedCmp",
                         [](const FfiArgs& a, DGLValue* ret, int* rtc) {
@@ -855,43 +929,35 @@ static Registrar r_stkcw("sparse._CAPI_DGLKernelSpMMStackedCmpWorkspaceBytes",
   return spmm_stacked_cmp_ffi(a, ret, rtc, true);
 });
 
-static Registrar r_sddmm("sparse._CAPI_DGLKernelSDDMM", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
-  const char* op;
-  DGLArray *lhs, *rhs, *out;
-  int64_t lt, rt;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_array(a, 2, &lhs) ||
-      get_array(a, 3, &rhs) || get_array(a, 4, &out) || get_int(a, 5, &lt) || get_int(a, 6, &rt))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (g->num_edges == 0) return 0;
-  if (null_array(out)) return fail("out array is empty");
-  dgla_dtype dt;
-  if (float_dtype(out, &dt)) return -1;
-  for (const DGLArray* t : {lhs, rhs, out}) {
-    if (null_array(t)) continue;
-    dgla_dtype d;
-    if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
-    if (check_contiguous(t, "array") || float_dtype(t, &d)) return -1;
-    if (d != dt) return fail("operand and output dtypes differ");
-  }
+// aten::SDDMM on one unit graph: COO preferred, else CSR (src/array/kernel.cc:230-247)
+static int sddmm_unit(const UnitGraph* g, const char* op, dgla_dtype dt, const DGLArray* lhs, const DGLArray* rhs,
+                      const DGLArray* out, int64_t lt, int64_t rt) {
   TensorArg l, r, o;
   to_tensor(lhs, &l);
   to_tensor(rhs, &r);
   to_tensor(out, &o);
-  // aten::SDDMM: COO preferred, else CSR (src/array/kernel.cc:230-247)
   if (g->coo.present) {
     const dgla_coo coo = coo_of(g);
-    return dgla_sddmm_coo(op, &coo, dt, &l.t, &r.t, &o.t, static_cast<int>(lt),
-                          static_cast<int>(rt), tls_stream);
+    return dgla_sddmm_coo(op, &coo, dt, &l.t, &r.t, &o.t, static_cast<int>(lt), static_cast<int>(rt), tls_stream);
   }
   if (g->csr.present) {
     const dgla_csr csr = csr_of(g, g->csr, false);
-    return dgla_sddmm_csr(op, &csr, dt, &l.t, &r.t, &o.t, static_cast<int>(lt),
-                          static_cast<int>(rt), tls_stream);
+    return dgla_sddmm_csr(op, &csr, dt, &l.t, &r.t, &o.t, static_cast<int>(lt), static_cast<int>(rt), tls_stream);
   }
   return fail("SDDMM only supports CSR and COO formats");  // kernel.cc:245
+}
+
+static Registrar r_sddmm("sparse._CAPI_DGLKernelSDDMM", [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph* g;
+  const char* op;
+  DGLArray *lhs, *rhs, *out;
+  int64_t lt, rt;
+  if (unpack(a, &g, &op, &lhs, &rhs, &out, &lt, &rt)) return -1;
+  if (g->num_edges == 0) return 0;
+  if (null_array(out)) return fail("out array is empty");
+  dgla_dtype dt;
+  if (float_dtype(out, &dt) || check_arrays({lhs, rhs, out}, "array", kNotOnGraphGpu, &dt)) return -1;
+  return sddmm_unit(g, op, dt, lhs, rhs, out, lt, rt);
 });
 
 // Will this call run the merge-path kernels (and so leave a valid plan in g->esm_ws)?
@@ -904,13 +970,10 @@ static bool esm_uses_workspace(const UnitGraph* g, const dgla_csr& csc, dgla_dty
 }
 
 static int edge_softmax_ffi(const FfiArgs& a, bool backward) {
-  void* h;
+  UnitGraph* g;
   const char* op;
   DGLArray *x, *y, *z;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_array(a, 2, &x) || get_array(a, 3, &y) ||
-      get_array(a, 4, &z))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (unpack(a, &g, &op, &x, &y, &z)) return -1;
   if (!g->csc.present) return fail("edge_softmax needs the CSC format");
   const dgla_csr csc = csr_of(g, g->csc, true);
   dgla_dtype dt;
@@ -918,62 +981,41 @@ static int edge_softmax_ffi(const FfiArgs& a, bool backward) {
   to_tensor(x, &tx);
   to_tensor(y, &ty);
   to_tensor(z, &tz);
-  if (!backward) {
-    // (g, op, U(null), E = score, V = out)
-    if (null_array(y) || null_array(z)) return g->num_edges == 0 ? 0 : fail("score / out missing");
-    if (float_dtype(y, &dt)) return -1;
-    const bool merge = esm_uses_workspace(g, csc, dt, y);
-    const int rc = dgla_edge_softmax_forward(&csc, dt, &ty.t, &tz.t, g->esm_ws, g->esm_ws_bytes,
-                                             g->esm_plan_valid ? DGLA_PLAN_VALID : 0, tls_stream);
-    if (rc == 0 && merge) g->esm_plan_valid = true;  // the plan was (re)built in esm_ws
-    return rc;
-  }
-  // (g, op, out, sds, back_out, ufeat(null))
-  if (null_array(x) || null_array(y) || null_array(z))
-    return g->num_edges == 0 ? 0 : fail("out / sds / back missing");
-  if (float_dtype(x, &dt)) return -1;
-  const bool merge = esm_uses_workspace(g, csc, dt, x);
-  const int rc = dgla_edge_softmax_backward(&csc, dt, &tx.t, &ty.t, &tz.t, g->esm_ws,
-                                            g->esm_ws_bytes,
-                                            g->esm_plan_valid ? DGLA_PLAN_VALID : 0, tls_stream);
-  if (rc == 0 && merge) g->esm_plan_valid = true;
+  // forward: (g, op, U(null), E = score, V = out); backward: (g, op, out, sds, back_out, ufeat(null))
+  if ((backward && null_array(x)) || null_array(y) || null_array(z))
+    return g->num_edges == 0 ? 0 : fail(backward ? "out / sds / back missing" : "score / out missing");
+  const DGLArray* first = backward ? x : y;
+  if (float_dtype(first, &dt)) return -1;
+  const bool merge = esm_uses_workspace(g, csc, dt, first);
+  const uint32_t flags = g->esm_plan_valid ? DGLA_PLAN_VALID : 0;
+  const int rc = backward ? dgla_edge_softmax_backward(&csc, dt, &tx.t, &ty.t, &tz.t, g->esm_ws, g->esm_ws_bytes, flags,
+                                                       tls_stream)
+                          : dgla_edge_softmax_forward(&csc, dt, &ty.t, &tz.t, g->esm_ws, g->esm_ws_bytes, flags,
+                                                      tls_stream);
+  if (rc == 0 && merge) g->esm_plan_valid = true;  // the plan was (re)built in esm_ws
   return rc;
 }
 
 // (g, dim, dtype_bits) -> bytes of scratch the merge-path softmax wants (0: none needed)
 static Registrar r_esw("sparse._CAPI_DGLKernelEdge_softmaxWorkspaceBytes",
                        [](const FfiArgs& a, DGLValue* ret, int* rtc) {
-  void* h;
+  UnitGraph* g;
   int64_t dim, bits;
-  if (get_handle(a, 0, &h) || get_int(a, 1, &dim) || get_int(a, 2, &bits)) return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  *rtc = kObjectInt;
-  ret->v_int64 = 0;
-  if (!g->csc.present) return 0;
+  if (unpack(a, &g, &dim, &bits)) return -1;
+  if (!g->csc.present) return ret_int(ret, rtc, 0);
   const dgla_csr csc = csr_of(g, g->csc, true);
-  ret->v_int64 = static_cast<int64_t>(
-      dgla_edge_softmax_workspace_bytes(&csc, bits == 64 ? DGLA_F64 : DGLA_F32, dim));
-  return 0;
+  return ret_int(ret, rtc, static_cast<int64_t>(
+                               dgla_edge_softmax_workspace_bytes(&csc, bits == 64 ? DGLA_F64 : DGLA_F32, dim)));
 });
 static Registrar r_esf("sparse._CAPI_DGLKernelEdge_softmax_forward",
-                       [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return edge_softmax_ffi(a, false);
-});
+                       [](const FfiArgs& a, DGLValue*, int*) { return edge_softmax_ffi(a, false); });
 static Registrar r_esb("sparse._CAPI_DGLKernelEdge_softmax_backward",
-                       [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return edge_softmax_ffi(a, true);
-});
+                       [](const FfiArgs& a, DGLValue*, int*) { return edge_softmax_ffi(a, true); });
 
 // ---- GAT attention block as one operator (csrc/gat_attention.hip) ---------------------------------------------
-static int seg_arrays_ok_fwd(std::initializer_list<const DGLArray*> arrs) {  // CheckCtx / CheckContiguous of the lambdas
-  for (const DGLArray* t : arrs) {
-    if (!t || t->ndim == 0) continue;
-    if (!on_gpu(t)) return fail("array is not on a GPU device");
-    if (check_contiguous(t, "array")) return -1;
-  }
-  return 0;
+// CheckCtx / CheckContiguous of the reference's lambdas (also the segment family's, below)
+static int seg_arrays_ok(std::initializer_list<const DGLArray*> arrs) {
+  return check_arrays(arrs, "array", kNotOnGpu, nullptr, true);
 }
 // a required array that was not given (an EMPTY array — a block side without nodes — is given: it has a shape)
 static bool gat_missing(const DGLArray* t) {
@@ -983,165 +1025,110 @@ static bool gat_missing(const DGLArray* t) {
     if (t->shape[i] == 0) return false;
   return true;
 }
-static void gat_tensor(const DGLArray* a, TensorArg* out) {  // to_tensor that keeps the shape of an empty array
-  out->shape.assign(a->shape, a->shape + a->ndim);
-  out->t.data = a->data ? data_ptr(a) : nullptr;
-  out->t.ndim = a->ndim;
-  out->t.shape = out->shape.data();
-}
-// every array of a call carries the operands' element type; mz is fp32 always
+// every array of a call (that the form takes) carries the operands' element type; mz is fp32 always
 static int gat_same_dtype(const DGLArray* ft, std::initializer_list<const DGLArray*> arrs, const DGLArray* mz) {
   for (const DGLArray* t : arrs)
-    if (t->dtype.code != ft->dtype.code || t->dtype.bits != ft->dtype.bits || t->dtype.lanes != ft->dtype.lanes)
+    if (t && (t->dtype.code != ft->dtype.code || t->dtype.bits != ft->dtype.bits || t->dtype.lanes != ft->dtype.lanes))
       return fail("gat_attention: mixed dtypes (ft, el, er, out, dout and the gradients share one element type)");
   if (mz->dtype.code != 2 || mz->dtype.bits != 32) return fail("gat_attention: mz must be float32");
   return 0;
 }
 // (g, heads, dim) -> bytes of scratch
 static Registrar r_gatw("dgl_amd._CAPI_GATAttentionWorkspaceBytes", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
-  void* h;
+  UnitGraph* g;
   int64_t heads, dim;
-  if (get_handle(a, 0, &h) || get_int(a, 1, &heads) || get_int(a, 2, &dim)) return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  *rtc = kObjectInt;
-  ret->v_int64 = 0;
+  if (unpack(a, &g, &heads, &dim)) return -1;
   if (!g->csc.present) return fail("gat_attention needs the CSC format");
   const dgla_csr csc = csr_of(g, g->csc, true);
-  ret->v_int64 = static_cast<int64_t>(dgla_gat_attention_workspace_bytes(&csc, heads, dim));
-  return 0;
+  return ret_int(ret, rtc, static_cast<int64_t>(dgla_gat_attention_workspace_bytes(&csc, heads, dim)));
 });
-// (g, ft, el, er, slope, out, mz, workspace)
-static Registrar r_gatf("dgl_amd._CAPI_GATAttentionForward", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
+// (g, ft, el, er, slope, out, mz, workspace); the training form (csrc/gat_attention_train.hip) applies attention
+// dropout with probability p, its mask keyed by (seed, edge id, head): (g, ft, el, er, slope, p, seed, out, mz, workspace)
+static int gat_forward_ffi(const FfiArgs& a, bool train) {
+  UnitGraph* g;
   DGLArray *ft, *el, *er, *out, *mz, *ws;
-  double slope;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
-      get_float(a, 4, &slope) || get_array(a, 5, &out) || get_array(a, 6, &mz) || get_array(a, 7, &ws))
+  double slope, p = 0;
+  int64_t seed = 0;
+  if (train ? unpack(a, &g, &ft, &el, &er, &slope, &p, &seed, &out, &mz, &ws)
+            : unpack(a, &g, &ft, &el, &er, &slope, &out, &mz, &ws))
     return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
   if (!g->csc.present) return fail("gat_attention needs the CSC format");
   if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
     return fail("gat_attention: ft / el / er / out / mz are required");
-  if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
+  if (seg_arrays_ok({ft, el, er, out, mz, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
   const dgla_csr csc = csr_of(g, g->csc, true);
   TensorArg tf, tl, tr, to;
-  gat_tensor(ft, &tf);
-  gat_tensor(el, &tl);
-  gat_tensor(er, &tr);
-  gat_tensor(out, &to);
-  return dgla_gat_attention_forward(&csc, dt, &tf.t, &tl.t, &tr.t, static_cast<float>(slope), &to.t, mz->data ? data_ptr(mz) : nullptr,
-                                    null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0], tls_stream);
-});
-// (g, ft, el, er, out, mz, dout, slope, d_ft, d_el, d_er, workspace)
-static Registrar r_gatb("dgl_amd._CAPI_GATAttentionBackward", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
-  DGLArray *ft, *el, *er, *out, *mz, *dout, *dft, *del_, *der, *ws;
-  double slope;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
-      get_array(a, 4, &out) || get_array(a, 5, &mz) || get_array(a, 6, &dout) || get_float(a, 7, &slope) ||
-      get_array(a, 8, &dft) || get_array(a, 9, &del_) || get_array(a, 10, &der) || get_array(a, 11, &ws))
+  shaped_tensor(ft, &tf);
+  shaped_tensor(el, &tl);
+  shaped_tensor(er, &tr);
+  shaped_tensor(out, &to);
+  const Workspace w = workspace_of(ws);
+  const float sl = static_cast<float>(slope);
+  if (!train)
+    return dgla_gat_attention_forward(&csc, dt, &tf.t, &tl.t, &tr.t, sl, &to.t, data_or_null(mz), w.p, w.bytes, tls_stream);
+  return dgla_gat_attention_train_forward(&csc, dt, &tf.t, &tl.t, &tr.t, sl, static_cast<float>(p),
+                                          static_cast<uint64_t>(seed), &to.t, data_or_null(mz), w.p, w.bytes, tls_stream);
+}
+static Registrar r_gatf("dgl_amd._CAPI_GATAttentionForward",
+                        [](const FfiArgs& a, DGLValue*, int*) { return gat_forward_ffi(a, false); });
+static Registrar r_gattf("dgl_amd._CAPI_GATAttentionTrainForward",
+                         [](const FfiArgs& a, DGLValue*, int*) { return gat_forward_ffi(a, true); });
+// (g, ft, el, er, out, mz, dout, slope, d_ft, d_el, d_er, workspace); the training form takes no `out`:
+// (g, ft, el, er, mz, dout, slope, p, seed, d_ft, d_el, d_er, workspace)
+static int gat_backward_ffi(const FfiArgs& a, bool train) {
+  UnitGraph* g;
+  DGLArray *ft, *el, *er, *out = nullptr, *mz, *dout, *dft, *del_, *der, *ws;
+  double slope, p = 0;
+  int64_t seed = 0;
+  if (train ? unpack(a, &g, &ft, &el, &er, &mz, &dout, &slope, &p, &seed, &dft, &del_, &der, &ws)
+            : unpack(a, &g, &ft, &el, &er, &out, &mz, &dout, &slope, &dft, &del_, &der, &ws))
     return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
   if (!g->csc.present || !g->csr.present) return fail("gat_attention backward needs the CSC and the CSR format");
-  for (DGLArray* t : {ft, el, er, out, mz, dout, dft, del_, der})
-    if (gat_missing(t)) return fail("gat_attention backward: every tensor is required");
-  if (seg_arrays_ok_fwd({ft, el, er, out, mz, dout, dft, del_, der, ws})) return -1;
+  bool missing = !train && gat_missing(out);
+  for (DGLArray* t : {ft, el, er, mz, dout, dft, del_, der}) missing = missing || gat_missing(t);
+  if (missing) return fail("gat_attention backward: every tensor is required");
+  if (seg_arrays_ok({ft, el, er, out, mz, dout, dft, del_, der, ws})) return -1;
   dgla_dtype dt;
   if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out, dout, dft, del_, der}, mz)) return -1;
   const dgla_csr csc = csr_of(g, g->csc, true), csr = csr_of(g, g->csr, false);
   TensorArg t[8];
   DGLArray* arrs[8] = {ft, el, er, out, dout, dft, del_, der};
-  for (int i = 0; i < 8; ++i) gat_tensor(arrs[i], &t[i]);
-  return dgla_gat_attention_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, &t[3].t, mz->data ? data_ptr(mz) : nullptr, &t[4].t,
-                                     static_cast<float>(slope), &t[5].t, &t[6].t, &t[7].t,
-                                     null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0], tls_stream);
-});
-// Training form (csrc/gat_attention_train.hip): attention dropout with probability p, mask keyed by (seed, edge id, head)
-// (g, ft, el, er, slope, p, seed, out, mz, workspace)
-static Registrar r_gattf("dgl_amd._CAPI_GATAttentionTrainForward", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
-  DGLArray *ft, *el, *er, *out, *mz, *ws;
-  double slope, p;
-  int64_t seed;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
-      get_float(a, 4, &slope) || get_float(a, 5, &p) || get_int(a, 6, &seed) || get_array(a, 7, &out) ||
-      get_array(a, 8, &mz) || get_array(a, 9, &ws))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present) return fail("gat_attention needs the CSC format");
-  if (gat_missing(ft) || gat_missing(el) || gat_missing(er) || gat_missing(out) || gat_missing(mz))
-    return fail("gat_attention: ft / el / er / out / mz are required");
-  if (seg_arrays_ok_fwd({ft, el, er, out, mz, ws})) return -1;
-  dgla_dtype dt;
-  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, out}, mz)) return -1;
-  const dgla_csr csc = csr_of(g, g->csc, true);
-  TensorArg tf, tl, tr, to;
-  gat_tensor(ft, &tf);
-  gat_tensor(el, &tl);
-  gat_tensor(er, &tr);
-  gat_tensor(out, &to);
-  return dgla_gat_attention_train_forward(&csc, dt, &tf.t, &tl.t, &tr.t, static_cast<float>(slope), static_cast<float>(p),
-                                          static_cast<uint64_t>(seed), &to.t, mz->data ? data_ptr(mz) : nullptr,
-                                          null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0],
-                                          tls_stream);
-});
-// (g, ft, el, er, mz, dout, slope, p, seed, d_ft, d_el, d_er, workspace)
-static Registrar r_gattb("dgl_amd._CAPI_GATAttentionTrainBackward", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
-  DGLArray *ft, *el, *er, *mz, *dout, *dft, *del_, *der, *ws;
-  double slope, p;
-  int64_t seed;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &ft) || get_array(a, 2, &el) || get_array(a, 3, &er) ||
-      get_array(a, 4, &mz) || get_array(a, 5, &dout) || get_float(a, 6, &slope) || get_float(a, 7, &p) ||
-      get_int(a, 8, &seed) || get_array(a, 9, &dft) || get_array(a, 10, &del_) || get_array(a, 11, &der) ||
-      get_array(a, 12, &ws))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
-  if (!g->csc.present || !g->csr.present) return fail("gat_attention backward needs the CSC and the CSR format");
-  for (DGLArray* t : {ft, el, er, mz, dout, dft, del_, der})
-    if (gat_missing(t)) return fail("gat_attention backward: every tensor is required");
-  if (seg_arrays_ok_fwd({ft, el, er, mz, dout, dft, del_, der, ws})) return -1;
-  dgla_dtype dt;
-  if (float_dtype(ft, &dt) || gat_same_dtype(ft, {el, er, dout, dft, del_, der}, mz)) return -1;
-  const dgla_csr csc = csr_of(g, g->csc, true), csr = csr_of(g, g->csr, false);
-  TensorArg t[7];
-  DGLArray* arrs[7] = {ft, el, er, dout, dft, del_, der};
-  for (int i = 0; i < 7; ++i) gat_tensor(arrs[i], &t[i]);
-  return dgla_gat_attention_train_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, mz->data ? data_ptr(mz) : nullptr,
-                                           &t[3].t, static_cast<float>(slope), static_cast<float>(p),
-                                           static_cast<uint64_t>(seed), &t[4].t, &t[5].t, &t[6].t,
-                                           null_array(ws) ? nullptr : data_ptr(ws), null_array(ws) ? 0 : ws->shape[0],
-                                           tls_stream);
-});
+  for (int i = 0; i < 8; ++i)
+    if (arrs[i]) shaped_tensor(arrs[i], &t[i]);
+  const Workspace w = workspace_of(ws);
+  const float sl = static_cast<float>(slope);
+  if (!train)
+    return dgla_gat_attention_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, &t[3].t, data_or_null(mz), &t[4].t, sl,
+                                       &t[5].t, &t[6].t, &t[7].t, w.p, w.bytes, tls_stream);
+  return dgla_gat_attention_train_backward(&csc, &csr, dt, &t[0].t, &t[1].t, &t[2].t, data_or_null(mz), &t[4].t, sl,
+                                           static_cast<float>(p), static_cast<uint64_t>(seed), &t[5].t, &t[6].t,
+                                           &t[7].t, w.p, w.bytes, tls_stream);
+}
+static Registrar r_gatb("dgl_amd._CAPI_GATAttentionBackward",
+                        [](const FfiArgs& a, DGLValue*, int*) { return gat_backward_ffi(a, false); });
+static Registrar r_gattb("dgl_amd._CAPI_GATAttentionTrainBackward",
+                         [](const FfiArgs& a, DGLValue*, int*) { return gat_backward_ffi(a, true); });
 // (g, el, er, mz, slope, p, seed, attn): the post-dropout attention weights, (E, H, 1) in edge-id order
-static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
+static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph* g;
   DGLArray *el, *er, *mz, *attn;
   double slope, p;
   int64_t seed;
-  if (get_handle(a, 0, &h) || get_array(a, 1, &el) || get_array(a, 2, &er) || get_array(a, 3, &mz) ||
-      get_float(a, 4, &slope) || get_float(a, 5, &p) || get_int(a, 6, &seed) || get_array(a, 7, &attn))
-    return -1;
-  UnitGraph* g = static_cast<UnitGraph*>(h);
+  if (unpack(a, &g, &el, &er, &mz, &slope, &p, &seed, &attn)) return -1;
   if (!g->csc.present) return fail("gat_attention needs the CSC format");
   if (gat_missing(el) || gat_missing(er) || gat_missing(mz) || gat_missing(attn))
     return fail("gat_attention_weights: el / er / mz / attn are required");
-  if (seg_arrays_ok_fwd({el, er, mz, attn})) return -1;
+  if (seg_arrays_ok({el, er, mz, attn})) return -1;
   dgla_dtype dt;
   if (float_dtype(el, &dt) || gat_same_dtype(el, {er, attn}, mz)) return -1;
   const dgla_csr csc = csr_of(g, g->csc, true);
   TensorArg tl, tr, ta;
-  gat_tensor(el, &tl);
-  gat_tensor(er, &tr);
-  gat_tensor(attn, &ta);
-  return dgla_gat_attention_weights(&csc, dt, &tl.t, &tr.t, mz->data ? data_ptr(mz) : nullptr, static_cast<float>(slope),
+  shaped_tensor(el, &tl);
+  shaped_tensor(er, &tr);
+  shaped_tensor(attn, &ta);
+  return dgla_gat_attention_weights(&csc, dt, &tl.t, &tr.t, data_or_null(mz), static_cast<float>(slope),
                                     static_cast<float>(p), static_cast<uint64_t>(seed), &ta.t, tls_stream);
 });
 
@@ -1150,177 +1137,150 @@ static Registrar r_gatwt("dgl_amd._CAPI_GATAttentionWeights", [](const FfiArgs& 
 // the product and the sum are a Count and a Fill over caller-allocated arrays.  Operands are unit-graph handles with
 // their CSR (rows = source nodes) registered — A->GetCSRMatrix(0) of kernel.cc:739-740 —, CSRMask's second operand
 // with its COO (kernel.cc:788).
-static int spgemm_csr(const FfiArgs& a, int i, dgla_csr* out) {
-  void* h;
-  if (get_handle(a, i, &h)) return -1;
-  if (!h || *static_cast<const uint32_t*>(h) != kMagicUnit) return fail("argument " + std::to_string(i) + ": not a unit graph");
-  const UnitGraph* g = static_cast<const UnitGraph*>(h);
+static int spgemm_csr(const UnitGraph* g, dgla_csr* out) {
   if (!g->csr.present) return fail("csr_mm / csr_sum / csr_mask need the CSR format of their operands");
   *out = csr_of(g, g->csr, false);
   return 0;
 }
-static int spgemm_ids(const DGLArray* t, int bits, const char* name) {
+static int spgemm_required(const DGLArray* t, const char* name) {  // an empty array is given: it has a shape
   if (!t || t->ndim == 0) return fail(std::string(name) + " is required");
-  if (!on_gpu(t)) return fail("array is not on a GPU device");
-  if (check_contiguous(t, name)) return -1;
+  return check_arrays({t}, name, kNotOnGpu, nullptr, true);
+}
+static int spgemm_ids(const DGLArray* t, int bits, const char* name) {
   int b;
-  if (idbits_of(t, &b)) return -1;
+  if (spgemm_required(t, name) || idbits_of(t, &b)) return -1;
   if (b != bits) return fail(std::string(name) + " must have the id type of the operands");
+  return 0;
+}
+static int spgemm_indptr(const DGLArray* ip, const dgla_csr& A) {
+  if (ip->shape[0] != A.num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
   return 0;
 }
 // weights: 1-D (or (n, 1)), one per edge
 static int spgemm_weights(const DGLArray* t, int64_t nnz, dgla_dtype* dt, const char* name) {
-  if (!t || t->ndim == 0) return fail(std::string(name) + " is required");
-  if (!on_gpu(t)) return fail("array is not on a GPU device");
-  if (check_contiguous(t, name) || float_dtype(t, dt)) return -1;
+  if (spgemm_required(t, name) || float_dtype(t, dt)) return -1;
   if (t->ndim > 2 || (t->ndim == 2 && t->shape[1] != 1)) return fail(std::string(name) + " must be one scalar per edge (1-D)");
   if (t->shape[0] != nnz)
     return fail(std::string(name) + " has " + std::to_string(t->shape[0]) + " entries for " + std::to_string(nnz) + " edges");
   return 0;
 }
-static void spgemm_ws(const DGLArray* ws, void** p, size_t* bytes) {
-  *p = null_array(ws) ? nullptr : data_ptr(ws);
-  *bytes = null_array(ws) ? 0 : static_cast<size_t>(ws->shape[0]);
-}
 // (gA, gB, c_indptr, workspace | null) -> nnz(C)
 static Registrar r_csrmmc("dgl_amd._CAPI_CSRMMCount", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
+  UnitGraph *ga, *gb;
   dgla_csr A, B;
   DGLArray *ip, *ws;
-  if (spgemm_csr(a, 0, &A) || spgemm_csr(a, 1, &B) || get_array(a, 2, &ip) || get_array(a, 3, &ws)) return -1;
-  if (spgemm_ids(ip, A.idtype_bits, "c_indptr")) return -1;
-  if (ip->shape[0] != A.num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
-  void* w;
-  size_t wb;
-  spgemm_ws(ws, &w, &wb);
+  if (unpack(a, &ga, &gb, &ip, &ws) || spgemm_csr(ga, &A) || spgemm_csr(gb, &B)) return -1;
+  if (spgemm_ids(ip, A.idtype_bits, "c_indptr") || spgemm_indptr(ip, A)) return -1;
+  const Workspace w = workspace_of(ws);
   int64_t nnz = 0;
-  if (dgla_csr_mm_count(&A, &B, data_ptr(ip), &nnz, w, wb, tls_stream)) return -1;
-  *rtc = kObjectInt;
-  ret->v_int64 = nnz;
-  return 0;
+  if (dgla_csr_mm_count(&A, &B, data_ptr(ip), &nnz, w.p, w.bytes, tls_stream)) return -1;
+  return ret_int(ret, rtc, nnz);
 });
 // (gA, a_w, gB, b_w, c_indptr, c_indices, c_w, workspace | null)
-static Registrar r_csrmmf("dgl_amd._CAPI_CSRMMFill", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_csrmmf("dgl_amd._CAPI_CSRMMFill", [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph *ga, *gb;
   dgla_csr A, B;
   DGLArray *aw, *bw, *ip, *ix, *cw, *ws;
-  if (spgemm_csr(a, 0, &A) || get_array(a, 1, &aw) || spgemm_csr(a, 2, &B) || get_array(a, 3, &bw) || get_array(a, 4, &ip) ||
-      get_array(a, 5, &ix) || get_array(a, 6, &cw) || get_array(a, 7, &ws))
-    return -1;
+  if (unpack(a, &ga, &aw, &gb, &bw, &ip, &ix, &cw, &ws) || spgemm_csr(ga, &A) || spgemm_csr(gb, &B)) return -1;
   dgla_dtype dt, dtb, dtc;
   if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(bw, B.nnz, &dtb, "b_weights")) return -1;
   if (spgemm_ids(ip, A.idtype_bits, "c_indptr") || spgemm_ids(ix, A.idtype_bits, "c_indices")) return -1;
   if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
   if (dt != dtb || dt != dtc) return fail("csr_mm: the weights of a, b and c must share one element type");
-  if (ip->shape[0] != A.num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
-  void* w;
-  size_t wb;
-  spgemm_ws(ws, &w, &wb);
-  return dgla_csr_mm_fill(&A, dt, aw->data ? data_ptr(aw) : nullptr, &B, bw->data ? data_ptr(bw) : nullptr, data_ptr(ip),
-                          ix->data ? data_ptr(ix) : nullptr, cw->data ? data_ptr(cw) : nullptr, w, wb, tls_stream);
+  if (spgemm_indptr(ip, A)) return -1;
+  const Workspace w = workspace_of(ws);
+  return dgla_csr_mm_fill(&A, dt, data_or_null(aw), &B, data_or_null(bw), data_ptr(ip), data_or_null(ix),
+                          data_or_null(cw), w.p, w.bytes, tls_stream);
 });
+// (n, g_0 .. g_{n-1}, ...): the operand list CSRSumCount and CSRSumFill open with
+struct CsrSumOperands {
+  int64_t n;
+  std::vector<dgla_csr> ops;
+  std::vector<const dgla_csr*> ptrs;
+};
+static int csr_sum_operands(const FfiArgs& a, CsrSumOperands* s) {
+  if (get_int(a, 0, &s->n)) return -1;
+  if (s->n < 1 || s->n > 4096) return fail("csr_sum: the number of operands must be in [1, 4096]");
+  s->ops.resize(s->n);
+  s->ptrs.resize(s->n);
+  for (int k = 0; k < s->n; ++k) {
+    UnitGraph* g;
+    if (unit_graph_at(a, 1 + k, &g) || spgemm_csr(g, &s->ops[k])) return -1;
+    s->ptrs[k] = &s->ops[k];
+  }
+  return 0;
+}
 // (n, g_0 .. g_{n-1}, c_indptr, workspace | null) -> nnz(C)
 static Registrar r_csrsumc("dgl_amd._CAPI_CSRSumCount", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
-  int64_t n;
-  if (get_int(a, 0, &n)) return -1;
-  if (n < 1 || n > 4096) return fail("csr_sum: the number of operands must be in [1, 4096]");
-  std::vector<dgla_csr> ops(n);
-  std::vector<const dgla_csr*> ptrs(n);
-  for (int k = 0; k < n; ++k) {
-    if (spgemm_csr(a, 1 + k, &ops[k])) return -1;
-    ptrs[k] = &ops[k];
-  }
+  CsrSumOperands s;
   DGLArray *ip, *ws;
-  if (get_array(a, 1 + n, &ip) || get_array(a, 2 + n, &ws)) return -1;
-  if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr")) return -1;
-  if (ip->shape[0] != ops[0].num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
-  void* w;
-  size_t wb;
-  spgemm_ws(ws, &w, &wb);
+  if (csr_sum_operands(a, &s) || get_array(a, 1 + s.n, &ip) || get_array(a, 2 + s.n, &ws)) return -1;
+  if (spgemm_ids(ip, s.ops[0].idtype_bits, "c_indptr") || spgemm_indptr(ip, s.ops[0])) return -1;
+  const Workspace w = workspace_of(ws);
   int64_t nnz = 0;
-  if (dgla_csr_sum_count(ptrs.data(), static_cast<int>(n), data_ptr(ip), &nnz, w, wb, tls_stream)) return -1;
-  *rtc = kObjectInt;
-  ret->v_int64 = nnz;
-  return 0;
+  if (dgla_csr_sum_count(s.ptrs.data(), static_cast<int>(s.n), data_ptr(ip), &nnz, w.p, w.bytes, tls_stream)) return -1;
+  return ret_int(ret, rtc, nnz);
 });
 // (n, g_0 .. g_{n-1}, w_0 .. w_{n-1}, c_indptr, c_indices, c_w, workspace | null)
-static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  int64_t n;
-  if (get_int(a, 0, &n)) return -1;
-  if (n < 1 || n > 4096) return fail("csr_sum: the number of operands must be in [1, 4096]");
-  std::vector<dgla_csr> ops(n);
-  std::vector<const dgla_csr*> ptrs(n);
+static Registrar r_csrsumf("dgl_amd._CAPI_CSRSumFill", [](const FfiArgs& a, DGLValue*, int*) {
+  CsrSumOperands s;
+  if (csr_sum_operands(a, &s)) return -1;
+  const int64_t n = s.n;
   std::vector<const void*> wts(n);
   dgla_dtype dt = DGLA_F32;
   for (int k = 0; k < n; ++k) {
-    if (spgemm_csr(a, 1 + k, &ops[k])) return -1;
-    ptrs[k] = &ops[k];
-  }
-  for (int k = 0; k < n; ++k) {
     DGLArray* t;
     dgla_dtype dk;
-    if (get_array(a, 1 + n + k, &t) || spgemm_weights(t, ops[k].nnz, &dk, "weights")) return -1;
+    if (get_array(a, 1 + n + k, &t) || spgemm_weights(t, s.ops[k].nnz, &dk, "weights")) return -1;
     if (k > 0 && dk != dt) return fail("csr_sum: the weights must share one element type");
     dt = dk;
-    wts[k] = t->data ? data_ptr(t) : nullptr;
+    wts[k] = data_or_null(t);
   }
   DGLArray *ip, *ix, *cw, *ws;
   if (get_array(a, 1 + 2 * n, &ip) || get_array(a, 2 + 2 * n, &ix) || get_array(a, 3 + 2 * n, &cw) || get_array(a, 4 + 2 * n, &ws))
     return -1;
   dgla_dtype dtc;
-  if (spgemm_ids(ip, ops[0].idtype_bits, "c_indptr") || spgemm_ids(ix, ops[0].idtype_bits, "c_indices")) return -1;
+  if (spgemm_ids(ip, s.ops[0].idtype_bits, "c_indptr") || spgemm_ids(ix, s.ops[0].idtype_bits, "c_indices")) return -1;
   if (spgemm_weights(cw, ix->shape[0], &dtc, "c_weights")) return -1;
   if (dtc != dt) return fail("csr_sum: the weights must share one element type");
-  if (ip->shape[0] != ops[0].num_rows + 1) return fail("c_indptr must have num_rows + 1 entries");
-  void* w;
-  size_t wb;
-  spgemm_ws(ws, &w, &wb);
-  return dgla_csr_sum_fill(ptrs.data(), static_cast<int>(n), dt, wts.data(), data_ptr(ip), ix->data ? data_ptr(ix) : nullptr,
-                           cw->data ? data_ptr(cw) : nullptr, w, wb, tls_stream);
+  if (spgemm_indptr(ip, s.ops[0])) return -1;
+  const Workspace w = workspace_of(ws);
+  return dgla_csr_sum_fill(s.ptrs.data(), static_cast<int>(n), dt, wts.data(), data_ptr(ip), data_or_null(ix),
+                           data_or_null(cw), w.p, w.bytes, tls_stream);
 });
 // (gA, a_w, gB, out): out[e] = A[row_B[e], col_B[e]] or 0, e over B's edge ids
-static Registrar r_csrmask("dgl_amd._CAPI_CSRMask", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_csrmask("dgl_amd._CAPI_CSRMask", [](const FfiArgs& a, DGLValue*, int*) {
+  UnitGraph *ga, *gb;
   dgla_csr A;
-  void* hb;
   DGLArray *aw, *out;
-  if (spgemm_csr(a, 0, &A) || get_array(a, 1, &aw) || get_handle(a, 2, &hb) || get_array(a, 3, &out)) return -1;
-  if (!hb || *static_cast<const uint32_t*>(hb) != kMagicUnit) return fail("argument 2: not a unit graph");
-  const UnitGraph* gb = static_cast<const UnitGraph*>(hb);
+  if (unpack(a, &ga, &aw, &gb, &out) || spgemm_csr(ga, &A)) return -1;
   if (!gb->coo.present) return fail("csr_mask needs the COO format of its second operand");
   const dgla_coo B = coo_of(gb);
   dgla_dtype dt, dto;
   if (spgemm_weights(aw, A.nnz, &dt, "a_weights") || spgemm_weights(out, B.nnz, &dto, "out")) return -1;
   if (dt != dto) return fail("csr_mask: a_weights and out must share one element type");
-  return dgla_csr_mask(&A, dt, aw->data ? data_ptr(aw) : nullptr, &B, out->data ? data_ptr(out) : nullptr, tls_stream);
+  return dgla_csr_mask(&A, dt, data_or_null(aw), &B, data_or_null(out), tls_stream);
 });
 
 // ---- segment reduce family (src/array/kernel.cc:658-708) -------------------------------------
-static int seg_arrays_ok(std::initializer_list<const DGLArray*> arrs) {
-  for (const DGLArray* t : arrs) {
-    if (!t || t->ndim == 0) continue;
-    if (!on_gpu(t)) return fail("array is not on a GPU device");
-    if (check_contiguous(t, "array")) return -1;
-  }
-  return 0;
+// CheckCtx / CheckContiguous as the reference lambda; dtype rules of SegmentReduceDispatch
+static int seg_operands(const DGLArray* feat, const DGLArray* index, const DGLArray* out, const DGLArray* arg,
+                        dgla_dtype* dt, int* bits) {
+  dgla_dtype df;
+  if (seg_arrays_ok({feat, index, out, arg})) return -1;
+  if (float_dtype(out, dt) || float_dtype(feat, &df) || idbits_of(index, bits)) return -1;
+  return *dt != df ? fail("feat and out dtypes differ") : 0;
 }
 
 // (str op, NDArray feat, NDArray offsets, NDArray out, NDArray arg)
-static Registrar r_segred("sparse._CAPI_DGLKernelSegmentReduce",
-                          [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_segred("sparse._CAPI_DGLKernelSegmentReduce", [](const FfiArgs& a, DGLValue*, int*) {
   const char* op;
   DGLArray *feat, *offsets, *out, *arg;
-  if (get_str(a, 0, &op) || get_array(a, 1, &feat) || get_array(a, 2, &offsets) ||
-      get_array(a, 3, &out) || get_array(a, 4, &arg))
-    return -1;
+  if (unpack(a, &op, &feat, &offsets, &out, &arg)) return -1;
   if (!feat || !offsets || !out || out->ndim == 0) return fail("feat / offsets / out is required");
-  if (seg_arrays_ok({feat, offsets, out, arg})) return -1;
-  // CheckCtx / CheckContiguous as the reference lambda; dtype rules of SegmentReduceDispatch
-  dgla_dtype dt, df;
+  dgla_dtype dt;
   int bits;
-  if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(offsets, &bits)) return -1;
-  if (dt != df) return fail("feat and out dtypes differ");
+  if (seg_operands(feat, offsets, out, arg, &dt, &bits)) return -1;
   if (offsets->ndim != 1 || offsets->shape[0] != out->shape[0] + 1)
     return fail("offsets must have out.shape[0] + 1 entries");
   const bool cmp = strcmp(op, "sum") != 0;
@@ -1331,28 +1291,22 @@ static Registrar r_segred("sparse._CAPI_DGLKernelSegmentReduce",
       return fail("arg dtype must equal the offsets dtype");
   }
   TensorArg tf, to;
-  tf.shape.assign(feat->shape, feat->shape + feat->ndim);
-  tf.t = dgla_tensor{data_ptr(feat), feat->ndim, tf.shape.data()};
-  to.shape.assign(out->shape, out->shape + out->ndim);
-  to.t = dgla_tensor{data_ptr(out), out->ndim, to.shape.data()};
-  return dgla_segment_reduce(op, bits, dt, &tf.t, data_ptr(offsets), out->shape[0], &to.t,
-                             null_array(arg) ? nullptr : data_ptr(arg), nullptr, 0, 0, tls_stream);
+  shaped_tensor(feat, &tf);
+  shaped_tensor(out, &to);
+  return dgla_segment_reduce(op, bits, dt, &tf.t, data_ptr(offsets), out->shape[0], &to.t, ptr_or_null(arg), nullptr,
+                             0, 0, tls_stream);
 });
 
 // (NDArray feat, NDArray idx, NDArray out)
-static Registrar r_scatter("sparse._CAPI_DGLKernelScatterAdd",
-                           [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_scatter("sparse._CAPI_DGLKernelScatterAdd", [](const FfiArgs& a, DGLValue*, int*) {
   DGLArray *feat, *idx, *out;
-  if (get_array(a, 0, &feat) || get_array(a, 1, &idx) || get_array(a, 2, &out)) return -1;
+  if (unpack(a, &feat, &idx, &out)) return -1;
   if (!feat || !idx || !out) return fail("feat / idx / out is required");
   if (null_array(feat)) return 0;
   if (null_array(out)) return fail("out is empty but feat is not");
-  if (seg_arrays_ok({feat, idx, out})) return -1;
-  dgla_dtype dt, df;
+  dgla_dtype dt;
   int bits;
-  if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(idx, &bits)) return -1;
-  if (dt != df) return fail("feat and out dtypes differ");
+  if (seg_operands(feat, idx, out, nullptr, &dt, &bits)) return -1;
   if (idx->ndim != 1 || idx->shape[0] != feat->shape[0])
     return fail("idx must have one entry per row of feat");
   TensorArg tf, to;
@@ -1362,18 +1316,14 @@ static Registrar r_scatter("sparse._CAPI_DGLKernelScatterAdd",
 });
 
 // (NDArray feat, NDArray arg, NDArray out)
-static Registrar r_bwdseg("sparse._CAPI_DGLKernelBwdSegmentCmp",
-                          [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_bwdseg("sparse._CAPI_DGLKernelBwdSegmentCmp", [](const FfiArgs& a, DGLValue*, int*) {
   DGLArray *feat, *arg, *out;
-  if (get_array(a, 0, &feat) || get_array(a, 1, &arg) || get_array(a, 2, &out)) return -1;
+  if (unpack(a, &feat, &arg, &out)) return -1;
   if (!feat || !arg || !out) return fail("feat / arg / out is required");
   if (null_array(feat) || null_array(out)) return 0;  // nothing to scatter / nowhere to write
-  if (seg_arrays_ok({feat, arg, out})) return -1;
-  dgla_dtype dt, df;
+  dgla_dtype dt;
   int bits;
-  if (float_dtype(out, &dt) || float_dtype(feat, &df) || idbits_of(arg, &bits)) return -1;
-  if (dt != df) return fail("feat and out dtypes differ");
+  if (seg_operands(feat, arg, out, nullptr, &dt, &bits)) return -1;
   TensorArg tf, to;
   to_tensor(feat, &tf);
   to_tensor(out, &to);
@@ -1384,19 +1334,15 @@ static Registrar r_bwdseg("sparse._CAPI_DGLKernelBwdSegmentCmp",
 static int mm_dims(const DGLArray* t, int want_ndim, const char* name) {
   if (!t || t->ndim != want_ndim)
     return fail(std::string(name) + " must be a " + std::to_string(want_ndim) + "-D array");
-  if (!on_gpu(t)) return fail(std::string(name) + " is not on a GPU device");
-  return check_contiguous(t, name);
+  if (!on_gpu(t)) return fail(std::string(name) + " is not on a GPU device");  // this family's sentence names the array
+  return check_arrays({t}, name, kNotOnGpu, nullptr, true);
 }
 
 // (NDArray A, NDArray B, NDArray C, NDArray seglen_A, bool A_trans, bool B_trans)
-static Registrar r_segmm("sparse._CAPI_DGLKernelSEGMENTMM",
-                         [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_segmm("sparse._CAPI_DGLKernelSEGMENTMM", [](const FfiArgs& a, DGLValue*, int*) {
   DGLArray *A, *B, *C, *seglen;
   int64_t a_trans, b_trans;
-  if (get_array(a, 0, &A) || get_array(a, 1, &B) || get_array(a, 2, &C) ||
-      get_array(a, 3, &seglen) || get_int(a, 4, &a_trans) || get_int(a, 5, &b_trans))
-    return -1;
+  if (unpack(a, &A, &B, &C, &seglen, &a_trans, &b_trans)) return -1;
   if (mm_dims(A, 2, "A") || mm_dims(B, 3, "B") || mm_dims(C, 2, "C")) return -1;
   if (!seglen || seglen->ndim != 1) return fail("seglen_A must be a 1-D array");
   if (a_trans) return fail("segment_mm: A_trans is not supported (the reference never sets it)");
@@ -1418,12 +1364,9 @@ static Registrar r_segmm("sparse._CAPI_DGLKernelSEGMENTMM",
 });
 
 // (NDArray A, NDArray dC, NDArray dB, NDArray seglen)
-static Registrar r_segmm_b("sparse._CAPI_DGLKernelSEGMENTMMBackwardB",
-                           [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
+static Registrar r_segmm_b("sparse._CAPI_DGLKernelSEGMENTMMBackwardB", [](const FfiArgs& a, DGLValue*, int*) {
   DGLArray *A, *dC, *dB, *seglen;
-  if (get_array(a, 0, &A) || get_array(a, 1, &dC) || get_array(a, 2, &dB) || get_array(a, 3, &seglen))
-    return -1;
+  if (unpack(a, &A, &dC, &dB, &seglen)) return -1;
   if (mm_dims(A, 2, "A") || mm_dims(dC, 2, "dC") || mm_dims(dB, 3, "dB")) return -1;
   if (!seglen || seglen->ndim != 1) return fail("seglen must be a 1-D array");
   dgla_dtype dt, d2, d3;
@@ -1441,10 +1384,7 @@ static Registrar r_segmm_b("sparse._CAPI_DGLKernelSEGMENTMMBackwardB",
 
 static int gather_mm_ffi(const FfiArgs& a, bool scatter) {
   DGLArray *A, *B, *C, *ia, *ib, *ic = nullptr;
-  if (get_array(a, 0, &A) || get_array(a, 1, &B) || get_array(a, 2, &C) || get_array(a, 3, &ia) ||
-      get_array(a, 4, &ib))
-    return -1;
-  if (scatter && get_array(a, 5, &ic)) return -1;
+  if (scatter ? unpack(a, &A, &B, &C, &ia, &ib, &ic) : unpack(a, &A, &B, &C, &ia, &ib)) return -1;
   if (mm_dims(A, 2, "A") || mm_dims(B, 3, "B") || mm_dims(C, 2, "C")) return -1;
   dgla_dtype dt, d2, d3;
   if (float_dtype(A, &dt) || float_dtype(B, &d2) || float_dtype(C, &d3)) return -1;
@@ -1454,8 +1394,7 @@ static int gather_mm_ffi(const FfiArgs& a, bool scatter) {
   for (DGLArray* t : {ia, ib, ic}) {
     if (null_array(t)) continue;
     int b;
-    if (!on_gpu(t)) return fail("index arrays must be on the GPU");
-    if (idbits_of(t, &b)) return -1;
+    if (check_arrays({t}, "index arrays", "index arrays must be on the GPU") || idbits_of(t, &b)) return -1;
     if (bits && b != bits) return fail("index arrays must share one dtype");
     if (rows >= 0 && t->shape[0] != rows) return fail("index arrays must have the same length");
     bits = b;
@@ -1464,48 +1403,18 @@ static int gather_mm_ffi(const FfiArgs& a, bool scatter) {
   if (rows < 0) return fail("gather_mm needs at least one index array");
   if (A->shape[1] != B->shape[1]) return fail("gather_mm expects A.shape[1] == B.shape[1]");
   if (C->shape[1] != B->shape[2]) return fail("gather_mm expects C.shape[1] == B.shape[2]");
-  auto ptr = [](DGLArray* t) { return null_array(t) ? nullptr : data_ptr(t); };
-  return dgla_gather_mm(bits, dt, data_ptr(A), data_ptr(B), data_ptr(C), ptr(ia), ptr(ib), ptr(ic),
-                        rows, A->shape[1], B->shape[2], tls_stream);
+  return dgla_gather_mm(bits, dt, data_ptr(A), data_ptr(B), data_ptr(C), ptr_or_null(ia), ptr_or_null(ib),
+                        ptr_or_null(ic), rows, A->shape[1], B->shape[2], tls_stream);
 }
 // (NDArray A, NDArray B, NDArray C, NDArray idx_a, NDArray idx_b)
-static Registrar r_gmm("sparse._CAPI_DGLKernelGATHERMM", [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return gather_mm_ffi(a, false);
-});
+static Registrar r_gmm("sparse._CAPI_DGLKernelGATHERMM",
+                       [](const FfiArgs& a, DGLValue*, int*) { return gather_mm_ffi(a, false); });
 // (NDArray A, NDArray B, NDArray C, NDArray idx_a, NDArray idx_b, NDArray idx_c), B 3-D
 static Registrar r_gmms("sparse._CAPI_DGLKernelGATHERMMSCATTER",
-                        [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  return gather_mm_ffi(a, true);
-});
+                        [](const FfiArgs& a, DGLValue*, int*) { return gather_mm_ffi(a, true); });
 
-
-// =========================================================================================
-// Lists of values and the heterograph handle: what sparse._CAPI_DGLKernelSpMMHetero /
-// SDDMMHetero need (src/array/kernel.cc:563-601,628-656).  The reference boxes Python lists
-// as List<Value> objects through `_List` / `_Value` (python/dgl/_ffi/object_generic.py:27-59,
-// src/api/api_container.cc); the same two global names exist here with the same meaning.
-// =========================================================================================
-struct ObjValue {
-  uint32_t magic = kMagicValue;
-  DGLValue v;
-  int tc = kNull;
-};
-struct ObjList {
-  uint32_t magic = kMagicList;
-  std::vector<ObjValue> items;
-};
+// ---- `_Value` / `_List` and the heterograph entries (the objects are defined next to the unit graph) ----------------
 static size_t dtype_bytes(dgla_dtype d) { return d == DGLA_F64 ? 8 : (d == DGLA_F32 ? 4 : 2); }
-
-struct HeteroGraphObj {
-  uint32_t magic = kMagicHetero;
-  int num_ntypes = 0;
-  std::vector<UnitGraph*> rel;  // borrowed: the unit graphs outlive this object
-  std::vector<int> src, dst;    // metagraph: etype -> (src ntype, dst ntype)
-};
-
-static uint32_t magic_of(const void* h) { return h ? *static_cast<const uint32_t*>(h) : 0; }
 
 static Registrar r_value("_Value", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   if (a.n != 1) return fail("_Value takes one argument");
@@ -1535,19 +1444,6 @@ static Registrar r_list("_List", [](const FfiArgs& a, DGLValue* ret, int* rtc) {
   *rtc = kObjectHandle;
   return 0;
 });
-
-static int get_list(const FfiArgs& a, int i, const ObjList** out) {
-  void* h = nullptr;
-  if (i < a.n && a.tc[i] == kNull) {
-    static const ObjList empty;
-    *out = &empty;
-    return 0;
-  }
-  if (get_handle(a, i, &h) || magic_of(h) != kMagicList)
-    return fail("argument " + std::to_string(i) + ": expected a list (see _List)");
-  *out = static_cast<const ObjList*>(h);
-  return 0;
-}
 
 // i-th entry as an NDArray; absent (short list, None) -> nullptr
 static int list_array(const ObjList* l, size_t i, DGLArray** out) {
@@ -1704,12 +1600,8 @@ static int spmm_unit(UnitGraph* g, const char* op, const char* reduce, dgla_dtyp
       flags |= DGLA_PLAN_VALID;
     }
     const int rc = dgla_spmm_csr(op, reduce, &csc, dt, u, e, v, arg_u, arg_e, ws, ws_bytes, flags, tls_stream);
-    if (owned) {
-      (void)hipFreeAsync(owned, tls_stream);
-    } else {
-      g->split_key = UnitGraph::SplitKey();
-      if (rc == 0) g->plan_valid = true;
-    }
+    if (!owned) return spmm_done(g, rc);
+    (void)hipFreeAsync(owned, tls_stream);
     return rc;
   }
   if (g->coo.present) {
@@ -1725,17 +1617,11 @@ static int spmm_unit(UnitGraph* g, const char* op, const char* reduce, dgla_dtyp
 // V arrives zero-filled; relations whose V entry is absent are skipped (the Python layer
 // routes those destination types through the fused stacked launch instead).
 static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
-                               [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
+                               [](const FfiArgs& a, DGLValue*, int*) {
+  HeteroGraphObj* hg;
   const char *op, *reduce;
   const ObjList *LU, *LE, *LV, *LAU, *LAE, *LUT, *LET;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_str(a, 2, &reduce) || get_list(a, 3, &LU) ||
-      get_list(a, 4, &LE) || get_list(a, 5, &LV) || get_list(a, 6, &LAU) || get_list(a, 7, &LAE) ||
-      get_list(a, 8, &LUT) || get_list(a, 9, &LET))
-    return -1;
-  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
-  HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
+  if (unpack(a, &hg, &op, &reduce, &LU, &LE, &LV, &LAU, &LAE, &LUT, &LET)) return -1;
   const bool is_sum = !strcmp(reduce, "sum"), is_max = !strcmp(reduce, "max");
   if (!is_sum && !is_max && strcmp(reduce, "min")) return fail(std::string("Unsupported SpMM reducer: ") + reduce);
   const bool use_u = strcmp(op, "copy_rhs") != 0, use_e = strcmp(op, "copy_lhs") != 0;
@@ -1755,12 +1641,7 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
     if (null_array(V)) continue;                               // not ours (see above)
     if ((use_u && null_array(U)) || (use_e && null_array(E))) continue;  // relation carries no message
     dgla_dtype dt;
-    if (float_dtype(V, &dt)) return -1;
-    for (const DGLArray* t : {U, E, V, AU, AE}) {
-      if (null_array(t)) continue;
-      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
-      if (check_contiguous(t, "array")) return -1;
-    }
+    if (float_dtype(V, &dt) || check_arrays({U, E, V, AU, AE}, "array", kNotOnGraphGpu)) return -1;
     const int64_t n_out = numel(V);
     TensorArg tu, te, tv;
     to_tensor(use_u ? U : nullptr, &tu);
@@ -1776,8 +1657,8 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
     if (!initialised[d]) {
       initialised[d] = true;
       if (fill_identity(dt, data_ptr(V), n_out, is_max)) return -1;    // spmm_hetero.cu:87-99
-      if (!null_array(UT) && fill_index(g->idbits, data_ptr(UT), n_out, -1)) return -1;  // :100-117
-      if (!null_array(ET) && fill_index(g->idbits, data_ptr(ET), n_out, -1)) return -1;
+      for (const DGLArray* t : {UT, ET})                                            // :100-117
+        if (!null_array(t) && fill_index(g->idbits, data_ptr(t), n_out, -1)) return -1;
     }
     if (g->num_edges == 0) continue;
     if (use_u && null_array(AU)) return fail("Arg_U is required for max/min");
@@ -1796,8 +1677,8 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
     if (rc == 0) {
       void* au = use_u ? data_ptr(AU) : nullptr;
       void* ae = use_e ? data_ptr(AE) : nullptr;
-      void* ut = (use_u && !null_array(UT)) ? data_ptr(UT) : nullptr;
-      void* et_p = (use_e && !null_array(ET)) ? data_ptr(ET) : nullptr;
+      void* ut = use_u ? ptr_or_null(UT) : nullptr;
+      void* et_p = use_e ? ptr_or_null(ET) : nullptr;
 #define DGLA_HCOMB(DT_)                                                                               \
   rc = g->idbits == 32                                                                                \
            ? hetero_combine<DT_, int32_t>(is_max, data_ptr(V), tmp, au, tmp + off_u, ae, tmp + off_e, \
@@ -1821,18 +1702,13 @@ static Registrar r_spmm_hetero("sparse._CAPI_DGLKernelSpMMHetero",
 // (hg, op, List lhs, List rhs, List out [by etype], int lhs_target, int rhs_target): operands
 // indexed by node type for u / v targets and by edge type for e (src/array/kernel.cc:249-290).
 static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
-                                [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
+                                [](const FfiArgs& a, DGLValue*, int*) {
+  HeteroGraphObj* hg;
   const char* op;
   const ObjList *LL, *LR, *LO;
   int64_t lt, rt;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_list(a, 2, &LL) || get_list(a, 3, &LR) ||
-      get_list(a, 4, &LO) || get_int(a, 5, &lt) || get_int(a, 6, &rt))
-    return -1;
-  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
+  if (unpack(a, &hg, &op, &LL, &LR, &LO, &lt, &rt)) return -1;
   if (lt < 0 || lt > 2 || rt < 0 || rt > 2) return fail("targets must be 0 (u), 1 (e) or 2 (v)");
-  HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
   for (size_t et = 0; et < hg->rel.size(); ++et) {
     UnitGraph* g = hg->rel[et];
     const size_t pick[3] = {static_cast<size_t>(hg->src[et]), et, static_cast<size_t>(hg->dst[et])};
@@ -1843,26 +1719,8 @@ static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
     const bool use_l = strcmp(op, "copy_rhs") != 0, use_r = strcmp(op, "copy_lhs") != 0;
     if ((use_l && null_array(lhs)) || (use_r && null_array(rhs))) continue;
     dgla_dtype dt;
-    if (float_dtype(out, &dt)) return -1;
-    for (const DGLArray* t : {lhs, rhs, out}) {
-      if (null_array(t)) continue;
-      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
-      if (check_contiguous(t, "array")) return -1;
-    }
-    TensorArg l, r, o;
-    to_tensor(use_l ? lhs : nullptr, &l);
-    to_tensor(use_r ? rhs : nullptr, &r);
-    to_tensor(out, &o);
-    int rc;
-    if (g->coo.present) {
-      const dgla_coo coo = coo_of(g);
-      rc = dgla_sddmm_coo(op, &coo, dt, &l.t, &r.t, &o.t, static_cast<int>(lt), static_cast<int>(rt), tls_stream);
-    } else if (g->csr.present) {
-      const dgla_csr csr = csr_of(g, g->csr, false);
-      rc = dgla_sddmm_csr(op, &csr, dt, &l.t, &r.t, &o.t, static_cast<int>(lt), static_cast<int>(rt), tls_stream);
-    } else {
-      return fail("SDDMM only supports CSR and COO formats");
-    }
+    if (float_dtype(out, &dt) || check_arrays({lhs, rhs, out}, "array", kNotOnGraphGpu)) return -1;
+    const int rc = sddmm_unit(g, op, dt, use_l ? lhs : nullptr, use_r ? rhs : nullptr, out, lt, rt);
     if (rc) return rc;
   }
   return 0;
@@ -1875,18 +1733,13 @@ static Registrar r_sddmm_hetero("sparse._CAPI_DGLKernelSDDMMHetero",
 // type this relation contributes; with copy_lhs a (destination type, source type) pair is
 // visited once however many relations connect it (the winners' node type is what is compared).
 static Registrar r_ugmm("sparse._CAPI_DGLKernelUpdateGradMinMaxHetero",
-                        [](const FfiArgs& a, DGLValue*, int* rtc) {
-  *rtc = kNull;
-  void* h;
+                        [](const FfiArgs& a, DGLValue*, int*) {
+  HeteroGraphObj* hg;
   const char* op;
   const ObjList *LF, *LI, *LT, *LO;
-  if (get_handle(a, 0, &h) || get_str(a, 1, &op) || get_list(a, 2, &LF) || get_list(a, 3, &LI) ||
-      get_list(a, 4, &LT) || get_list(a, 5, &LO))
-    return -1;
-  if (magic_of(h) != kMagicHetero) return fail("argument 0: expected a heterograph handle");
+  if (unpack(a, &hg, &op, &LF, &LI, &LT, &LO)) return -1;
   const bool lhs = strcmp(op, "copy_lhs") == 0;
   if (!lhs && strcmp(op, "copy_rhs") != 0) return 0;  // segment_reduce.cuh:190: other operators: no-op
-  HeteroGraphObj* hg = static_cast<HeteroGraphObj*>(h);
   std::vector<std::vector<int>> seen(hg->num_ntypes);
   for (size_t et = 0; et < hg->rel.size(); ++et) {
     const int dst_nt = hg->src[et], src_nt = hg->dst[et];  // the graph is reversed
@@ -1906,10 +1759,7 @@ static Registrar r_ugmm("sparse._CAPI_DGLKernelUpdateGradMinMaxHetero",
     int bi, bt;
     if (float_dtype(feat, &dt) || idbits_of(idx, &bi) || idbits_of(idt, &bt)) return -1;
     if (bi != bt) return fail("idx and idx_type must have the same integer type");
-    for (const DGLArray* t : {feat, idx, idt, out}) {
-      if (!on_gpu(t)) return fail("array is not on the GPU device of the graph");
-      if (check_contiguous(t, "array")) return -1;
-    }
+    if (check_arrays({feat, idx, idt, out}, "array", kNotOnGraphGpu)) return -1;
     TensorArg f, o;
     to_tensor(feat, &f);
     to_tensor(out, &o);
@@ -2071,9 +1921,10 @@ int DGLFuncCall(DGLFunctionHandle func, DGLValue* args, int* type_codes, int num
       if (on) (void)hipSetDevice(dev);
     }
   } restore{prev_dev, switched};
+  if (!ret_type_code) ret_type_code = &dummy_tc;
+  *ret_type_code = kNull;  // what an entry returns unless it says otherwise (ret_int, the handle makers)
   try {
-    return (*static_cast<PackedFn*>(func))(a, ret_val ? ret_val : &dummy,
-                                           ret_type_code ? ret_type_code : &dummy_tc);
+    return (*static_cast<PackedFn*>(func))(a, ret_val ? ret_val : &dummy, ret_type_code);
   } catch (const std::exception& e) {
     last_error() = e.what();
     return -1;
