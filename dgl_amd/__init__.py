@@ -17,8 +17,9 @@ from . import udf  # noqa: E402,F401
 from . import nn  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401
 from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, add_self_loop, batch, bipartite_from_scipy, edge_subgraph,  # noqa: E402,F401
-                         from_scipy, in_subgraph, node_subgraph, remove_edges, remove_self_loop, reorder_graph,
-                         to_bidirected, to_simple, unbatch)
+                         from_scipy, in_subgraph, knn, knn_graph, node_subgraph, remove_edges, remove_self_loop, reorder_graph,
+                         segmented_knn_graph, to_bidirected, to_simple, unbatch)
+from . import geometry  # noqa: E402,F401
 from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401

@@ -912,6 +912,94 @@ def labor_pick_host(csr, seeds, fanout, rng_seed=0, prob=None, c=None):
     return indptr, nbr, eids, imp
 
 
+def knn_max_k():
+    """kKnnMaxK: the largest k of :func:`knn` (host query)."""
+    return int(LIB.dgla_knn_max_k())
+
+
+def knn_tile_sizes():
+    """(queries per workgroup, data rows per LDS tile) of the k-NN kernel (host query)."""
+    q, d = ctypes.c_int(), ctypes.c_int()
+    LIB.dgla_knn_tile_sizes(ctypes.byref(q), ctypes.byref(d))
+    return q.value, d.value
+
+
+def _knn_args(who, x, y, x_offsets, y_offsets, k, idtype, with_dist, gpu):
+    """The arguments the two k-NN entry points share, and their outputs.  The offsets are host sequences of ints."""
+    _all_on(gpu, who, x, y)
+    for t in (x, y):
+        if t is not None and (t.dim() != 2 or not t.is_contiguous()):
+            raise _lib.DGLAMDError("%s: x and y must be contiguous 2-D tensors" % who)
+    if y is not None and (y.dtype != x.dtype or y.shape[1] != x.shape[1] or y.device != x.device):
+        raise _lib.DGLAMDError("%s: x and y must share dtype, width and device" % who)
+    if x.dtype not in _DTYPES:
+        raise _lib.DGLAMDError("%s: x must be a floating-point tensor, got %s" % (who, x.dtype))
+    if len(x_offsets) != len(y_offsets) or len(x_offsets) < 1:
+        raise _lib.DGLAMDError("%s: x_offsets and y_offsets do not match: %d and %d entries"
+                               % (who, len(x_offsets), len(y_offsets)))
+    num_segs = len(x_offsets) - 1
+    xo = (ctypes.c_int64 * (num_segs + 1))(*[int(v) for v in x_offsets])
+    yo = (ctypes.c_int64 * (num_segs + 1))(*[int(v) for v in y_offsets])
+    num_y = x.shape[0] if y is None else y.shape[0]
+    k = int(k)
+    slots = num_y * max(k, 0)
+    ids = torch.empty((2, slots), dtype=idtype, device=x.device)
+    dist = torch.empty(slots, dtype=x.dtype, device=x.device) if with_dist else None
+    args = [_ptr(x), x.shape[0], _ptr(y), num_y, _DTYPES[x.dtype], x.shape[1], xo, yo, num_segs, k,
+            32 if idtype == torch.int32 else 64, _ptr(ids), _ptr(dist)]
+    return args, num_segs, ids, dist
+
+
+def knn(x, x_offsets, k, y=None, y_offsets=None, idtype=torch.int64, with_dist=False):
+    """k nearest rows of `x` for every row of `y` inside the same segment (dgla_knn; the rule: include/dgl_amd.h
+    "Point-cloud graphs").  `x_offsets` / `y_offsets` are host sequences [S + 1]; ``y=None`` is the self-query.  Returns
+    the (2, k * num_y) id tensor (queries, global data rows; -1 where a segment is shorter than k) and, with `with_dist`,
+    the squared distances.  One launch, nothing read back."""
+    args, num_segs, ids, dist = _knn_args("knn", x, y, x_offsets, x_offsets if y_offsets is None else y_offsets, k, idtype,
+                                          with_dist, True)
+    need = LIB.dgla_knn_workspace_bytes(num_segs)
+    ws = _workspace(need, x.device)
+    check_call(LIB.dgla_knn(*args, _ptr(ws), need, _stream(x)))
+    return (ids, dist) if with_dist else ids
+
+
+def knn_host(x, x_offsets, k, y=None, y_offsets=None, idtype=torch.int64, with_dist=False):
+    """:func:`knn` run by the CPU on CPU tensors (dgla_knn_host): the same rule compiled for the host, bit for bit what
+    the kernel writes.  Needs no GPU."""
+    args, _, ids, dist = _knn_args("knn_host", x, y, x_offsets, x_offsets if y_offsets is None else y_offsets, k, idtype,
+                                   with_dist, False)
+    check_call(LIB.dgla_knn_host(*args))
+    return (ids, dist) if with_dist else ids
+
+
+def _fps_args(who, pos, npoints, start, gpu):
+    _all_on(gpu, who, pos, start)
+    if pos.dim() != 3 or not pos.is_contiguous() or pos.dtype not in _DTYPES:
+        raise _lib.DGLAMDError("%s: pos must be a contiguous floating-point (B, N, C) tensor" % who)
+    B, N, C = pos.shape
+    if start.dtype != torch.int64 or start.shape != (B,) or not start.is_contiguous() or start.device != pos.device:
+        raise _lib.DGLAMDError("%s: start must be a contiguous int64 tensor with one row per cloud, on pos's device" % who)
+    out = torch.empty((B, max(int(npoints), 0)), dtype=torch.int64, device=pos.device)
+    return [_ptr(pos), _DTYPES[pos.dtype], B, N, C, int(npoints), _ptr(start), _ptr(out)], out
+
+
+def fps(pos, npoints, start):
+    """Farthest point sampling of every cloud of `pos` (B, N, C) from the rows `start` (B,) (dgla_fps; the rule:
+    include/dgl_amd.h "Point-cloud graphs"): (B, npoints) int64 row numbers inside each cloud.  One launch."""
+    args, out = _fps_args("fps", pos, npoints, start, True)
+    need = LIB.dgla_fps_workspace_bytes(args[1], args[2], args[3])
+    ws = _workspace(need, pos.device)
+    check_call(LIB.dgla_fps(*args, _ptr(ws), need, _stream(pos)))
+    return out
+
+
+def fps_host(pos, npoints, start):
+    """:func:`fps` run by the CPU on CPU tensors (dgla_fps_host).  Needs no GPU."""
+    args, out = _fps_args("fps_host", pos, npoints, start, False)
+    check_call(LIB.dgla_fps_host(*args))
+    return out
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

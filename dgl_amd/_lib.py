@@ -276,6 +276,26 @@ LIB.dgla_labor_fill.argtypes = _LABOR_REL + [c_void_p] + _LABOR_SEEDS + [ctypes.
 LIB.dgla_labor_pick_host.restype = c_int
 LIB.dgla_labor_pick_host.argtypes = _LABOR_REL + [c_void_p] + _LABOR_SEEDS + [ctypes.c_uint64, c_void_p, c_void_p,
                                                                              c_void_p, c_void_p]
+# x, num_x, y, num_y, dtype, dim, x_offsets, y_offsets, num_segs, k, id width, out_ids, out_dist
+_KNN_ARGS = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
+             c_void_p]
+_FPS_ARGS = [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]   # pos, dtype, batch, N, dim, npoints, start, out
+LIB.dgla_knn_max_k.restype = c_int
+LIB.dgla_knn_max_k.argtypes = []
+LIB.dgla_knn_tile_sizes.restype = c_int
+LIB.dgla_knn_tile_sizes.argtypes = [P(c_int), P(c_int)]
+LIB.dgla_knn_workspace_bytes.restype = c_size_t
+LIB.dgla_knn_workspace_bytes.argtypes = [c_int64]
+LIB.dgla_knn.restype = c_int
+LIB.dgla_knn.argtypes = _KNN_ARGS + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_knn_host.restype = c_int
+LIB.dgla_knn_host.argtypes = _KNN_ARGS
+LIB.dgla_fps_workspace_bytes.restype = c_size_t
+LIB.dgla_fps_workspace_bytes.argtypes = [c_int, c_int64, c_int64]
+LIB.dgla_fps.restype = c_int
+LIB.dgla_fps.argtypes = _FPS_ARGS + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_fps_host.restype = c_int
+LIB.dgla_fps_host.argtypes = _FPS_ARGS
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -8,7 +8,13 @@
 (tests/python/pytorch/nn/test_nn.py, tests/utils/graph_cases.py) build their graphs with — tools/ref_suite runs those
 files unmodified.  None of this is a kernel and none of it is timed; every graph these return builds its CSR / CSC with
 the library's COO -> CSR kernel the first time an operator asks for it, like any other graph.
+
+``knn`` / ``knn_graph`` / ``segmented_knn_graph`` (python/dgl/transforms/functional.py:111-278, 337-488, 641-785) are the
+exception: graph construction from coordinates is a hot path (EdgeConv rebuilds the graph in every layer) and runs the
+k-NN kernel of csrc/knn.hip.
 """
+import warnings
+
 import torch
 
 from . import function as fn
@@ -457,6 +463,127 @@ def adj_sum_graph(graphs, weight_name):
     return C
 
 
+class DGLWarning(UserWarning):
+    """The reference's ``dgl.base.DGLWarning``."""
+
+
+_KNN_ALGORITHMS = ("bruteforce", "bruteforce-blas", "bruteforce-sharemem")
+
+
+def _segment_list(segs):
+    return [int(v) for v in (segs.tolist() if isinstance(segs, torch.Tensor) else segs)]
+
+
+def _offsets(segs):
+    off = [0]
+    for n in segs:
+        off.append(off[-1] + n)
+    return off
+
+
+def knn(k, x, x_segs, y=None, y_segs=None, algorithm="bruteforce", dist="euclidean"):
+    """``dgl.functional.knn`` (python/dgl/transforms/functional.py:641-785): for every row of ``y`` the ``k`` nearest
+    rows of ``x`` inside the same segment; ``y=None`` is the self-query.  Returns the reference's ``(2, k * len(y))``
+    int64 tensor: row 0 the query ids, row 1 the ids in ``x``, the ``k`` slots of a query next to each other in
+    ascending (distance, id) order.
+
+    ``"bruteforce"``, ``"bruteforce-blas"`` and ``"bruteforce-sharemem"`` all run the one device kernel (csrc/knn.hip;
+    the rule: include/dgl_amd.h "Point-cloud graphs"): exact, one total order, the same bytes on every run, nothing of
+    size N x N.  ``"kd-tree"`` and ``"nn-descent"`` are refused.  ``dist="cosine"`` normalises the rows with the
+    reference's ``v / (|v| + 1e-5)`` and uses the same kernel.  ``k`` above the smallest segment of ``x`` is clamped
+    with a warning; ``k`` above ``kKnnMaxK`` (64) is refused by the library.  There is no CPU path."""
+    from . import _capi
+
+    if algorithm in ("kd-tree", "nn-descent"):
+        raise DGLAMDError("knn: algorithm '%s' is not supported: only the exact brute-force kernel runs here (%s)"
+                          % (algorithm, ", ".join(_KNN_ALGORITHMS)))
+    if algorithm not in _KNN_ALGORITHMS:
+        raise DGLAMDError("knn: unknown algorithm %r; expected one of %s" % (algorithm, ", ".join(_KNN_ALGORITHMS)))
+    self_query = y is None
+    if self_query:
+        y, y_segs = x, x_segs
+    if x.device != y.device:
+        raise DGLAMDError("knn: x and y must be on the same device")
+    x_segs, y_segs = _segment_list(x_segs), _segment_list(y_segs)
+    min_num_points = min(x_segs) if x_segs else 0
+    if k > min_num_points:
+        warnings.warn("'k' should be less than or equal to the number of points in 'x'"
+                      "expect k <= {0}, got k = {1}, use k = {0}".format(min_num_points, k), DGLWarning, stacklevel=2)
+        k = min_num_points
+    if k <= 0:
+        raise DGLAMDError("Invalid k value. expect k > 0, got k = {}".format(k))
+    if x.shape[0] == 0 or y.shape[0] == 0:
+        raise DGLAMDError("Find empty point set")
+    dist = dist.lower()
+    if dist not in ("euclidean", "cosine"):
+        raise DGLAMDError("Only ['euclidean', 'cosine'] are supported for distance computation, got {}".format(dist))
+    if x.dim() != 2 or y.dim() != 2:
+        raise DGLAMDError("knn: x and y must be 2-D")
+    if len(x_segs) != len(y_segs):
+        raise DGLAMDError("knn: x_segs and y_segs do not match: %d and %d segments" % (len(x_segs), len(y_segs)))
+    if dist == "cosine":
+        def l2_normalised(v):
+            return v / (torch.sqrt(torch.sum(v * v, dim=1, keepdim=True)) + 1e-5)
+        x = l2_normalised(x)
+        y = None if self_query else l2_normalised(y)
+    elif self_query:
+        y = None
+    return _capi.knn(x.contiguous(), _offsets(x_segs), k, None if y is None else y.contiguous(), _offsets(y_segs))
+
+
+def _knn_graph_of(x, k, segs, algorithm, dist, exclude_self, batched):
+    """The graph of a self-query over the segments ``segs`` of the 2-D ``x`` (``k`` already includes the self edge when
+    ``exclude_self``), with the batch information of the reference when ``batched``."""
+    out = knn(k, x, segs, algorithm=algorithm, dist=dist)
+    n = x.shape[0]
+    kk = out.shape[1] // n            # k after clamping
+    nbr, qry = out[1].view(n, kk), out[0].view(n, kk)
+    if exclude_self:
+        # drop the self edge of every node; a node among more than k coincident points may not hold one, and then
+        # loses its last (equally distant) neighbour instead: every node keeps kk - 1 (functional.py:257-276)
+        is_self = nbr == qry
+        drop = torch.where(is_self.any(1), is_self.int().argmax(1), torch.full_like(nbr[:, 0], kk - 1))
+        keep = torch.ones_like(is_self).scatter_(1, drop.unsqueeze(1), False)
+        nbr, qry, kk = nbr[keep], qry[keep], kk - 1
+    g = graph((nbr.reshape(-1), qry.reshape(-1)), num_nodes=n, idtype=torch.int64, device=x.device)
+    if batched:
+        num_nodes = torch.tensor(segs, dtype=torch.int64, device=x.device)
+        g._batch_num_nodes = {g.ntypes[0]: num_nodes}
+        g._batch_num_edges = {g.canonical_etypes[0]: kk * num_nodes}
+        g.batch_size = len(segs)
+    return g
+
+
+def knn_graph(x, k, algorithm="bruteforce-blas", dist="euclidean", exclude_self=False):
+    """``dgl.knn_graph`` (python/dgl/transforms/functional.py:111-278): the graph whose node ``i`` has the ``k`` nearest
+    points of ``x[i]`` as predecessors.  A 3-D ``x`` gives one graph per ``x[b]``, batched.  Every algorithm name of
+    :func:`knn` runs the device kernel, the default ``"bruteforce-blas"`` included; the neighbour sets are those of
+    ``cdist`` + ``topk`` away from ties, ties go to the smaller id.  ``exclude_self`` searches ``k + 1`` and removes the
+    self edge, with the reference's repair for more than ``k`` coincident points."""
+    if exclude_self:
+        k = k + 1
+    if k <= 0:
+        raise DGLAMDError("Invalid k value. expect k > 0, got k = {}".format(k))
+    if x.shape[0] == 0:
+        raise DGLAMDError("Find empty point set")
+    if x.dim() == 3:
+        segs = x.shape[0] * [x.shape[1]]
+        return _knn_graph_of(x.reshape(-1, x.shape[2]), k, segs, algorithm, dist, exclude_self, True)
+    return _knn_graph_of(x, k, [x.shape[0]], algorithm, dist, exclude_self, False)
+
+
+def segmented_knn_graph(x, k, segs, algorithm="bruteforce-blas", dist="euclidean", exclude_self=False):
+    """``dgl.segmented_knn_graph`` (python/dgl/transforms/functional.py:337-488): :func:`knn_graph` over point sets of
+    different sizes stored one after the other in the 2-D ``x``; ``segs`` are their sizes.  The result is batched."""
+    if exclude_self:
+        k = k + 1
+    if k <= 0:
+        raise DGLAMDError("Invalid k value. expect k > 0, got k = {}".format(k))
+    if x.shape[0] == 0:
+        raise DGLAMDError("Find empty point set")
+    return _knn_graph_of(x, k, _segment_list(segs), algorithm, dist, exclude_self, True)
+
+
 __all__ = ["adj_product_graph", "adj_sum_graph", "add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
            "node_subgraph", "edge_subgraph", "in_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
-           "adj_external"]
+           "adj_external", "knn", "knn_graph", "segmented_knn_graph", "DGLWarning"]

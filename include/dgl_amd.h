@@ -829,6 +829,71 @@ int dgla_labor_pick_host(const dgla_csr* csr, const void* prob, int prob_dtype, 
                          int64_t num_seeds, int64_t fanout, uint64_t seed, void* out_indptr, void* out_nbr, void* out_eid,
                          void* out_imp);
 
+/* ---- Point-cloud graphs: k nearest neighbours per segment, farthest points (csrc/knn.hip) -----------
+ * Replace BruteforceKnnKernel / BruteforceKnnShareKernel (src/graph/transform/cuda/knn.cu, behind dgl.knn_graph,
+ * dgl.segmented_knn_graph and dgl.functional.knn) and fps_kernel (src/geometry/cuda/geometry_op_impl.cu, behind
+ * dgl.geometry.farthest_point_sampler).  The reference's result depends on heap order and on which thread wins a tie;
+ * here it has one total order.  The rule (ONE definition for device and host, csrc/knn_step.h):
+ *
+ * Distance.  Rows have D >= 1 columns of the operand type T (fp32 or fp64; fp16 / bf16 are refused).  d(q, p) is the
+ * squared Euclidean distance computed in T as ONE chain of fused multiply-adds in ASCENDING COLUMN ORDER:
+ *     acc = 0;   for j = 0, 1, ..., D - 1:   t = q[j] - p[j];   acc = fma(t, t, acc);   d = acc.
+ * The chain does not depend on launch geometry, tile sizes, k or the segment; a wide row walked in column chunks
+ * carries acc from chunk to chunk.  fma is spelled as fma on both sides, never left to contraction.
+ *
+ * Abandoning.  The partial sums of a chain never decrease (a NaN partial sum stays NaN), so a candidate whose partial
+ * sum compares greater than the distance of the current k-th key may be abandoned: its key loses whatever the
+ * remaining columns hold.  Permitted, never required; the result cannot change.
+ *
+ * Order.  Candidates compare by the key (d, data row id), ascending.  A NaN distance orders as +inf and is written as
+ * +inf; ties in d fall to the smaller id.
+ *
+ * k-NN result.  x_offsets[S + 1] and y_offsets[S + 1] (HOST arrays, ascending from 0, ending at num_x / num_y) cut the
+ * data rows x and the query rows y into S segments.  For query row i of y in segment s the result is the k smallest
+ * keys among the rows of x in segment s, written to slots i * k ... i * k + k - 1 in ascending key order:
+ * out_ids[slot] = i, out_ids[k * num_y + slot] = the GLOBAL row id in x (the reference's (2, k * num_y) tensor, in the
+ * id type), out_dist[slot] = d (type T; out_dist may be NULL).  A segment with fewer than k data rows leaves its last
+ * slots at id -1 and distance +inf.  y == NULL is the self-query y = x (then num_y == num_x).
+ *
+ * Farthest points.  Per cloud of N rows (pos is [batch, N, D]) with start row s = start[cloud] and n <= N samples:
+ *   1. mind[i] = +inf for every row;  out[0] = s.
+ *   2. After choosing c = out[t]:  mind[c] = -1 (chosen, never chosen again); for every other row
+ *      dd = d(p_i, p_c);  mind[i] = dd < mind[i] ? dd : mind[i].
+ *   3. out[t + 1] = the row with the largest mind; ties go to the smallest i.
+ * On distinct points this is the textbook sampler; coincident points come in ascending id, never one row twice.  A NaN
+ * distance lowers nothing: a row with a NaN coordinate keeps mind = +inf until it is chosen (such rows go first, in
+ * ascending i) and lowers no other row's mind afterwards.  out holds row numbers INSIDE the cloud, int64.
+ *
+ * The results are a pure function of the inputs: no atomics, the same bytes on every run, device == host bit for bit.
+ *
+ * dgla_knn_max_k: kKnnMaxK = 64, the largest k.  dgla_knn_tile_sizes: queries per workgroup and data rows per LDS tile.
+ * dgla_knn_workspace_bytes: the tile table (three int64 per segment boundary, 256-byte aligned); 0 for num_segs <= 0.
+ * dgla_knn: x, y, out_ids, out_dist and the workspace are device memory; the offsets are host memory and are copied
+ *   to the workspace in stream order.  One launch: a wavefront owns 64 queries of one segment and streams the segment's
+ *   data rows through LDS; the k best keys of a query live in LDS.  No allocation, nothing read back.
+ * dgla_fps_workspace_bytes: 0 up to 4096 rows per cloud (mind lives in LDS), else batch * num_rows values of T.
+ * dgla_fps: pos, start [batch] (int64), out [batch, npoints] (int64) and the workspace are device memory.  One launch,
+ *   one workgroup per cloud, the loop over the samples inside it.  A start outside [0, num_rows) counts as row 0.
+ * dgla_knn_host / dgla_fps_host: the same rule run by the CPU on HOST pointers, no workspace and no stream.
+ * All fail with -1 and a message, before any launch, for fp16 / bf16 operands (by name), an id width other than
+ *   32 / 64, dim < 1, k < 1, k above kKnnMaxK (by name), NULL x / offsets / outputs, offsets that do not match (not
+ *   starting at 0, descending, or not ending at the row count), num_x or num_y >= 2^31 - 64, k * num_y >= 2^31 with
+ *   int32 ids, npoints outside [1, num_rows] and a workspace that is too small.  num_y == 0 and batch == 0 are valid. */
+int dgla_knn_max_k(void);
+int dgla_knn_tile_sizes(int* query_tile, int* data_tile);
+size_t dgla_knn_workspace_bytes(int64_t num_segs);
+int dgla_knn(const void* x, int64_t num_x, const void* y, int64_t num_y, int dtype, int64_t dim, const int64_t* x_offsets,
+             const int64_t* y_offsets, int64_t num_segs, int64_t k, int idtype_bits, void* out_ids, void* out_dist,
+             void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_knn_host(const void* x, int64_t num_x, const void* y, int64_t num_y, int dtype, int64_t dim,
+                  const int64_t* x_offsets, const int64_t* y_offsets, int64_t num_segs, int64_t k, int idtype_bits,
+                  void* out_ids, void* out_dist);
+size_t dgla_fps_workspace_bytes(int dtype, int64_t batch, int64_t num_rows);
+int dgla_fps(const void* pos, int dtype, int64_t batch, int64_t num_rows, int64_t dim, int64_t npoints, const int64_t* start,
+             int64_t* out, void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_fps_host(const void* pos, int dtype, int64_t batch, int64_t num_rows, int64_t dim, int64_t npoints,
+                  const int64_t* start, int64_t* out);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
