@@ -511,6 +511,33 @@ int dgla_csr_mask(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dg
  *   yields min(fanout, #positive edges) entries (the reference removes them after sampling).
  *   Call with out_src == NULL first to get out_indptr when the caller does not want to
  *   over-allocate num_seeds * fanout. */
+/* The rule of the three calls (tests/neighbor_cases.py restates it in Python; the device is held to that model bit for
+ * bit).  mix64, walk_key(seed, i) = mix64(seed ^ (i * 0xD1B54A32D192ED03)), step_key(wk, t) = mix64(wk + t) and
+ * index(r, n) = (r * n) >> 64 are those of csrc/random_walk_step.h.
+ *
+ * Uniform.  Seed row i with node id r = seeds[i], deg in-edges starting at position start, call seed S.
+ *   Count: fanout = -1: deg.  With replacement: fanout, or 0 for deg == 0.  Otherwise min(deg, fanout).
+ *   Positions: with fanout = -1, or deg <= fanout without replacement: 0 .. deg-1 in order.  With replacement slot k
+ *   gets index(step_key(walk_key(S, r), k), deg).  Without replacement the rule is Floyd's: for m = 0 .. fanout-1 let
+ *   j = deg - fanout + m and t = index(step_key(walk_key(S, r), m), j + 1); slot m gets t unless an earlier slot holds
+ *   t, then it gets j.
+ *   The generator is keyed by the NODE ID, not by the position in `seeds`: a node listed twice gets the same picks, and
+ *   permuting `seeds` permutes the rows.  The picks do not depend on the launch geometry.
+ *   Output: slot k of row i, at out_indptr[i] + k, holds indices[start + pos] and data ? data[start + pos] : start + pos.
+ *
+ * Weighted.  `prob` is indexed by edge id: the weight at position j of the row is w_j = prob[data ? data[start+j] :
+ *   start+j].  A position is positive iff w_j > 0, so NaN, negative weights and +-0 are never positive.
+ *   Count: without replacement min(fanout, #positive); with replacement fanout, or 0 with no positive edge.
+ *   Without replacement: u_j = ((mix64(walk_key(S, r) + 0x5851F42D4C957F2D * (j+1)) >> 11) + 1) * 2^-53 and
+ *   key_j = -ln(u_j) / (double) w_j.  The slots hold the positive positions in ascending (key, j).
+ *   With replacement: total is the fp64 sum of the positive weights (the order of the additions is free).  For slot t,
+ *   rr = mix64(walk_key(S, r) + 0x2545F4914F6CDD1D * (t+1)) and target = ((double)(rr >> 11) + 0.5) * 2^-53 * total,
+ *   evaluated left to right.  The pick is the first positive position whose inclusive prefix of positive weights is
+ *   >= target; if rounding leaves none, the last positive position.
+ *
+ * Block.  src_nodes = seeds in the given order, then the ids of `src` that are not seeds, ascending, each once.
+ *   local_src[e] is the index of src[e] in src_nodes, *num_src_out the length of src_nodes, and node_map is all -1
+ *   again on return. */
 size_t dgla_sample_neighbors_workspace_bytes(int idtype_bits, int64_t num_seeds);
 int dgla_sample_neighbors_weighted(const dgla_csr* csc, const void* prob, dgla_dtype prob_dtype,
                                    const void* seeds, int64_t num_seeds, int fanout, int replace,
