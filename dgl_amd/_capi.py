@@ -1000,6 +1000,60 @@ def fps_host(pos, npoints, start):
     return out
 
 
+MATCHING_MAX_ROUNDS = 256     # the default round cap of neighbour matching
+
+
+def _matching_args(who, csr, weight, rng_seed, max_rounds, gpu):
+    """The arguments the two neighbour-matching entry points share (csr, weight, weight_dtype, seed, max_rounds)."""
+    _all_on(gpu, who, csr._keep[0], weight)
+    if weight is not None:
+        if weight.dim() != 1 or not weight.is_contiguous() or weight.dtype not in _DTYPES:
+            raise _lib.DGLAMDError("%s: weight must be a contiguous 1-D floating-point tensor" % who)
+        if weight.shape[0] != csr.nnz:
+            raise _lib.DGLAMDError("%s: weight must hold one value per edge (%d), got %d" % (who, csr.nnz, weight.shape[0]))
+        if weight.device != csr._keep[0].device:
+            raise _lib.DGLAMDError("%s: weight and the csr must be on one device" % who)
+    return [ctypes.byref(csr), _ptr(weight), _DTYPES[weight.dtype] if weight is not None else 0, _u64(rng_seed),
+            int(max_rounds)]
+
+
+def neighbor_matching(csr, weight=None, rng_seed=0, max_rounds=MATCHING_MAX_ROUNDS, relabel=False, batch_rounds=0,
+                      workspace=None):
+    """Neighbour matching of the square CSR `csr` (dgla_neighbor_matching; the rule: include/dgl_amd.h "Graph
+    matching"): returns ``(label, rounds)``, `label` [num_rows] in the csr's id type with the smaller id of every
+    node's cluster (or, with `relabel`, consecutive cluster ids in ascending label order, dgla_neighbor_matching_relabel).
+    `weight` holds one non-negative value per EDGE ID.  The host reads one word back per `batch_rounds` rounds (0: the
+    library's default); `workspace` (uint8, dgla_neighbor_matching_workspace_bytes) is optional."""
+    args = _matching_args("neighbor_matching", csr, weight, rng_seed, max_rounds, True)
+    indptr = csr._keep[0]
+    n = csr.num_rows
+    label = torch.empty(n, dtype=indptr.dtype, device=indptr.device)
+    rounds = ctypes.c_int64(0)
+    ws_bytes = workspace.numel() if workspace is not None else 0
+    st = _stream(indptr)
+    check_call(LIB.dgla_neighbor_matching(*args, int(batch_rounds), _ptr(label), ctypes.byref(rounds), _ptr(workspace),
+                                          ws_bytes, st))
+    if relabel:
+        out = torch.empty_like(label)
+        check_call(LIB.dgla_neighbor_matching_relabel(_ptr(label), csr.idtype_bits, n, _ptr(out), _ptr(workspace), ws_bytes,
+                                                      st))
+        label = out
+    return label, rounds.value
+
+
+def neighbor_matching_host(csr, weight=None, rng_seed=0, max_rounds=MATCHING_MAX_ROUNDS, relabel=False):
+    """:func:`neighbor_matching` run by the CPU on CPU tensors (dgla_neighbor_matching_host; `csr` built with
+    :func:`host_csr`): the same rule compiled for the host, bit for bit what the kernels write.  With `relabel` returns
+    ``(label, rounds, relabelled)``.  Needs no GPU."""
+    args = _matching_args("neighbor_matching_host", csr, weight, rng_seed, max_rounds, False)
+    indptr = csr._keep[0]
+    label = torch.empty(csr.num_rows, dtype=indptr.dtype)
+    out = torch.empty_like(label) if relabel else None
+    rounds = ctypes.c_int64(0)
+    check_call(LIB.dgla_neighbor_matching_host(*args, _ptr(label), ctypes.byref(rounds), _ptr(out)))
+    return (label, rounds.value, out) if relabel else (label, rounds.value)
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

@@ -296,6 +296,15 @@ LIB.dgla_fps.restype = c_int
 LIB.dgla_fps.argtypes = _FPS_ARGS + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_fps_host.restype = c_int
 LIB.dgla_fps_host.argtypes = _FPS_ARGS
+_MATCH_ARGS = [P(CSR), c_void_p, c_int, ctypes.c_uint64, c_int64]   # csr, weight, weight_dtype, seed, max_rounds
+LIB.dgla_neighbor_matching_workspace_bytes.restype = c_size_t
+LIB.dgla_neighbor_matching_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_neighbor_matching.restype = c_int
+LIB.dgla_neighbor_matching.argtypes = _MATCH_ARGS + [c_int64, c_void_p, P(c_int64), c_void_p, c_size_t, c_void_p]
+LIB.dgla_neighbor_matching_relabel.restype = c_int
+LIB.dgla_neighbor_matching_relabel.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_neighbor_matching_host.restype = c_int
+LIB.dgla_neighbor_matching_host.argtypes = _MATCH_ARGS + [c_void_p, P(c_int64), c_void_p]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int
