@@ -17,14 +17,14 @@ from . import udf  # noqa: E402,F401
 from . import nn  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401
 from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, add_self_loop, batch, bipartite_from_scipy, edge_subgraph,  # noqa: E402,F401
-                         from_scipy, in_subgraph, knn, knn_graph, node_subgraph, remove_edges, remove_self_loop, reorder_graph,
+                         from_scipy, in_subgraph, khop_in_subgraph, khop_out_subgraph, knn, knn_graph, node_subgraph, out_subgraph, remove_edges, remove_self_loop, reorder_graph,
                          segmented_knn_graph, to_bidirected, to_simple, unbatch)
 from . import geometry  # noqa: E402,F401
 from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401
 from .sampling import (EID, NID, LaborSampler, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
-                       global_uniform_negative_sampling, node2vec_random_walk, to_block)
+                       SAINTSampler, ShaDowKHopSampler, global_uniform_negative_sampling, node2vec_random_walk, to_block)
 from . import negative_sampler  # noqa: E402,F401
 from .mm import gather_mm, segment_mm  # noqa: E402,F401
 from .segment import scatter_add, segment_reduce, segment_softmax  # noqa: E402,F401

@@ -1054,6 +1054,110 @@ def neighbor_matching_host(csr, weight=None, rng_seed=0, max_rounds=MATCHING_MAX
     return (label, rounds.value, out) if relabel else (label, rounds.value)
 
 
+SUBGRAPH_OUT_OF_RANGE, SUBGRAPH_DUPLICATE = 1, 2     # the flag bits of node_map_mark (include/dgl_amd.h)
+
+
+def _node_map_args(who, ids, node_map):
+    _all_on(True, who, ids, node_map)
+    if ids.dim() != 1 or not ids.is_contiguous():
+        raise _lib.DGLAMDError("%s: ids must be a contiguous 1-D tensor" % who)
+    if node_map.dtype != torch.int32 or node_map.dim() != 1 or not node_map.is_contiguous() or node_map.device != ids.device:
+        raise _lib.DGLAMDError("%s: the node map must be a contiguous 1-D int32 tensor on the ids' device" % who)
+    return [_idbits(ids), _ptr(ids), ids.shape[0], _ptr(node_map), node_map.shape[0]]
+
+
+def node_map_mark(ids, node_map, flags):
+    """``node_map[ids[i]] = i`` (dgla_node_map_mark).  `node_map` is int32 scratch that is all -1 between calls; `flags`
+    is a one-element int32 device tensor the call ORs SUBGRAPH_OUT_OF_RANGE / SUBGRAPH_DUPLICATE into.  Nothing is read
+    back."""
+    args = _node_map_args("node_map_mark", ids, node_map)
+    if flags.dtype != torch.int32 or flags.numel() != 1 or flags.device != ids.device:
+        raise _lib.DGLAMDError("node_map_mark: flags must be one int32 on the ids' device")
+    check_call(LIB.dgla_node_map_mark(*args, _ptr(flags), _stream(ids)))
+
+
+def node_map_clear(ids, node_map):
+    """Writes -1 back at ``node_map[ids]`` (dgla_node_map_clear); ids out of range are skipped."""
+    check_call(LIB.dgla_node_map_clear(*_node_map_args("node_map_clear", ids, node_map), _stream(ids)))
+
+
+def _flag_error(who, flags):
+    if flags & SUBGRAPH_OUT_OF_RANGE:
+        raise _lib.DGLAMDError("%s: node id out of range" % who)
+    if flags & SUBGRAPH_DUPLICATE:
+        raise _lib.DGLAMDError("%s: duplicate node id" % who)
+
+
+def _subgraph_rows_ok(who, csr, rows):
+    if rows.dim() != 1 or not rows.is_contiguous() or _idbits(rows) != csr.idtype_bits:
+        raise _lib.DGLAMDError("%s: rows must be a contiguous 1-D tensor of the csr's id type" % who)
+
+
+def induced_subgraph(csr, rows, col_map, eid_order=True, col_ids=None, flags=None, workspace=None):
+    """The entries of `csr` whose row is in `rows` and whose column is selected (dgla_induced_subgraph_count + _fill; the
+    rule: include/dgl_amd.h "Induced subgraphs").  Returns ``(out_indptr, row, col, eid)``: LOCAL row / column ids and
+    the edge ids, in ascending edge-id order (`eid_order`) or in row order, where ``out_indptr`` is the result's CSR.
+
+    `col_map` is the int32 node map of the column side.  With `col_ids` the call owns it: it marks the map from
+    `col_ids`, and ALWAYS clears it again, also when it refuses.  Without, the caller has marked it (into the device
+    word `flags`) and clears it.  Either way the flags are read back together with the total, the one host
+    synchronisation, and a set bit raises ``DGLAMDError`` ("node id out of range" / "duplicate node id").  `workspace`
+    (uint8) is optional; one that is too small for the result is refused."""
+    who = "induced_subgraph"
+    _all_on(True, who, csr._keep[0], rows, col_map, col_ids, flags)
+    _subgraph_rows_ok(who, csr, rows)
+    if col_map.dtype != torch.int32 or not col_map.is_contiguous() or col_map.shape[0] < csr.num_cols:
+        raise _lib.DGLAMDError("%s: col_map must be a contiguous int32 tensor with one entry per column node" % who)
+    nr, dev, dt, bits = rows.shape[0], rows.device, rows.dtype, csr.idtype_bits
+    st = _stream(rows)
+    if flags is None:
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    try:
+        if col_ids is not None:
+            node_map_mark(col_ids, col_map, flags)
+        need = LIB.dgla_induced_subgraph_workspace_bytes(bits, nr, 0)
+        ws = workspace if workspace is not None else _workspace(need, dev)
+        out_indptr = torch.empty(nr + 1, dtype=dt, device=dev)
+        check_call(LIB.dgla_induced_subgraph_count(ctypes.byref(csr), _ptr(rows), nr, _ptr(col_map), _ptr(out_indptr),
+                                                   _ptr(ws), ws.numel() if ws is not None else 0, st))
+        total, fl = torch.stack([out_indptr[nr].long(), flags[0].long()]).tolist()
+        _flag_error(who, fl)
+        row = torch.empty(total, dtype=dt, device=dev)
+        col = torch.empty(total, dtype=dt, device=dev)
+        eid = torch.empty(total, dtype=dt, device=dev)
+        if workspace is None and eid_order:
+            ws = _workspace(LIB.dgla_induced_subgraph_workspace_bytes(bits, nr, total), dev)
+        check_call(LIB.dgla_induced_subgraph_fill(ctypes.byref(csr), _ptr(rows), nr, _ptr(col_map), _ptr(out_indptr), total,
+                                                  _ptr(row), _ptr(col), _ptr(eid), 1 if eid_order else 0, _ptr(ws),
+                                                  ws.numel() if ws is not None else 0, st))
+    finally:
+        if col_ids is not None:
+            node_map_clear(col_ids, col_map)
+    return out_indptr, row, col, eid
+
+
+def induced_subgraph_host(csr, rows, cols, eid_order=True):
+    """:func:`induced_subgraph` run by the CPU on CPU tensors (dgla_induced_subgraph_host; `csr` built with
+    :func:`host_csr`): the same rule compiled for the host, bit for bit what the kernels write.  `cols` is the column
+    selection as a list of ids.  Returns ``(out_indptr, row, col, eid, flags)``; with a flag set the arrays are not
+    meaningful.  Needs no GPU."""
+    who = "induced_subgraph_host"
+    _all_on(False, who, rows, cols)
+    _subgraph_rows_ok(who, csr, rows)
+    if cols.dim() != 1 or not cols.is_contiguous() or cols.dtype != rows.dtype:
+        raise _lib.DGLAMDError("%s: cols must be a contiguous 1-D tensor of the csr's id type" % who)
+    nr, dt = rows.shape[0], rows.dtype
+    out_indptr = torch.empty(nr + 1, dtype=dt)
+    total, flags = ctypes.c_int64(0), ctypes.c_int32(0)
+    args = [ctypes.byref(csr), _ptr(rows), nr, _ptr(cols), cols.shape[0], 1 if eid_order else 0, _ptr(out_indptr)]
+    check_call(LIB.dgla_induced_subgraph_host(*args, None, None, None, ctypes.byref(total), ctypes.byref(flags)))   # sizes
+    row, col, eid = (torch.empty(total.value, dtype=dt) for _ in range(3))
+    if total.value:     # (an empty tensor has no address to hand over)
+        check_call(LIB.dgla_induced_subgraph_host(*args, _ptr(row), _ptr(col), _ptr(eid), ctypes.byref(total),
+                                                  ctypes.byref(flags)))
+    return out_indptr, row, col, eid, flags.value
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

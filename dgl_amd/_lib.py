@@ -305,6 +305,23 @@ LIB.dgla_neighbor_matching_relabel.restype = c_int
 LIB.dgla_neighbor_matching_relabel.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
 LIB.dgla_neighbor_matching_host.restype = c_int
 LIB.dgla_neighbor_matching_host.argtypes = _MATCH_ARGS + [c_void_p, P(c_int64), c_void_p]
+# the induced-subgraph unit: id width, ids, n, map, map_len / csr, rows, nr, col_map
+_NODE_MAP = [c_int, c_void_p, c_int64, c_void_p, c_int64]
+_SUBGRAPH = [P(CSR), c_void_p, c_int64, c_void_p]
+LIB.dgla_node_map_mark.restype = c_int
+LIB.dgla_node_map_mark.argtypes = _NODE_MAP + [c_void_p, c_void_p]
+LIB.dgla_node_map_clear.restype = c_int
+LIB.dgla_node_map_clear.argtypes = _NODE_MAP + [c_void_p]
+LIB.dgla_induced_subgraph_workspace_bytes.restype = c_size_t
+LIB.dgla_induced_subgraph_workspace_bytes.argtypes = [c_int, c_int64, c_int64]
+LIB.dgla_induced_subgraph_count.restype = c_int
+LIB.dgla_induced_subgraph_count.argtypes = _SUBGRAPH + [c_void_p, c_void_p, c_size_t, c_void_p]
+LIB.dgla_induced_subgraph_fill.restype = c_int
+LIB.dgla_induced_subgraph_fill.argtypes = _SUBGRAPH + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                                      c_size_t, c_void_p]
+LIB.dgla_induced_subgraph_host.restype = c_int
+LIB.dgla_induced_subgraph_host.argtypes = [P(CSR), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, P(c_int64), P(ctypes.c_int32)]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

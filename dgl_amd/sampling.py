@@ -933,6 +933,128 @@ def pack_traces(traces, types):
     return traces[keep], types.to(traces.device).expand_as(traces)[keep], lengths, offsets
 
 
+# ---- subgraph samplers ---------------------------------------------------------------------------
+def _induced_on(g, ids_per_type):
+    """The node-induced subgraph of ``g`` on ``ids_per_type`` in list order: the kernels of csrc/subgraph.hip on a GPU
+    graph (work proportional to the selected nodes' degrees), ``node_subgraph`` on a CPU graph."""
+    from . import transforms
+
+    if g.device.type == "cuda":
+        return transforms._induced_rows(g, ids_per_type, True, True)
+    return transforms.node_subgraph(g, ids_per_type if len(g.ntypes) > 1 else ids_per_type[g.ntypes[0]])
+
+
+class ShaDowKHopSampler:
+    """``dgl.dataloading.ShaDowKHopSampler`` (python/dgl/dataloading/shadow.py): the subgraph induced on a sampled
+    k-hop in-neighbourhood of the seeds (Zeng et al., arXiv:2012.01380).  For each fanout in reverse it runs
+    ``sample_neighbors`` + ``to_block`` and takes the block's source nodes as the next seeds; the subgraph is then cut
+    on that node list, so the seeds come first and ``subg.ndata[dgl.NID] == input_nodes``.  Fanouts may be dicts keyed
+    by edge type; ``seed_nodes`` is a dict per node type on a heterograph.  ``seed`` pins the picks as in
+    :class:`NeighborSampler`.  A CPU graph takes all neighbours only (every fanout -1): sampled fanouts run on the
+    device.  ``exclude_eids`` and the prefetch arguments are refused."""
+
+    def __init__(self, fanouts, replace=False, prob=None, seed=0, prefetch_node_feats=None, prefetch_edge_feats=None):
+        if prefetch_node_feats is not None:
+            raise _DGLError("ShaDowKHopSampler: prefetch_node_feats is not supported (features follow the subgraph eagerly)")
+        if prefetch_edge_feats is not None:
+            raise _DGLError("ShaDowKHopSampler: prefetch_edge_feats is not supported (features follow the subgraph eagerly)")
+        self.fanouts = [f if isinstance(f, dict) else int(f) for f in fanouts]
+        self.replace = bool(replace)
+        self.prob = prob
+        self.seed = int(seed)
+        self._calls = 0
+
+    def sample(self, g, seed_nodes, exclude_eids=None):
+        """``(input_nodes, output_nodes, subg)``: the node ids inducing the subgraph, the seeds, the subgraph."""
+        from . import transforms
+
+        if exclude_eids is not None:
+            raise _DGLError("ShaDowKHopSampler: exclude_eids is not supported")
+        if g.is_block:
+            raise _DGLError("ShaDowKHopSampler: the graph must not be a block")
+        is_mapping = isinstance(seed_nodes, dict)
+        if not is_mapping:
+            if len(g.ntypes) != 1:
+                raise _DGLError("seed_nodes must be a dict of node type -> ids on a graph with several node types")
+            seed_nodes = {g.ntypes[0]: seed_nodes}
+        seeds = {}
+        for n, v in seed_nodes.items():
+            t = _node_ids(v, g.device, g.idtype)
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= g.num_nodes(n)):
+                raise _DGLError("ShaDowKHopSampler: node id out of range for node type %s" % n)
+            seeds[n] = t
+        output_nodes = dict(seeds)
+        on_gpu = g.device.type == "cuda"
+        for layer, fanout in enumerate(reversed(self.fanouts)):
+            if on_gpu:
+                rng = (self.seed * 1000003 + self._calls) * 64 + layer
+                frontier = sample_neighbors(g, seeds, fanout, prob=self.prob, replace=self.replace, seed=rng)
+            else:
+                if any(int(f) != -1 for f in (fanout.values() if isinstance(fanout, dict) else [fanout])):
+                    raise _DGLError("ShaDowKHopSampler: a sampled fanout needs a graph on the GPU (no CPU fallback); "
+                                    "a CPU graph takes fanout -1 only")
+                frontier = transforms.in_subgraph(g, seeds)
+            blk = to_block(frontier, seeds)
+            seeds = {n: blk.srcnodes[n].data[NID] for n in g.ntypes}
+        self._calls += 1
+        subg = _induced_on(g, seeds)
+        if is_mapping:
+            return seeds, output_nodes, subg
+        return seeds[g.ntypes[0]], output_nodes[g.ntypes[0]], subg
+
+
+class SAINTSampler:
+    """``dgl.dataloading.SAINTSampler`` (python/dgl/dataloading/graphsaint.py; Zeng et al., arXiv:1907.04931): the
+    subgraph induced on a random node set of a homogeneous graph.  ``mode='node'`` draws ``budget`` nodes with
+    probability proportional to ``max(out-degree, 1)``; ``'edge'`` draws ``budget`` edges with probability proportional
+    to ``1 / in_deg(dst) + 1 / out_deg(src)`` and keeps their end points; ``'walk'`` takes ``budget = (num_roots,
+    walk_length)`` uniform roots and keeps every node their walks visit (this package's :func:`random_walk`, so the
+    graph is on the GPU).  The draws come from torch's generators, like the reference's; ``cache`` keeps the
+    probabilities between calls.  The result lists the distinct node ids in ascending order."""
+
+    def __init__(self, mode, budget, cache=True):
+        if mode not in ("node", "edge", "walk"):
+            raise _DGLError("Expect mode to be 'node', 'edge' or 'walk', got {}.".format(mode))
+        self.mode = mode
+        self.budget = budget
+        self.cache = cache
+        self.prob = None
+
+    def _cached(self, build):
+        if self.cache and self.prob is not None:
+            return self.prob
+        prob = build()
+        if self.cache:
+            self.prob = prob
+        return prob
+
+    def node_sampler(self, g):
+        prob = self._cached(lambda: g.out_degrees().float().clamp(min=1))
+        return torch.multinomial(prob, num_samples=self.budget, replacement=True).unique().to(g.idtype)
+
+    def edge_sampler(self, g):
+        src, dst = g.edges()
+
+        def build():
+            p = 1.0 / g.in_degrees().float().clamp(min=1)[dst.long()] + 1.0 / g.out_degrees().float().clamp(min=1)[src.long()]
+            return p / p.sum()
+        picked = torch.multinomial(self._cached(build), num_samples=self.budget, replacement=True).unique()
+        return torch.cat([src[picked], dst[picked]]).unique().to(g.idtype)
+
+    def walk_sampler(self, g):
+        num_roots, walk_length = self.budget
+        roots = torch.randint(0, g.num_nodes(), (num_roots,)).to(device=g.device, dtype=g.idtype)
+        traces, types = random_walk(g, roots, length=walk_length)
+        return pack_traces(traces, types)[0].unique().to(g.idtype)
+
+    def sample(self, g, indices=None):  # noqa: ARG002  (a placeholder in the reference too)
+        """The sampled subgraph; ``subg.ndata[dgl.NID]`` are the drawn nodes."""
+        if len(g.ntypes) != 1 or len(g.canonical_etypes) != 1:
+            raise _DGLError("SAINTSampler only supports homogeneous graphs")
+        node_ids = getattr(self, self.mode + "_sampler")(g)
+        return _induced_on(g, {g.ntypes[0]: node_ids})
+
+
 # ---- PinSAGE neighbourhoods ----------------------------------------------------------------------
 class RandomWalkNeighborSampler:
     """``dgl.sampling.RandomWalkNeighborSampler`` (python/dgl/sampling/pinsage.py:27-163): the neighbours of a seed are

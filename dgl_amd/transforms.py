@@ -318,6 +318,13 @@ def _induced(g, node_ids_per_type, edge_ids_per_etype, relabel_nodes, store_ids)
         if relabel_nodes:
             uu, vv = maps[c[0]][uu], maps[c[2]][vv]
         data[c] = (uu.to(idt), vv.to(idt))
+    return _assemble(g, data, counts, node_ids_per_type, edge_ids_per_etype, relabel_nodes, store_ids)
+
+
+def _assemble(g, data, counts, node_ids_per_type, edge_ids_per_etype, relabel_nodes, store_ids):
+    """The subgraph with edges ``data`` and node counts ``counts``, the features of ``g`` following its nodes and edges."""
+    nts, cets = g.ntypes, g.canonical_etypes
+    dev, idt = g.device, g.idtype
     if len(cets) == 1 and len(nts) == 1:
         out = graph(data[cets[0]], num_nodes=counts[nts[0]], idtype=idt, device=dev)
     else:
@@ -421,6 +428,168 @@ def in_subgraph(g, nodes, relabel_nodes=False, store_ids=True, output_device=Non
         out = _induced(g, ids, eids, True, store_ids)
     return out.to(output_device) if output_device is not None else out
 
+
+def out_subgraph(g, nodes, relabel_nodes=False, store_ids=True, output_device=None):
+    """Every outbound edge of the given nodes, all nodes kept unless ``relabel_nodes`` (subgraph.py out_subgraph): the
+    mirror image of :func:`in_subgraph`."""
+    nodes = _per_type(g, nodes, g.ntypes, "out_subgraph")
+    eids = {}
+    for c in g.canonical_etypes:
+        u, v = g.edges(etype=c)
+        if c[0] in nodes:
+            m = torch.zeros(max(g.num_nodes(c[0]), 1), dtype=torch.bool, device=g.device)
+            m[_ids_of(nodes[c[0]], 0).long()] = True
+            eids[c] = torch.nonzero(m[u.long()]).reshape(-1)
+        else:
+            eids[c] = torch.empty(0, dtype=torch.long, device=g.device)
+    if not relabel_nodes:
+        out = _induced(g, None, eids, False, store_ids)
+    else:
+        ids = {}
+        for n in g.ntypes:
+            parts = [_ids_of(nodes[n], 0).long()] if n in nodes else []
+            for c in g.canonical_etypes:
+                u, v = g.edges(etype=c)
+                e = eids[c].long()
+                if c[0] == n:
+                    parts.append(u[e].long())
+                if c[2] == n:
+                    parts.append(v[e].long())
+            ids[n] = torch.unique(torch.cat(parts)) if parts else torch.empty(0, dtype=torch.long, device=g.device)
+        out = _induced(g, ids, eids, True, store_ids)
+    return out.to(output_device) if output_device is not None else out
+
+
+def _induced_rows(g, ids_per_type, relabel_nodes=True, store_ids=True):
+    """The node-induced subgraph of a GPU graph in O(sum of the selected nodes' in-degrees): what :func:`node_subgraph`
+    returns for the id lists ``ids_per_type`` ({node type: ids}, local ids in list order), cut by the kernels of
+    csrc/subgraph.hip.  Every node type's map is marked once, every relation is swept over its in-edge CSR (count, ONE
+    read-back of (total, flags), fill in edge-id order), and the maps are cleared again whatever happens.  A duplicate or
+    out-of-range id raises ``DGLAMDError``."""
+    from . import _capi
+    from .sampling import _node_map
+
+    if g.device.type != "cuda":
+        raise DGLAMDError("_induced_rows runs on a GPU graph; use node_subgraph on %s" % g.device)
+    nts, cets = g.ntypes, g.canonical_etypes
+    dev, idt = g.device, g.idtype
+    ids = {n: (torch.as_tensor(ids_per_type[n]).reshape(-1).to(device=dev, dtype=idt).contiguous() if n in ids_per_type
+               else torch.empty(0, dtype=idt, device=dev)) for n in nts}
+    maps = {n: _node_map(g, dev, None if len(nts) == 1 else i) for i, n in enumerate(nts)}
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    data, eids, checked = {}, {}, False
+    try:
+        for n in nts:
+            _capi.node_map_mark(ids[n], maps[n], flags)
+        for etid, c in enumerate(cets):
+            rel = g._graph.relations[etid]
+            if rel.num_edges == 0 or ids[c[2]].shape[0] == 0:
+                row = col = eid = torch.empty(0, dtype=idt, device=dev)
+            else:
+                indptr, indices, emap = rel.csc()
+                csr = _capi.make_csr(indptr, indices, emap, rel.num_src)
+                _, row, col, eid = _capi.induced_subgraph(csr, ids[c[2]], maps[c[0]], eid_order=True, flags=flags)
+                checked = True
+            data[c], eids[c] = (col, row), eid          # (rows of the in-edge CSR are destinations)
+        if not checked:
+            _capi._flag_error("induced_subgraph", int(flags.item()))
+    finally:
+        for n in nts:
+            _capi.node_map_clear(ids[n], maps[n])
+    if relabel_nodes:
+        counts = {n: int(ids[n].shape[0]) for n in nts}
+    else:
+        counts = {n: g.num_nodes(n) for n in nts}
+        data = {c: (ids[c[0]][u.long()], ids[c[2]][v.long()]) for c, (u, v) in data.items()}
+    return _assemble(g, data, counts, ids, eids, relabel_nodes, store_ids)
+
+
+def _all_neighbors(rel, frontier, direction):
+    """The predecessors (``"in"``) or successors (``"out"``) of ``frontier`` over relation ``rel``, with repeats: the
+    device's all-neighbour pick on a GPU graph, the same rows of the CSC / CSR in index arithmetic on a CPU graph."""
+    indptr, indices, emap = rel.csc() if direction == "in" else rel.csr()
+    if rel.device.type == "cuda":
+        from . import _capi
+
+        csr = _capi.make_csr(indptr, indices, emap, rel.num_src if direction == "in" else rel.num_dst)
+        return _capi.sample_neighbors(csr, frontier.contiguous(), -1)[1]
+    f = frontier.long()
+    deg = (indptr[f + 1] - indptr[f]).long()
+    total = int(deg.sum())
+    first = torch.cumsum(deg, 0) - deg
+    pos = torch.repeat_interleave(indptr[f].long() - first, deg, output_size=total) + torch.arange(total)
+    return indices[pos]
+
+
+def _khop_subgraph(g, nodes, k, direction, relabel_nodes, store_ids, output_device):
+    who = "khop_%s_subgraph" % direction
+    if g.is_block:
+        raise DGLAMDError("Extracting subgraph of a block graph is not allowed.")
+    is_mapping = isinstance(nodes, dict)
+    if not is_mapping:
+        if len(g.ntypes) != 1:
+            raise DGLAMDError("%s: need a dict of node type and IDs for graph with multiple node types" % who)
+        nodes = {g.ntypes[0]: nodes}
+    dev, idt = g.device, g.idtype
+    seeds = {}
+    for n, v in nodes.items():
+        if n not in g.ntypes:
+            raise DGLAMDError('Node type "{}" does not exist.'.format(n))
+        t = torch.as_tensor(v).reshape(-1).to(device=dev, dtype=idt)
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= g.num_nodes(n)):
+            raise DGLAMDError("%s: node id out of range for node type %s" % (who, n))
+        seeds[n] = t
+    empty = torch.empty(0, dtype=idt, device=dev)
+    last, hops = seeds, [seeds]
+    for _ in range(int(k)):
+        cur = {n: [] for n in g.ntypes}
+        for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
+            here, there = (d_t, s_t) if direction == "in" else (s_t, d_t)
+            frontier = last.get(here, empty)
+            rel = g._graph.relations[etid]
+            if frontier.numel() and rel.num_edges:
+                cur[there].append(_all_neighbors(rel, frontier, direction))
+        last = {n: (torch.unique(torch.cat(v)) if v else empty) for n, v in cur.items()}
+        hops.append(last)
+    khop, inverse = {}, {}
+    for n in g.ntypes:
+        khop[n], inverse[n] = torch.unique(torch.cat([h.get(n, empty) for h in hops]), return_inverse=True)
+    if dev.type == "cuda":
+        sg = _induced_rows(g, khop, relabel_nodes, store_ids)
+    else:
+        sg = node_subgraph(g, khop, relabel_nodes=relabel_nodes, store_ids=store_ids)
+    if output_device is not None:
+        sg = sg.to(output_device)
+    if not relabel_nodes:
+        return sg
+    inv = {n: inverse[n][:seeds[n].shape[0]] for n in seeds}
+    if output_device is not None:
+        inv = {n: t.to(output_device) for n, t in inv.items()}
+    return sg, (inv if is_mapping else inv[g.ntypes[0]])
+
+
+def khop_in_subgraph(g, nodes, k, *, relabel_nodes=True, store_ids=True, output_device=None):
+    """``dgl.khop_in_subgraph`` (python/dgl/subgraph.py:618-800): the subgraph induced on the ``k``-hop in-neighbourhood
+    of ``nodes`` (ids, or a dict per node type on a heterograph), i.e. the nodes themselves and everything that reaches
+    them in at most ``k`` steps: per type the ascending distinct ids.  With ``relabel_nodes`` returns
+    ``(subgraph, inverse_indices)``, the new ids of ``nodes`` in the form they were given.  On a GPU graph every hop is
+    the device's all-neighbour pick and the subgraph is cut by csrc/subgraph.hip; on a CPU graph both steps are torch
+    index arithmetic.  Blocks are refused."""
+    return _khop_subgraph(g, nodes, k, "in", relabel_nodes, store_ids, output_device)
+
+
+def khop_out_subgraph(g, nodes, k, *, relabel_nodes=True, store_ids=True, output_device=None):
+    """``dgl.khop_out_subgraph`` (python/dgl/subgraph.py:803-985): :func:`khop_in_subgraph` along the out-edges, the nodes
+    reached from ``nodes`` in at most ``k`` steps."""
+    return _khop_subgraph(g, nodes, k, "out", relabel_nodes, store_ids, output_device)
+
+
+DGLGraph.subgraph = node_subgraph
+DGLGraph.edge_subgraph = edge_subgraph
+DGLGraph.in_subgraph = in_subgraph
+DGLGraph.out_subgraph = out_subgraph
+DGLGraph.khop_in_subgraph = khop_in_subgraph
+DGLGraph.khop_out_subgraph = khop_out_subgraph
 
 
 def adj_product_graph(A, B, weight_name, etype="_E"):
@@ -585,5 +754,5 @@ def segmented_knn_graph(x, k, segs, algorithm="bruteforce-blas", dist="euclidean
 
 
 __all__ = ["adj_product_graph", "adj_sum_graph", "add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
-           "node_subgraph", "edge_subgraph", "in_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
+           "node_subgraph", "edge_subgraph", "in_subgraph", "out_subgraph", "khop_in_subgraph", "khop_out_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
            "adj_external", "knn", "knn_graph", "segmented_knn_graph", "DGLWarning"]

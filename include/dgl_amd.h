@@ -997,6 +997,68 @@ int dgla_neighbor_matching_relabel(const void* label, int idtype_bits, int64_t n
 int dgla_neighbor_matching_host(const dgla_csr* csr, const void* weight, int weight_dtype, uint64_t seed, int64_t max_rounds,
                                 void* label, int64_t* rounds, void* relabel);
 
+/* ---- Induced subgraphs: the edges among a list of nodes (csrc/subgraph.hip) ----------------------------
+ * The step behind dgl.node_subgraph on a mini-batch of nodes, dgl.khop_in_subgraph / khop_out_subgraph and the ShaDow
+ * and SAINT samplers of dgl.dataloading (python/dgl/subgraph.py, python/dgl/dataloading/shadow.py, graphsaint.py).  The
+ * reference cuts the subgraph on the CPU (src/graph/unit_graph.cc VertexSubgraph over aten::CSRSliceMatrix).  Here the
+ * work is O(sum of deg(selected rows)); nothing of graph size is filled or scanned.  The rule (ONE definition for device
+ * and host, csrc/subgraph_step.h):
+ *
+ * Setting.  One relation as a CSR: indptr, indices, data (the edge-id map, or NULL for the identity).  For
+ * in-neighbourhoods this is the in-edge CSR: rows are destinations, indices are sources.  A list rows[nr] of selected
+ * row ids, and a dense col_map with one int32 per COLUMN node (csr->num_cols entries): -1 = not selected, otherwise the
+ * node's local id.  On a homogeneous graph rows and the column selection are the same list and col_map[rows[i]] == i.
+ *
+ * Rule.  For position i and row r = rows[i], visit every j in [indptr[r], indptr[r + 1]) in order, with u = indices[j]
+ * and l = col_map[u].  The entry is kept iff l >= 0, and then yields the triple
+ *     (local_row = i, local_col = l, eid = data ? data[j] : j).
+ * A row id outside [0, num_rows) keeps nothing and is never dereferenced; neither is a column id outside [0, num_cols).
+ *
+ * Order.  Rows of the result go by i, then by j.  out_indptr[i] = the number of kept entries of the positions before i,
+ * out_indptr[nr] = the total.  Integer arithmetic only: device == host bit for bit, whatever the launch geometry.
+ *
+ * dgla_node_map_mark: map[ids[i]] = i for the ids inside [0, map_len); ORs DGLA_SUBGRAPH_OUT_OF_RANGE (1) into the
+ *   device word *flags when some id lies outside, and, in a second launch, DGLA_SUBGRAPH_DUPLICATE (2) when
+ *   map[ids[i]] != i for some i, i.e. an id appears twice (the racing plain stores are benign: one writer wins and the
+ *   loser is seen by the check).  *flags is only ORed into: the caller zeroes it, and may share it between calls.
+ * dgla_node_map_clear: writes -1 back at the ids inside [0, map_len).  `map` is caller-owned scratch, all -1 between
+ *   calls, exactly like the node_map of dgla_to_block.  Both refuse n >= 2^31 (local ids are int32).
+ * dgla_induced_subgraph_workspace_bytes: the workspace of count (total = 0) and of fill in eid order (the `total` count
+ *   reported): 8 bytes per row plus the scan's scratch, and for the eid order two id arrays, two 64-bit key arrays of
+ *   `total` entries and the sort's tables.  Monotone in total.  0 for another id width or negative sizes.
+ * dgla_induced_subgraph_count: out_indptr[nr + 1] (device, the CSR's id type): the kept entries per row, counted by a
+ *   group of 16 lanes per row when csr->nnz / csr->num_rows <= 32 and a wavefront of 64 otherwise (the bits written do
+ *   not depend on it), then the library's own scan.  Stream-ordered, no allocation, no atomics, nothing read back: the
+ *   caller reads out_indptr[nr] (and the flags word of mark) before it sizes the outputs of fill.
+ * dgla_induced_subgraph_fill: the same sweep; a kept entry goes to out_indptr[i] + (kept so far in the row) +
+ *   popcount(lower lanes of the group's ballot bits).  out_row / out_col / out_eid hold `total` = out_indptr[nr] entries
+ *   (the caller read it back); no write goes past total.  eid_order == 0: the outputs stay in row order and, with
+ *   out_indptr, are the subgraph's CSR over the selected rows.  eid_order != 0: the call finishes by permuting the three
+ *   arrays into ascending eid, ties by row-order position, with the library's own stable sort (csrc/sort.hip.h) over
+ *   keys (eid << bits(total)) | position; edge ids are distinct, so the result is unique.  Edge ids must lie in
+ *   [0, csr->nnz) (the edge-id map is a permutation, as everywhere in this header), and bits(nnz) + bits(total) <= 63.
+ *   Row-order calls need no workspace.
+ * dgla_induced_subgraph_host: the same rule run by the CPU on HOST pointers, no workspace and no stream.  It takes the
+ *   column selection as the list cols[nc] and builds its own map; *total and *flags (the bits above, also set for a row
+ *   id outside [0, num_rows)) are host words.  out_row == NULL: out_indptr, *total and *flags only (the sizes).
+ * All fail with -1 and a message, before any launch, for a NULL csr / indptr / indices / rows / ids / map / flags /
+ *   output, an id width other than 32 / 64, negative sizes, nr or n >= 2^31 and a workspace that is too small.  nr == 0
+ *   and total == 0 are valid. */
+#define DGLA_SUBGRAPH_OUT_OF_RANGE 1
+#define DGLA_SUBGRAPH_DUPLICATE 2
+int dgla_node_map_mark(int idtype_bits, const void* ids, int64_t n, int32_t* map, int64_t map_len, int32_t* flags,
+                       void* hip_stream);
+int dgla_node_map_clear(int idtype_bits, const void* ids, int64_t n, int32_t* map, int64_t map_len, void* hip_stream);
+size_t dgla_induced_subgraph_workspace_bytes(int idtype_bits, int64_t nr, int64_t total);
+int dgla_induced_subgraph_count(const dgla_csr* csr, const void* rows, int64_t nr, const int32_t* col_map, void* out_indptr,
+                                void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_induced_subgraph_fill(const dgla_csr* csr, const void* rows, int64_t nr, const int32_t* col_map,
+                               const void* out_indptr, int64_t total, void* out_row, void* out_col, void* out_eid,
+                               int eid_order, void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_induced_subgraph_host(const dgla_csr* csr, const void* rows, int64_t nr, const void* cols, int64_t nc,
+                               int eid_order, void* out_indptr, void* out_row, void* out_col, void* out_eid, int64_t* total,
+                               int32_t* flags);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
