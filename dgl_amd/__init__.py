@@ -16,7 +16,7 @@ from .heterograph import (DGLGraph, ETYPE, NTYPE, create_block, from_networkx, g
 from . import udf  # noqa: E402,F401
 from . import nn  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401
-from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, add_self_loop, batch, bipartite_from_scipy, edge_subgraph,  # noqa: E402,F401
+from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, add_self_loop, batch, bipartite_from_scipy, compact_graphs, edge_subgraph,  # noqa: E402,F401
                          from_scipy, in_subgraph, khop_in_subgraph, khop_out_subgraph, knn, knn_graph, node_subgraph, out_subgraph, remove_edges, remove_self_loop, reorder_graph,
                          segmented_knn_graph, to_bidirected, to_simple, unbatch)
 from . import geometry  # noqa: E402,F401
@@ -26,6 +26,7 @@ from .ops import edge_softmax  # noqa: E402,F401
 from .sampling import (EID, NID, LaborSampler, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
                        SAINTSampler, ShaDowKHopSampler, global_uniform_negative_sampling, node2vec_random_walk, to_block)
 from . import negative_sampler  # noqa: E402,F401
+from . import dataloading  # noqa: E402,F401
 from .mm import gather_mm, segment_mm  # noqa: E402,F401
 from .segment import scatter_add, segment_reduce, segment_softmax  # noqa: E402,F401
 from .sparse_kernels import release_static, set_auto_edge_operand, static_features  # noqa: E402,F401

@@ -1158,6 +1158,118 @@ def induced_subgraph_host(csr, rows, cols, eid_order=True):
     return out_indptr, row, col, eid, flags.value
 
 
+EXCLUDE_OUT_OF_RANGE = 1     # the flag bit of exclude_set / compact_nodes (include/dgl_amd.h)
+
+
+def _ids_ok(who, gpu, *tensors):
+    """1-D contiguous id tensors of one width, all on the device (`gpu`) or all on the CPU; None entries are skipped."""
+    ts = [t for t in tensors if t is not None]
+    _all_on(gpu, who, *ts)
+    for t in ts:
+        if t.dim() != 1 or not t.is_contiguous() or t.dtype != ts[0].dtype or t.device != ts[0].device:
+            raise _lib.DGLAMDError("%s: the arrays must be contiguous 1-D tensors of one id type on one device" % who)
+    return _idbits(ts[0])
+
+
+def exclude_set(ids, num_edges, reverse=None, workspace=None):
+    """The exclusion set of the seed edges `ids` (dgla_exclude_set; the rule: include/dgl_amd.h "Edge exclusion and
+    compaction"): ``sort(ids ++ reverse[ids])``, or ``sort(ids)`` without a reverse map.  The flag word is read back once
+    and an id outside ``[0, num_edges)`` raises ``DGLAMDError`` ("edge id out of range").  `workspace` (uint8) is
+    optional; one that is too small is refused."""
+    who = "exclude_set"
+    bits = _ids_ok(who, True, ids, reverse)
+    if reverse is not None and reverse.shape[0] != int(num_edges):
+        raise _lib.DGLAMDError("%s: the reverse map must have one entry per edge" % who)
+    n, dev = ids.shape[0], ids.device
+    out = torch.empty(2 * n if reverse is not None else n, dtype=ids.dtype, device=dev)
+    if n == 0:
+        return out
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    check_call(LIB.dgla_exclude_set(bits, _ptr(ids), n, _ptr(reverse), int(num_edges), _ptr(out), _ptr(flags), _ptr(workspace),
+                                    workspace.numel() if workspace is not None else 0, _stream(ids)))
+    if int(flags.item()) & EXCLUDE_OUT_OF_RANGE:
+        raise _lib.DGLAMDError("%s: edge id out of range" % who)
+    return out
+
+
+def exclude_set_host(ids, num_edges, reverse=None):
+    """:func:`exclude_set` run by the CPU on CPU tensors (dgla_exclude_set_host).  Returns ``(x, flags)`` and raises
+    nothing for an id out of range: the flag word is the caller's to read.  Needs no GPU."""
+    bits = _ids_ok("exclude_set_host", False, ids, reverse)
+    n = ids.shape[0]
+    out = torch.empty(2 * n if reverse is not None else n, dtype=ids.dtype)
+    flags = ctypes.c_int32(0)
+    check_call(LIB.dgla_exclude_set_host(bits, _ptr(ids), n, _ptr(reverse), int(num_edges), _ptr(out), ctypes.byref(flags)))
+    return out, flags.value
+
+
+def frontier_exclude(indptr, src, eids, x, workspace=None):
+    """Drops the entries of a sampled frontier whose edge id is in the sorted set `x` (dgla_frontier_exclude).  The
+    frontier is the CSR over the seeds that :func:`sample_neighbors` returns.  Returns ``(out_indptr, out_src,
+    out_eids)`` with the outputs allocated at the frontier's size: the first ``out_indptr[-1]`` entries are the result.
+    Nothing is read back."""
+    who = "frontier_exclude"
+    bits = _ids_ok(who, True, indptr, src, eids, x)
+    nr, nnz = indptr.shape[0] - 1, src.shape[0]
+    if nr < 0 or eids.shape[0] != nnz:
+        raise _lib.DGLAMDError("%s: indptr needs at least one entry, src and eids one length" % who)
+    out_indptr, out_src, out_eids = torch.empty_like(indptr), torch.empty_like(src), torch.empty_like(eids)
+    check_call(LIB.dgla_frontier_exclude(bits, _ptr(indptr), _ptr(src), _ptr(eids), nr, nnz, _ptr(x), x.shape[0],
+                                         _ptr(out_indptr), _ptr(out_src), _ptr(out_eids), _ptr(workspace),
+                                         workspace.numel() if workspace is not None else 0, _stream(indptr)))
+    return out_indptr, out_src, out_eids
+
+
+def frontier_exclude_host(indptr, src, eids, x):
+    """:func:`frontier_exclude` run by the CPU on CPU tensors (dgla_frontier_exclude_host); the outputs are cut to the
+    result's length.  Needs no GPU."""
+    who = "frontier_exclude_host"
+    bits = _ids_ok(who, False, indptr, src, eids, x)
+    nr, nnz = indptr.shape[0] - 1, src.shape[0]
+    if nr < 0 or eids.shape[0] != nnz:
+        raise _lib.DGLAMDError("%s: indptr needs at least one entry, src and eids one length" % who)
+    out_indptr, out_src, out_eids = torch.empty_like(indptr), torch.empty_like(src), torch.empty_like(eids)
+    check_call(LIB.dgla_frontier_exclude_host(bits, _ptr(indptr), _ptr(src), _ptr(eids), nr, nnz, _ptr(x), x.shape[0],
+                                              _ptr(out_indptr), _ptr(out_src), _ptr(out_eids)))
+    total = int(out_indptr[-1])
+    return out_indptr, out_src[:total], out_eids[:total]
+
+
+def compact_nodes(preserve, ends, node_map, workspace=None):
+    """The compact node space of one node type (dgla_compact_nodes): ``(local, nodes)`` with ``nodes`` = `preserve` in
+    the order given (a repeated id at its first position), then the other ids of `ends` ascending, and ``local[e]`` the
+    index of ``ends[e]`` in it.  `node_map` is the type's int32 scratch, all -1 before and after, refusals included.  The
+    node count and the flag word come back in ONE read-back; an id outside the map raises ``DGLAMDError`` ("node id out
+    of range")."""
+    who = "compact_nodes"
+    bits = _ids_ok(who, True, preserve, ends)
+    if node_map.dtype != torch.int32 or node_map.dim() != 1 or not node_map.is_contiguous() or node_map.device != ends.device:
+        raise _lib.DGLAMDError("%s: the node map must be a contiguous 1-D int32 tensor on the ids' device" % who)
+    np_, ne, dev, dt = preserve.shape[0], ends.shape[0], ends.device, ends.dtype
+    local = torch.empty(ne, dtype=dt, device=dev)
+    nodes = torch.empty(np_ + ne, dtype=dt, device=dev)
+    words = torch.zeros(2, dtype=torch.int64, device=dev)       # [node count, flags (its low int32)]
+    check_call(LIB.dgla_compact_nodes(bits, _ptr(preserve), np_, _ptr(ends), ne, _ptr(node_map), node_map.shape[0], _ptr(local),
+                                      _ptr(nodes), words.data_ptr(), words.data_ptr() + 8, _ptr(workspace),
+                                      workspace.numel() if workspace is not None else 0, _stream(ends)))
+    num, fl = words.tolist()
+    if fl & EXCLUDE_OUT_OF_RANGE:
+        raise _lib.DGLAMDError("%s: node id out of range" % who)
+    return local, nodes[:num]
+
+
+def compact_nodes_host(preserve, ends, num_nodes):
+    """:func:`compact_nodes` run by the CPU on CPU tensors (dgla_compact_nodes_host).  Returns ``(local, nodes,
+    flags)``.  Needs no GPU."""
+    bits = _ids_ok("compact_nodes_host", False, preserve, ends)
+    np_, ne, dt = preserve.shape[0], ends.shape[0], ends.dtype
+    local, nodes = torch.empty(ne, dtype=dt), torch.empty(np_ + ne, dtype=dt)
+    num, flags = ctypes.c_int64(0), ctypes.c_int32(0)
+    check_call(LIB.dgla_compact_nodes_host(bits, _ptr(preserve), np_, _ptr(ends), ne, int(num_nodes), _ptr(local), _ptr(nodes),
+                                           ctypes.byref(num), ctypes.byref(flags)))
+    return local, nodes[:num.value], flags.value
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

@@ -322,6 +322,30 @@ LIB.dgla_induced_subgraph_fill.argtypes = _SUBGRAPH + [c_void_p, c_int64, c_void
 LIB.dgla_induced_subgraph_host.restype = c_int
 LIB.dgla_induced_subgraph_host.argtypes = [P(CSR), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, P(c_int64), P(ctypes.c_int32)]
+# the exclusion / compaction unit: id width, ids, n, rev, num_edges, out, flags / id width, indptr, src, eids, rows, nnz,
+# x, n_x, out_indptr, out_src, out_eids / id width, preserve, np, ends, ne
+_EXCLUDE_SET = [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+_FRONTIER = [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+_COMPACT = [c_int, c_void_p, c_int64, c_void_p, c_int64]
+LIB.dgla_exclude_set_workspace_bytes.restype = c_size_t
+LIB.dgla_exclude_set_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+LIB.dgla_exclude_set.restype = c_int
+LIB.dgla_exclude_set.argtypes = _EXCLUDE_SET + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_exclude_set_host.restype = c_int
+LIB.dgla_exclude_set_host.argtypes = _EXCLUDE_SET
+LIB.dgla_frontier_exclude_workspace_bytes.restype = c_size_t
+LIB.dgla_frontier_exclude_workspace_bytes.argtypes = [c_int, c_int64, c_int64]
+LIB.dgla_frontier_exclude.restype = c_int
+LIB.dgla_frontier_exclude.argtypes = _FRONTIER + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_frontier_exclude_host.restype = c_int
+LIB.dgla_frontier_exclude_host.argtypes = _FRONTIER
+LIB.dgla_compact_nodes_workspace_bytes.restype = c_size_t
+LIB.dgla_compact_nodes_workspace_bytes.argtypes = [c_int, c_int64, c_int64]
+LIB.dgla_compact_nodes.restype = c_int
+LIB.dgla_compact_nodes.argtypes = _COMPACT + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]
+LIB.dgla_compact_nodes_host.restype = c_int
+LIB.dgla_compact_nodes_host.argtypes = _COMPACT + [c_int64, c_void_p, c_void_p, P(c_int64), P(ctypes.c_int32)]
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -104,7 +104,50 @@ def _per_etype(g, value, what):
     return out
 
 
-def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed):
+def _per_etype_ids(g, value):
+    """``value`` (ids, or a dict keyed by edge type) -> one id tensor or None per relation."""
+    if value is None:
+        return [None] * len(g.canonical_etypes)
+    if not isinstance(value, dict):
+        if len(g.canonical_etypes) > 1:
+            raise _DGLError("Must specify etype when the graph is not homogeneous.")
+        value = {g.canonical_etypes[0]: value}
+    out = [None] * len(g.canonical_etypes)
+    for e, ids in value.items():
+        out[g.get_etype_id(e)] = ids
+    return out
+
+
+class _ExclusionSets(list):
+    """One sorted exclusion list (or None) per relation of a graph: what :func:`_exclusion_sets` builds once per batch."""
+
+
+def _mark_exclusion_set(x):
+    """Tags ``x`` as a sorted exclusion list (the output of ``_capi.exclude_set``), so that handing it on as
+    ``exclude_eids`` does not sort it a second time.  The tag lives on this tensor object alone."""
+    x._dgla_exclusion_set = True
+    return x
+
+
+def _exclusion_sets(g, exclude_edges):
+    """``exclude_edges`` (ids, or a dict per edge type / canonical edge type) as one sorted list per relation on the
+    graph's device (csrc/exclude.hip; one read-back of the flag word per relation that has a list).  An id outside the
+    relation's edges is refused ("edge id out of range")."""
+    if exclude_edges is None or isinstance(exclude_edges, _ExclusionSets):
+        return exclude_edges
+    out = _ExclusionSets()
+    for etid, ids in enumerate(_per_etype_ids(g, exclude_edges)):
+        rel = g._graph.relations[etid]
+        if ids is None or torch.as_tensor(ids).numel() == 0:
+            out.append(None)
+        elif getattr(ids, "_dgla_exclusion_set", False) and ids.device == rel.device and ids.dtype == rel.idtype:
+            out.append(ids)
+        else:
+            out.append(_capi.exclude_set(_node_ids(ids, rel.device, rel.idtype), rel.num_edges))
+    return out
+
+
+def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed, excluded=None):
     """sample_neighbors on a graph with several relations (python/dgl/sampling/neighbor.py:300-395): relation by
     relation through the same kernels; a relation whose seed side has no nodes in ``nodes``, or whose fanout is 0, comes
     out empty.  The result keeps every node type and node count of ``g``."""
@@ -139,6 +182,8 @@ def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed):
             indptr, nbr, eids = _capi.sample_neighbors(csr, seeds, -1, False, rng)
         else:
             indptr, nbr, eids = _capi.sample_neighbors_weighted(csr, p, seeds, f, replace, rng)
+        if excluded is not None and excluded[etid] is not None:     # sample first, then drop (sampling/utils.py EidExcluder)
+            indptr, nbr, eids = _capi.frontier_exclude(indptr, nbr, eids, excluded[etid])
         n_e = int(indptr[-1])
         own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
         nbr, eids = nbr[:n_e], eids[:n_e]
@@ -156,10 +201,14 @@ def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed):
     return out
 
 
-def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, seed=None):
+def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, seed=None, exclude_edges=None):
     """Frontier graph on the nodes of `g` holding, for every node in `nodes`, ``fanout`` of its
     inbound edges picked uniformly (all of them when it has fewer, or ``fanout == -1``).
     ``edata[dgl.EID]`` carries the original edge ids.
+
+    ``exclude_edges`` (ids, or a dict keyed by edge type / canonical edge type) drops those edges from the frontier
+    AFTER the picks (the reference's rule, sampling/utils.py EidExcluder: a row may come out shorter than its fanout):
+    the filter of csrc/exclude.hip, on a GPU graph only.
 
     ``seed=None`` (default) draws a fresh stream for every call from torch's global CPU
     generator, like the reference's advancing global RNG (so ``torch.manual_seed`` makes a run
@@ -167,8 +216,9 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
     seed = _call_seed(seed)
     if edge_dir not in ("in", "out"):
         raise ValueError("edge_dir must be 'in' or 'out'")
+    excluded = _exclusion_sets(g, exclude_edges)
     if len(g.canonical_etypes) != 1 or isinstance(nodes, dict) or isinstance(fanout, dict):
-        return _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed)
+        return _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed, excluded)
     if edge_dir == "in":
         rel, csr, keep = _csc_of(g)
     else:  # outbound edges: the same kernel over the out-edge CSR (rows = source nodes)
@@ -194,6 +244,8 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
             indptr, nbr, eids = _capi.sample_neighbors(csr, nodes, -1, False, int(seed))
         else:
             indptr, nbr, eids = _capi.sample_neighbors_weighted(csr, p, nodes, int(fanout), replace, int(seed))
+    if excluded is not None and excluded[0] is not None:     # sample first, then drop
+        indptr, nbr, eids = _capi.frontier_exclude(indptr, nbr, eids, excluded[0])
     n_e = int(indptr[-1])
     own = torch.repeat_interleave(nodes, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
     nbr, eids = nbr[:n_e], eids[:n_e]
@@ -208,10 +260,13 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
     return out
 
 
-def sample_neighbors_fused(g, nodes, fanout, edge_dir="in", prob=None, replace=False, seed=None):
+def sample_neighbors_fused(g, nodes, fanout, edge_dir="in", prob=None, replace=False, seed=None, exclude_edges=None):
     """``sample_neighbors`` followed by ``to_block`` on the seeds (python/dgl/sampling/neighbor.py
     sample_neighbors_fused, a CPU-only fusion of the two there): the block of one sampling step, its edge ids those of
-    ``g``."""
+    ``g``.  ``exclude_edges`` is refused: use :func:`sample_neighbors` and :func:`to_block`."""
+    if exclude_edges is not None:
+        raise _DGLError("sample_neighbors_fused: exclude_edges is not supported; call sample_neighbors(exclude_edges=) "
+                        "and to_block")
     if edge_dir != "in":
         raise _DGLError("sample_neighbors_fused: only inbound sampling yields a block whose destinations are the seeds")
     frontier = sample_neighbors(g, nodes, fanout, edge_dir=edge_dir, prob=prob, replace=replace, seed=seed)
@@ -397,9 +452,15 @@ class NeighborSampler:
         self.replace = bool(replace)
         self.seed = int(seed)
         self.prob = prob  # name of an edge feature holding sampling weights (the reference's `prob`)
+        self.output_device = None
         self._calls = 0
 
-    def _sample_blocks_hetero(self, g, seed_nodes):
+    def sample(self, g, seed_nodes, exclude_eids=None):
+        """``BlockSampler.sample`` of dataloading/base.py: :meth:`sample_blocks`, the signature that
+        ``as_edge_prediction_sampler`` looks for."""
+        return self.sample_blocks(g, seed_nodes, exclude_eids=exclude_eids)
+
+    def _sample_blocks_hetero(self, g, seed_nodes, excluded=None):
         """Several relations: ``sample_neighbors`` + ``to_block`` per layer, as neighbor_sampler.py:150-175 composes
         them; fanouts may be dicts keyed by edge type."""
         if not isinstance(seed_nodes, dict):
@@ -411,7 +472,8 @@ class NeighborSampler:
         blocks = []
         for layer, fanout in enumerate(reversed(self.fanouts)):
             rng = (self.seed * 1000003 + self._calls) * 64 + layer
-            frontier = sample_neighbors(g, seeds, fanout, prob=self.prob, replace=self.replace, seed=rng)
+            frontier = sample_neighbors(g, seeds, fanout, prob=self.prob, replace=self.replace, seed=rng,
+                                        exclude_edges=excluded)
             blk = to_block(frontier, seeds)
             for etid in range(len(g.canonical_etypes)):          # ids of the ORIGINAL graph (neighbor_sampler.py:170-172)
                 fe = frontier._edge_frames[etid][EID]
@@ -421,9 +483,14 @@ class NeighborSampler:
         self._calls += 1
         return seeds, output_nodes, blocks
 
-    def sample_blocks(self, g, seed_nodes):
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        """``exclude_eids`` (ids, or a dict per edge type): those edges are dropped from every layer's frontier after
+        the picks (csrc/exclude.hip).  The set is sorted once per call; a layer with exclusion reads back the number of
+        surviving picks and then the number of source nodes (two read-backs instead of the one of the plain path)."""
+        excluded = _exclusion_sets(g, exclude_eids)
         if len(g.canonical_etypes) != 1 or len(g.ntypes) != 1 or isinstance(seed_nodes, dict):
-            return self._sample_blocks_hetero(g, seed_nodes)
+            return self._sample_blocks_hetero(g, seed_nodes, excluded)
+        x = excluded[0] if excluded is not None else None
         rel, csr, keep = _csc_of(g)
         dev, idt = rel.device, rel.idtype
         node_map = _node_map(g, dev)
@@ -433,7 +500,7 @@ class NeighborSampler:
         for layer, fanout in enumerate(reversed(self.fanouts)):
             rng = (self.seed * 1000003 + self._calls) * 64 + layer
             if self.prob is None:
-                if not (fanout > 0 and seeds.shape[0] > 0):
+                if x is not None or not (fanout > 0 and seeds.shape[0] > 0):
                     indptr, src, eids = _capi.sample_neighbors(csr, seeds, fanout, self.replace, rng)
             else:
                 p = g.edata[self.prob] if isinstance(self.prob, str) else self.prob
@@ -444,7 +511,9 @@ class NeighborSampler:
                 p = (p if p.dtype in (torch.float32, torch.float64) else p.float()).contiguous().reshape(-1)
                 indptr, src, eids = _capi.sample_neighbors_weighted(csr, p, seeds, fanout, self.replace, rng)
             n = seeds.shape[0]
-            if self.prob is None and fanout > 0 and n > 0:
+            if x is not None:       # sample first, then drop (sampling/utils.py EidExcluder)
+                indptr, src, eids = _capi.frontier_exclude(indptr, src, eids, x)
+            if x is None and self.prob is None and fanout > 0 and n > 0:
                 # ONE read-back per layer instead of two: renumber the whole fixed-size pick buffer
                 # (its unused tail is filled with the first seed, which adds no node) and fetch the
                 # number of picks and of source nodes together.  Same picks, same local ids.
@@ -465,7 +534,7 @@ class NeighborSampler:
         self._calls += 1
         return seeds, output_nodes, blocks
 
-    def sample_blocks_padded(self, g, seed_nodes, num_valid=None):
+    def sample_blocks_padded(self, g, seed_nodes, num_valid=None, exclude_eids=None):
         """Static-shape ``sample_blocks``: no size is read back, every tensor has a shape that depends
         only on ``len(seed_nodes)`` and the fanouts, so the call — and the training step around it —
         can be captured in one hipGraph (``torch.cuda.graph``) and replayed.
@@ -481,7 +550,10 @@ class NeighborSampler:
         a smaller batch is refused.  Returns ``(input_nodes,
         num_input, output_nodes, blocks)``; ``blocks[i].num_src_valid`` / ``.num_dst_valid`` are the
         device-side counts.  Each call advances a DEVICE-side draw counter (``self.counter``), so a
-        replayed graph samples fresh neighbours."""
+        replayed graph samples fresh neighbours.  ``exclude_eids`` is refused: dropping picks would move the sink rows'
+        edges, a layout of its own."""
+        if exclude_eids is not None:
+            raise _DGLError("sample_blocks_padded: exclude_eids is not supported in the padded form; use sample_blocks")
         if len(g.canonical_etypes) != 1 or any(isinstance(f, dict) for f in self.fanouts):
             raise _DGLError("sample_blocks_padded: single-relation graphs only (one static shape per layer)")
         if min(self.fanouts) < 1:
@@ -532,20 +604,6 @@ def _labor_seed(random_seed):
             raise _DGLError("sample_labors: random_seed must be an int or a tensor with one element")
         random_seed = int(random_seed.reshape(-1)[0].item())
     return _call_seed(random_seed)
-
-
-def _per_etype_ids(g, value):
-    """``value`` (ids, or a dict keyed by edge type) -> one id tensor or None per relation."""
-    if value is None:
-        return [None] * len(g.canonical_etypes)
-    if not isinstance(value, dict):
-        if len(g.canonical_etypes) > 1:
-            raise _DGLError("Must specify etype when the graph is not homogeneous.")
-        value = {g.canonical_etypes[0]: value}
-    out = [None] * len(g.canonical_etypes)
-    for e, ids in value.items():
-        out[g.get_etype_id(e)] = ids
-    return out
 
 
 def sample_labors(g, nodes, fanout, edge_dir="in", prob=None, importance_sampling=0, random_seed=None,
@@ -663,9 +721,16 @@ class LaborSampler:
         self.importance_sampling = importance_sampling
         self.layer_dependency = bool(layer_dependency)
         self.seed = int(seed)
+        self.output_device = None
         self._calls = 0
 
-    def sample_blocks(self, g, seed_nodes):
+    def sample(self, g, seed_nodes, exclude_eids=None):
+        """``BlockSampler.sample`` of dataloading/base.py: :meth:`sample_blocks`, the signature that
+        ``as_edge_prediction_sampler`` looks for."""
+        return self.sample_blocks(g, seed_nodes, exclude_eids=exclude_eids)
+
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        """``exclude_eids`` is handed to :func:`sample_labors` as ``exclude_edges`` for every layer."""
         as_dict = isinstance(seed_nodes, dict)
         if not as_dict:
             if len(g.ntypes) != 1:
@@ -678,7 +743,7 @@ class LaborSampler:
             rng = (self.seed * 1000003 + self._calls) * 64 + (0 if self.layer_dependency else layer)
             frontier, imps = sample_labors(g, seeds, fanout, edge_dir=self.edge_dir, prob=self.prob,
                                            importance_sampling=self.importance_sampling, random_seed=rng,
-                                           copy_ndata=False, copy_edata=False)
+                                           copy_ndata=False, copy_edata=False, exclude_edges=exclude_eids)
             blk = to_block(frontier, seeds)
             for etid in range(len(g.canonical_etypes)):          # ids of the ORIGINAL graph (labor_sampler.py)
                 fe = frontier._edge_frames[etid][EID]

@@ -504,6 +504,116 @@ def _induced_rows(g, ids_per_type, relabel_nodes=True, store_ids=True):
     return _assemble(g, data, counts, ids, eids, relabel_nodes, store_ids)
 
 
+def _compact_nodes_torch(preserve, ends, num_nodes):
+    """The compaction rule of include/dgl_amd.h ("Edge exclusion and compaction") in torch index arithmetic, for a CPU
+    graph: ``preserve`` in the order given (a repeated id at its first position), then the other ids of ``ends``
+    ascending.  Returns ``(local ids of ends, nodes)``."""
+    dev = ends.device
+    p, e = preserve.long(), ends.long()
+    if p.numel() and (int(p.min()) < 0 or int(p.max()) >= num_nodes):
+        raise DGLAMDError("compact_graphs: node id out of range in always_preserve")
+    if p.numel():
+        uniq, inv = torch.unique(p, return_inverse=True)
+        at = torch.arange(p.shape[0], device=dev)
+        first = torch.full((uniq.shape[0],), p.shape[0], dtype=torch.long, device=dev).scatter_reduce(0, inv, at, "amin")
+        p = p[first[inv] == at]
+    mark = torch.full((max(1, num_nodes),), -1, dtype=torch.long, device=dev)
+    mark[p] = torch.arange(p.shape[0], device=dev)
+    new = torch.unique(e[mark[e] < 0])
+    mark[new] = p.shape[0] + torch.arange(new.shape[0], device=dev)
+    return mark[e].to(ends.dtype), torch.cat([p, new]).to(ends.dtype)
+
+
+def compact_graphs(graphs, always_preserve=None, copy_ndata=True, copy_edata=True):
+    """``dgl.compact_graphs`` (python/dgl/transforms/functional.py compact_graphs): the graphs (one, or a list over the
+    same node space) with every node dropped that is not an end point of an edge of ANY of them, except the ids of
+    ``always_preserve`` (ids, or a dict per node type).  All returned graphs share one node space, stored as
+    ``ndata[dgl.NID]``; edge order and edge features are the input's.
+
+    The node order is the block rule of ``to_block``, per node type: the ``always_preserve`` ids in the order given (a
+    repeated id keeps its first position), then every other end point ascending.  (The reference's CPU order is first
+    appearance and its GPU order is unspecified.)  A GPU graph runs csrc/exclude.hip (dgla_compact_nodes) with ONE
+    read-back per node type; a CPU graph follows the same rule in torch.  Blocks are refused."""
+    as_list = isinstance(graphs, (list, tuple))
+    graphs = list(graphs) if as_list else [graphs]
+    if not graphs:
+        return []
+    g0 = graphs[0]
+    nts, dev, idt = g0.ntypes, g0.device, g0.idtype
+    for g in graphs:
+        if g.is_block:
+            raise DGLAMDError("compact_graphs: a block is refused (its source and destination nodes are two node spaces)")
+        if g.ntypes != nts:
+            raise DGLAMDError("compact_graphs: all graphs must have the same node types in the same order")
+        if g.idtype != idt or g.device != dev:
+            raise DGLAMDError("compact_graphs: all graphs must have the same idtype and device, got %s / %s and %s / %s"
+                              % (idt, dev, g.idtype, g.device))
+        for n in nts:
+            if g.num_nodes(n) != g0.num_nodes(n):
+                raise DGLAMDError("compact_graphs: the graphs disagree on the number of nodes of type %s (%d and %d)"
+                                  % (n, g0.num_nodes(n), g.num_nodes(n)))
+    if always_preserve is None:
+        always_preserve = {}
+    elif not isinstance(always_preserve, dict):
+        if len(nts) != 1:
+            raise DGLAMDError("compact_graphs: always_preserve must be a dict of node type -> ids on a graph with "
+                              "several node types")
+        always_preserve = {nts[0]: always_preserve}
+    for n in always_preserve:
+        if n not in nts:
+            raise DGLAMDError('Node type "{}" does not exist.'.format(n))
+    edges = [{c: g.edges(etype=c) for c in g.canonical_etypes} for g in graphs]
+    local, nodes = {}, {}       # local: (graph, canonical etype, end) -> ids in the compact space
+    for ntid, n in enumerate(nts):
+        keys, parts = [], []
+        for gi, g in enumerate(graphs):
+            for c in g.canonical_etypes:
+                for end in (0, 2):
+                    if c[end] == n:
+                        keys.append((gi, c, end))
+                        parts.append(edges[gi][c][end // 2].to(idt))
+        ends = torch.cat(parts).contiguous() if parts else torch.empty(0, dtype=idt, device=dev)
+        keep = torch.as_tensor(always_preserve.get(n, [])).reshape(-1).to(device=dev, dtype=idt).contiguous()
+        if dev.type == "cuda":
+            from . import _capi
+            from .sampling import _node_map
+
+            try:
+                loc, nodes[n] = _capi.compact_nodes(keep, ends, _node_map(g0, dev, None if len(nts) == 1 else ntid))
+            except DGLAMDError as err:
+                if "node id out of range" in str(err):
+                    raise DGLAMDError("compact_graphs: node id out of range in always_preserve") from None
+                raise
+        else:
+            loc, nodes[n] = _compact_nodes_torch(keep, ends, g0.num_nodes(n))
+        at = 0
+        for key, part in zip(keys, parts):
+            local[key] = loc[at:at + part.shape[0]]
+            at += part.shape[0]
+    counts = {n: int(nodes[n].shape[0]) for n in nts}
+    out = []
+    for gi, g in enumerate(graphs):
+        cets = g.canonical_etypes
+        data = {c: (local[(gi, c, 0)], local[(gi, c, 2)]) for c in cets}
+        if len(cets) == 1 and len(nts) == 1:
+            new = graph(data[cets[0]], num_nodes=counts[nts[0]], idtype=idt, device=dev)
+        else:
+            new = heterograph(data, counts, idtype=idt, device=dev)
+        for n in nts:
+            of = new._node_frames[new.get_ntype_id(n)]
+            if copy_ndata:
+                for k, val in g._node_frames[g.get_ntype_id(n)].items():
+                    of[k] = val[nodes[n].long()]
+            of[NID] = nodes[n]
+        if copy_edata:
+            for c in cets:
+                of = new._edge_frames[new.get_etype_id(c)]
+                for k, val in g._edge_frames[g.get_etype_id(c)].items():
+                    of[k] = val
+        out.append(new)
+    return out if as_list else out[0]
+
+
 def _all_neighbors(rel, frontier, direction):
     """The predecessors (``"in"``) or successors (``"out"``) of ``frontier`` over relation ``rel``, with repeats: the
     device's all-neighbour pick on a GPU graph, the same rows of the CSC / CSR in index arithmetic on a CPU graph."""

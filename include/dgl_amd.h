@@ -1059,6 +1059,70 @@ int dgla_induced_subgraph_host(const dgla_csr* csr, const void* rows, int64_t nr
                                int eid_order, void* out_indptr, void* out_row, void* out_col, void* out_eid, int64_t* total,
                                int32_t* flags);
 
+/* ---- Edge exclusion and compaction: link-prediction batches (csrc/exclude.hip) ------------------------
+ * The steps a link-prediction / edge-classification mini-batch needs on top of neighbour sampling: drop the seed edges
+ * (and their reverses) from every sampled frontier (python/dgl/sampling/utils.py EidExcluder, dataloading/base.py
+ * find_exclude_eids) and renumber the end points of the positive and negative pair graphs into one compact node space
+ * (dgl.compact_graphs, src/graph/transform/cuda/cuda_compact_graph.cu).  The rules (ONE definition for device and host,
+ * csrc/exclude_step.h):
+ *
+ * The exclusion set X.  n_x edge ids sorted ascending, duplicates allowed, in the graph's id width.  member(X, n_x, e)
+ * is a lower-bound bisection (the first position whose id is >= e) followed by an equality test.  No atomics, nothing
+ * sized by the graph, no state to clean afterwards.
+ *
+ * Building X.  Seed edge ids ids[n] and optionally a reverse map rev[num_edges].  Slot k of the unsorted list holds
+ * ids[k] for k < n and rev[ids[k - n]] for n <= k < 2n (n slots without rev); X is the slots sorted ascending by the
+ * library's own sort.  An id outside [0, num_edges) is never used as an index: its slots hold num_edges (no edge's id)
+ * and DGLA_EXCLUDE_OUT_OF_RANGE (1) is ORed into *flags; a rev entry outside the range does the same for its slot.
+ *
+ * The frontier filter.  A frontier is a CSR over the seeds in the form dgla_sample_neighbors* returns: indptr[nr + 1],
+ * src[nnz], eids[nnz].  Entry j is kept iff !member(X, n_x, eids[j]); row i of the result holds the kept entries of
+ * [indptr[i], indptr[i + 1]) in their order, out_indptr their offsets.  Sample first, then drop: a row may come out
+ * shorter than its fanout.  Row bounds are clamped into [0, nnz].  A pure function of (frontier, X): it does not depend
+ * on the launch geometry.
+ *
+ * Compaction of one node type.  preserve[n_preserve] (repeats allowed) and ends[n_ends] (the end points of this type of
+ * every edge of every graph).  nodes = the ids of preserve in the order given, a repeated id at its first position only,
+ * then the ids of ends that are not in preserve, ascending, each once (the block rule of dgla_to_block).  local[e] = the
+ * index of ends[e] in nodes, *num_out = the length of nodes.  An id outside [0, num_nodes) ORs the bit above into
+ * *flags, is never used as an index and gets local -1.
+ *
+ * dgla_exclude_set: out[n or 2n] (device) = X.  One gather launch, then the sort.  `flags` is one device word the caller
+ *   zeroes and reads back.  `workspace` (dgla_exclude_set_workspace_bytes(bits, n, rev != NULL)) is optional: NULL takes
+ *   stream-ordered scratch; one that is too small is refused.  n < 2^30.
+ * dgla_frontier_exclude: count (a group of 16 lanes per row when nnz / num_rows <= 32, a wavefront of 64 otherwise; every
+ *   lane bisects X for its entry, the keep flags of a step are one ballot, the count their popcount; ONE KEEP BYTE per
+ *   entry goes to the workspace), the library's scan, fill (reads the keep bytes; a kept entry goes to offset + kept so
+ *   far + popcount(lower lanes)).  out_src / out_eids hold nnz entries (the upper bound), out_indptr num_rows + 1; the
+ *   first out_indptr[num_rows] entries are the result.  Plain stores, no atomics, nothing read back.  Workspace as above
+ *   (dgla_frontier_exclude_workspace_bytes(bits, num_rows, nnz)).
+ * dgla_compact_nodes: `node_map` is caller-owned int32 scratch with num_nodes entries, all -1 on entry and again on exit
+ *   (exactly the node map of dgla_to_block).  First occurrences in preserve are found with one unsigned atomic min per
+ *   id on the map; the rest is the library's sort and scan.  local[n_ends], nodes[n_preserve + n_ends], *num_out and
+ *   *flags are device memory; the caller reads the two words back together.  n_preserve + n_ends < 2^31.
+ * dgla_exclude_set_host / dgla_frontier_exclude_host / dgla_compact_nodes_host: the same rules run by the CPU on HOST
+ *   pointers (*flags, *num_out host words), no workspace, no stream, no node map.
+ * All fail with -1 and a message, before any launch, for a NULL array that is needed, an id width other than 32 / 64,
+ *   negative sizes, sizes above the bounds given and a workspace that is too small.  Empty inputs are valid. */
+#define DGLA_EXCLUDE_OUT_OF_RANGE 1
+size_t dgla_exclude_set_workspace_bytes(int idtype_bits, int64_t n, int with_reverse);
+int dgla_exclude_set(int idtype_bits, const void* ids, int64_t n, const void* rev, int64_t num_edges, void* out,
+                     int32_t* flags, void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_exclude_set_host(int idtype_bits, const void* ids, int64_t n, const void* rev, int64_t num_edges, void* out,
+                          int32_t* flags);
+size_t dgla_frontier_exclude_workspace_bytes(int idtype_bits, int64_t num_rows, int64_t nnz);
+int dgla_frontier_exclude(int idtype_bits, const void* indptr, const void* src, const void* eids, int64_t num_rows,
+                          int64_t nnz, const void* x, int64_t n_x, void* out_indptr, void* out_src, void* out_eids,
+                          void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_frontier_exclude_host(int idtype_bits, const void* indptr, const void* src, const void* eids, int64_t num_rows,
+                               int64_t nnz, const void* x, int64_t n_x, void* out_indptr, void* out_src, void* out_eids);
+size_t dgla_compact_nodes_workspace_bytes(int idtype_bits, int64_t n_preserve, int64_t n_ends);
+int dgla_compact_nodes(int idtype_bits, const void* preserve, int64_t n_preserve, const void* ends, int64_t n_ends,
+                       int32_t* node_map, int64_t num_nodes, void* local, void* nodes, int64_t* num_out, int32_t* flags,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_compact_nodes_host(int idtype_bits, const void* preserve, int64_t n_preserve, const void* ends, int64_t n_ends,
+                            int64_t num_nodes, void* local, void* nodes, int64_t* num_out, int32_t* flags);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
