@@ -20,6 +20,10 @@ from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, ad
                          from_scipy, in_subgraph, khop_in_subgraph, khop_out_subgraph, knn, knn_graph, node_subgraph, out_subgraph, remove_edges, remove_self_loop, reorder_graph,
                          segmented_knn_graph, to_bidirected, to_simple, unbatch)
 from . import geometry  # noqa: E402,F401
+from . import traversal  # noqa: E402,F401
+from . import propagate  # noqa: E402,F401
+from .traversal import bfs_edges_generator, bfs_nodes_generator, topological_nodes_generator  # noqa: E402,F401
+from .propagate import prop_edges, prop_nodes, prop_nodes_bfs, prop_nodes_topo  # noqa: E402,F401
 from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401

@@ -1270,6 +1270,55 @@ def compact_nodes_host(preserve, ends, num_nodes):
     return local, nodes[:num.value], flags.value
 
 
+TRAVERSE_BFS_NODES, TRAVERSE_BFS_EDGES, TRAVERSE_TOPO_NODES = 0, 1, 2     # the modes of dgla_traverse (include/dgl_amd.h)
+
+
+def _traverse_args(who, mode, csr, opposite, sources, gpu):
+    """The arguments the two traversal entry points share, and the outputs: ``(args, ids, num_ids, num_sections,
+    sections)``."""
+    indptr = csr._keep[0]
+    _all_on(gpu, who, indptr, sources, None if opposite is None else opposite._keep[0])
+    ns = 0
+    if mode != TRAVERSE_TOPO_NODES:
+        if sources is None or sources.dim() != 1 or not sources.is_contiguous() or sources.dtype != indptr.dtype \
+                or sources.device != indptr.device:
+            raise _lib.DGLAMDError("%s: sources must be a contiguous 1-D tensor of the csr's id type on its device" % who)
+        ns = sources.shape[0]
+    cap = csr.num_rows + (ns if mode == TRAVERSE_BFS_NODES else 0)
+    ids = torch.empty(cap, dtype=indptr.dtype, device=indptr.device)
+    sections = (ctypes.c_int64 * max(cap, 1))()
+    num_ids, num_sections = ctypes.c_int64(0), ctypes.c_int64(0)
+    args = [int(mode), ctypes.byref(csr), None if opposite is None else ctypes.byref(opposite), _ptr(sources), ns, _ptr(ids),
+            sections, ctypes.byref(num_ids), ctypes.byref(num_sections)]
+    return args, ids, num_ids, num_sections, sections
+
+
+def traverse_workspace_bytes(idtype, num_nodes):
+    """The bytes of the optional workspace of :func:`traverse` (dgla_traverse_workspace_bytes; host query)."""
+    return int(LIB.dgla_traverse_workspace_bytes(32 if idtype == torch.int32 else 64, int(num_nodes)))
+
+
+def traverse(mode, csr, opposite=None, sources=None, workspace=None):
+    """The frontiers of a BFS or of the topological order over the square CSR `csr` (dgla_traverse; the rule:
+    include/dgl_amd.h "Graph traversal"): returns ``(ids, sections)``, `ids` in the csr's id type on its device holding
+    the frontiers one after the other and `sections` the Python list of their sizes.  `mode` is TRAVERSE_BFS_NODES
+    (node ids, the sources first), TRAVERSE_BFS_EDGES (tree-edge ids) or TRAVERSE_TOPO_NODES (node ids; `opposite` is
+    the CSR of the other direction, whose row lengths are the counts).  Only sizes come back to the host: 24 bytes per
+    level.  `workspace` (uint8, :func:`traverse_workspace_bytes`) is optional."""
+    args, ids, num_ids, num_sections, sections = _traverse_args("traverse", mode, csr, opposite, sources, True)
+    check_call(LIB.dgla_traverse(*args, _ptr(workspace), workspace.numel() if workspace is not None else 0,
+                                 _stream(csr._keep[0])))
+    return ids[:num_ids.value], list(sections[:num_sections.value])
+
+
+def traverse_host(mode, csr, opposite=None, sources=None):
+    """:func:`traverse` run by the CPU on CPU tensors (dgla_traverse_host; CSRs built with :func:`host_csr`): the same
+    rule compiled for the host, bit for bit what the kernels write.  Needs no GPU."""
+    args, ids, num_ids, num_sections, sections = _traverse_args("traverse_host", mode, csr, opposite, sources, False)
+    check_call(LIB.dgla_traverse_host(*args))
+    return ids[:num_ids.value], list(sections[:num_sections.value])
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

@@ -346,6 +346,14 @@ LIB.dgla_compact_nodes.argtypes = _COMPACT + [c_void_p, c_int64, c_void_p, c_voi
                                               c_void_p]
 LIB.dgla_compact_nodes_host.restype = c_int
 LIB.dgla_compact_nodes_host.argtypes = _COMPACT + [c_int64, c_void_p, c_void_p, P(c_int64), P(ctypes.c_int32)]
+# the traversal unit: mode, csr, opposite, sources, num_sources, ids, sections, num_ids, num_sections
+_TRAVERSE = [c_int, P(CSR), P(CSR), c_void_p, c_int64, c_void_p, P(c_int64), P(c_int64), P(c_int64)]
+LIB.dgla_traverse_workspace_bytes.restype = c_size_t
+LIB.dgla_traverse_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_traverse.restype = c_int
+LIB.dgla_traverse.argtypes = _TRAVERSE + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_traverse_host.restype = c_int
+LIB.dgla_traverse_host.argtypes = _TRAVERSE
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -620,6 +620,19 @@ class DGLGraph:
         u, v = g.find_edges(eid)
         self._partial_message_passing(g, u, v, eid, None, message_func, reduce_func, apply_node_func)
 
+    def prop_nodes(self, nodes_generator, message_func, reduce_func, apply_node_func=None, etype=None):
+        """Message passing frontier by frontier: :meth:`pull` on every node frontier of ``nodes_generator`` in turn
+        (python/dgl/heterograph.py prop_nodes).  The frontiers of :mod:`dgl_amd.traversal` are already on the graph's
+        device and are used where they are."""
+        for frontier in nodes_generator:
+            self.pull(frontier, message_func, reduce_func, apply_node_func, etype=etype)
+
+    def prop_edges(self, edges_generator, message_func, reduce_func, apply_node_func=None, etype=None):
+        """Message passing frontier by frontier: :meth:`send_and_recv` on every edge frontier of ``edges_generator``
+        in turn (python/dgl/heterograph.py prop_edges)."""
+        for frontier in edges_generator:
+            self.send_and_recv(frontier, message_func, reduce_func, apply_node_func, etype=etype)
+
     # ---- structure queries used by the calls above ------------------------------------------------
     def _gather_ranges(self, fmt, ids):
         """All (position, owner) pairs of rows ``ids`` of a compressed format."""

@@ -1123,6 +1123,71 @@ int dgla_compact_nodes(int idtype_bits, const void* preserve, int64_t n_preserve
 int dgla_compact_nodes_host(int idtype_bits, const void* preserve, int64_t n_preserve, const void* ends, int64_t n_ends,
                             int64_t num_nodes, void* local, void* nodes, int64_t* num_out, int32_t* flags);
 
+/* ---- Graph traversal: BFS and topological frontiers (csrc/traversal.hip) -------------------------------
+ * The frontiers of dgl.bfs_nodes_generator, bfs_edges_generator and topological_nodes_generator, which prop_nodes_bfs /
+ * prop_nodes_topo walk (TreeLSTM, junction-tree encoders, sweeps over a DAG).  The reference has no GPU form:
+ * python/dgl/traversal.py copies the graph to the CPU on every call and runs a sequential queue there
+ * (src/graph/traversal.cc).  The rule (ONE definition for device and host, csrc/traversal_step.h):
+ *
+ * Input.  One CSR (indptr[n + 1], indices[nnz], data[nnz] = the edge-id map or NULL; int32 or int64 ids): the out-edge
+ * CSR for a forward traversal, the in-edge CSR for a reverse one.  For BFS a list of source ids.
+ *
+ * Expansion position.  Let the current frontier be f[0 .. m) and base[r] the exclusive scan of the row lengths of f[r].
+ * Entry j of row f[r] has the position x = off + base[r] + j, where off is the number of entries all earlier frontiers
+ * expanded, so positions keep growing across levels and nothing has to be cleared.  x is a 64-bit integer (a level can
+ * expand more than 2^32 entries).
+ *
+ * BFS.  Frontier 0 is the source list as given; duplicates are kept.  From a frontier, every node that no earlier
+ * frontier holds and that some entry points at takes key[v] = min x over those entries.  The next frontier is the
+ * targets whose entry holds the winning x, in ascending x; the tree edge of v is the edge id of that entry.  Self-loops
+ * and parallel edges need no special case.  The loop ends at an empty frontier.
+ *
+ * Topological.  count[v] = the row length of v in the OPPOSITE CSR (the in-degree for a forward traversal; parallel
+ * edges count once each).  Frontier 0 is the nodes with count == 0, ascending.  From a frontier, every entry into v
+ * decrements count[v] and key[v] = max x.  The next frontier is the targets with count[v] == 0 whose entry holds the
+ * winning x, in ascending x.  If fewer than n nodes were emitted by the end the call fails with "loop detected"; a
+ * self-loop is such a loop.
+ *
+ * This is the order of the reference's sequential queue, which pops the rows of a frontier in order and scans each row
+ * in order (ascending x): BFS appends v at the first entry that finds it unseen, the topological sort at the entry that
+ * takes its count to 0, which is the last.  Integer arithmetic only; min, max and the decrement commute, so the integer
+ * atomics of the kernels leave the same values whatever the arrival order: device == host bit for bit, whatever the
+ * launch geometry.  An entry whose target lies outside [0, n) is ignored and nothing is read or written through it.
+ *
+ * Result.  ids = the frontiers one after the other, sections[k] = the size of the k-th reported frontier; frontiers of
+ * size 0 are never reported.  DGLA_TRAVERSE_BFS_NODES reports every frontier, the sources included (ids holds up to
+ * n + num_sources entries); DGLA_TRAVERSE_BFS_EDGES reports the tree-edge ids of every frontier after the sources (up to
+ * n); DGLA_TRAVERSE_TOPO_NODES reports every frontier (n).  `sections` has the capacity of ids.
+ *
+ * dgla_traverse_workspace_bytes: the optional workspace: two 64-bit words per node (key, count), the node frontiers of
+ *   the edge form, and per frontier row two 64-bit words with the scan's temporary: O(n), nothing of size nnz.  0 for
+ *   another id width or num_nodes <= 0.
+ * dgla_traverse: the CSR's arrays, sources, ids and the workspace are device memory; sections, *num_ids and
+ *   *num_sections are HOST memory (the host loop knows every size).  n = csr->num_rows.  `opposite` is read only by
+ *   the topological mode (its indptr), and may be NULL otherwise; `sources` is ignored by the topological mode.  A row
+ *   of the frontier is streamed by a group of 16 lanes when csr->nnz / csr->num_rows <= 32 and by a wavefront of 64
+ *   otherwise (the bits written do not depend on it).  A level is 6 launches (row lengths, scan, mark, count, scan,
+ *   fill; a scan is 3 launches above 32 768 rows) and ONE read-back of 24 bytes; the frontiers land in ids in their
+ *   final order, without a sort.  workspace == NULL: stream-ordered scratch is allocated for the call; a workspace that
+ *   is given but too small is refused with the bytes required.  A source list longer than n takes scratch of its own
+ *   for the row arrays of frontier 0.
+ * dgla_traverse_host: the same rule run by the CPU on HOST pointers, no workspace and no stream.
+ * Both fail with -1 and a message that names the entry point, before any launch and before any array is read, for an
+ *   unknown mode, a NULL csr, an invalid csr (negative sizes, not square, NULL indptr / indices), an id width other than
+ *   32 / 64, NULL outputs, a topological call whose opposite CSR is NULL or does not match (its count array has another
+ *   number of rows or entries than the csr), and a workspace that is too small.  A source outside [0, n) is refused and
+ *   no memory is touched through it: the host twin checks the list (and that indptr is a row pointer) before anything
+ *   else; the device form finds it in its first launch, treats it as an empty row and fails at the first read-back. */
+#define DGLA_TRAVERSE_BFS_NODES 0
+#define DGLA_TRAVERSE_BFS_EDGES 1
+#define DGLA_TRAVERSE_TOPO_NODES 2
+size_t dgla_traverse_workspace_bytes(int idtype_bits, int64_t num_nodes);
+int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const void* sources, int64_t num_sources,
+                  void* ids, int64_t* sections, int64_t* num_ids, int64_t* num_sections, void* workspace,
+                  size_t workspace_bytes, void* hip_stream);
+int dgla_traverse_host(int mode, const dgla_csr* csr, const dgla_csr* opposite, const void* sources, int64_t num_sources,
+                       void* ids, int64_t* sections, int64_t* num_ids, int64_t* num_sections);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
