@@ -28,7 +28,7 @@ from .readout import *  # noqa: E402,F401,F403
 from . import sparse  # noqa: E402,F401
 from .ops import edge_softmax  # noqa: E402,F401
 from .sampling import (EID, NID, LaborSampler, NeighborSampler, PinSAGESampler, RandomWalkNeighborSampler,  # noqa: E402,F401
-                       SAINTSampler, ShaDowKHopSampler, global_uniform_negative_sampling, node2vec_random_walk, to_block)
+                       SAINTSampler, ShaDowKHopSampler, global_uniform_negative_sampling, node2vec_random_walk, select_topk, to_block)
 from . import negative_sampler  # noqa: E402,F401
 from . import dataloading  # noqa: E402,F401
 from .mm import gather_mm, segment_mm  # noqa: E402,F401

@@ -1319,6 +1319,72 @@ def traverse_host(mode, csr, opposite=None, sources=None):
     return ids[:num_ids.value], list(sections[:num_sections.value])
 
 
+_TOPK_DTYPES = dict(_DTYPES)       # the weight types of dgla_select_topk: dgla_dtype, DGLA_TOPK_I32, DGLA_TOPK_I64
+_TOPK_DTYPES.update({torch.int32: 4, torch.int64: 5})
+
+
+def select_topk_max_picks():
+    """The largest number of picks one row may yield (dgla_select_topk_max_picks; host query)."""
+    return int(LIB.dgla_select_topk_max_picks())
+
+
+def select_topk_workspace_bytes(idtype, num_seeds):
+    """The bytes of the optional workspace of :func:`select_topk` (dgla_select_topk_workspace_bytes; host query)."""
+    return int(LIB.dgla_select_topk_workspace_bytes(32 if idtype == torch.int32 else 64, int(num_seeds)))
+
+
+def _topk_args(who, csr, weight, seeds, k, ascending, gpu):
+    """The checks the two top-k entry points share, and their leading arguments."""
+    indptr = csr._keep[0]
+    _all_on(gpu, who, indptr, weight, seeds)
+    if weight.dtype not in _TOPK_DTYPES:
+        raise _lib.DGLAMDError("%s: unsupported weight dtype %s (fp32, fp64, fp16, bf16, int32 and int64 are accepted)"
+                               % (who, weight.dtype))
+    if weight.dim() != 1 or not weight.is_contiguous() or weight.shape[0] != csr.nnz or weight.device != indptr.device:
+        raise _lib.DGLAMDError("%s: weight must be a contiguous 1-D tensor with one value per edge on the csr's device" % who)
+    if seeds.dim() != 1 or not seeds.is_contiguous() or seeds.dtype != indptr.dtype or seeds.device != indptr.device:
+        raise _lib.DGLAMDError("%s: seeds must be a contiguous 1-D tensor of the csr's id type on its device" % who)
+    return [ctypes.byref(csr), _ptr(weight), _TOPK_DTYPES[weight.dtype], _ptr(seeds), seeds.shape[0], int(k),
+            1 if ascending else 0]
+
+
+def select_topk(csr, weight, seeds, k, ascending=False, workspace=None):
+    """For every seed row of `csr` the ``min(k, deg)`` entries with the largest (``ascending``: smallest) weight, best
+    first (dgla_select_topk; the rule: include/dgl_amd.h "Top-k neighbour selection").  `weight` has one value per EDGE
+    ID.  Returns ``(indptr, nbr, eids)``, a CSR over the seeds.  For ``0 <= k <= 1024`` the outputs are allocated at
+    ``num_seeds * k``, the first ``indptr[-1]`` entries are the result and nothing is read back; for ``k = -1`` or
+    ``k > 1024`` the sizes come first and the outputs have the result's length.  `workspace` (uint8,
+    :func:`select_topk_workspace_bytes`) is optional."""
+    args = _topk_args("select_topk", csr, weight, seeds, k, ascending, True)
+    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
+    indptr = torch.empty(n + 1, dtype=dt, device=dev)
+    wp, wb = _ws(workspace)
+    st = _stream(seeds)
+    if 0 <= k <= select_topk_max_picks():
+        cap = n * int(k)
+    else:
+        check_call(LIB.dgla_select_topk(*args, indptr.data_ptr(), None, None, wp, wb, st))
+        cap = int(indptr[-1])
+    nbr = torch.empty(cap, dtype=dt, device=dev)
+    eids = torch.empty(cap, dtype=dt, device=dev)
+    check_call(LIB.dgla_select_topk(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), wp, wb, st))
+    return indptr, nbr, eids
+
+
+def select_topk_host(csr, weight, seeds, k, ascending=False):
+    """:func:`select_topk` run by the CPU on CPU tensors (dgla_select_topk_host; CSRs built with :func:`host_csr`): the
+    same rule compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs
+    no GPU."""
+    args = _topk_args("select_topk_host", csr, weight, seeds, k, ascending, False)
+    n, dt = seeds.shape[0], seeds.dtype
+    indptr = torch.empty(n + 1, dtype=dt)
+    check_call(LIB.dgla_select_topk_host(*args, indptr.data_ptr(), None, None))
+    total = int(indptr[-1])
+    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
+    check_call(LIB.dgla_select_topk_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr()))
+    return indptr, nbr, eids
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))

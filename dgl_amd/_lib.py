@@ -354,6 +354,16 @@ LIB.dgla_traverse.restype = c_int
 LIB.dgla_traverse.argtypes = _TRAVERSE + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_traverse_host.restype = c_int
 LIB.dgla_traverse_host.argtypes = _TRAVERSE
+# the top-k selection unit: csr, weight, weight dtype, seeds, num_seeds, k, ascending, out_indptr, out_nbr, out_eids
+_TOPK = [P(CSR), c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]
+LIB.dgla_select_topk_max_picks.restype = c_int
+LIB.dgla_select_topk_max_picks.argtypes = []
+LIB.dgla_select_topk_workspace_bytes.restype = c_size_t
+LIB.dgla_select_topk_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_select_topk.restype = c_int
+LIB.dgla_select_topk.argtypes = _TOPK + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_select_topk_host.restype = c_int
+LIB.dgla_select_topk_host.argtypes = _TOPK
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

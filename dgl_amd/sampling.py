@@ -16,7 +16,9 @@ the visit-count top-k of csrc/pinsage.hip.  ``node2vec_random_walk`` mirrors pyt
 over csrc/node2vec.hip: the bounded second-order step of csrc/node2vec_step.h.  ``global_uniform_negative_sampling`` mirrors
 python/dgl/sampling/negative.py over csrc/negative_sampling.hip (the rule: csrc/negative_sample_step.h).  ``sample_labors`` /
 ``LaborSampler`` mirror python/dgl/sampling/labor.py and python/dgl/dataloading/labor_sampler.py over csrc/labor.hip:
-layer-neighbour sampling, one variate per source node (the rule: csrc/labor_step.h).
+layer-neighbour sampling, one variate per source node (the rule: csrc/labor_step.h).  ``select_topk`` mirrors
+``dgl.sampling.select_topk`` (python/dgl/sampling/neighbor.py:880) over csrc/topk.hip: the k heaviest (or lightest) edges of
+every node in one pass over its row (the rule: csrc/topk_step.h).
 """
 import math
 
@@ -701,6 +703,96 @@ def sample_labors(g, nodes, fanout, edge_dir="in", prob=None, importance_samplin
 
 
 DGLGraph.sample_labors = sample_labors
+
+
+def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False, copy_ndata=True, copy_edata=True,
+                output_device=None):
+    """``dgl.sampling.select_topk`` (python/dgl/sampling/neighbor.py:880): for every node in ``nodes`` the ``k`` inbound
+    (``edge_dir="out"``: outbound) edges per edge type with the largest (``ascending``: smallest) weight, all of them
+    when it has no more or ``k == -1``.
+
+    ``k`` is an int or a dict that names every edge type; ``weight`` is the name of an edge feature with one element per
+    edge (fp32, fp64, fp16, bf16, int32 or int64), which every edge type must have; ``nodes`` is an id tensor, a dict per
+    node type, or None for all nodes.  A node listed twice is selected twice.
+
+    Returns a graph with all nodes of ``g`` and only the selected edges, ordered by node in the given order and then by
+    rank, best first; ``edata[dgl.EID]`` holds their ids in ``g``, the node features are those of ``g`` (the same
+    tensors, ``copy_ndata``) and the edge features follow the selected edges (``copy_edata``).
+
+    A GPU graph runs the kernels of csrc/topk.hip, a CPU graph the same rule compiled for the host
+    (dgla_select_topk_host; the reference has the CPU form only).  The rule is written in include/dgl_amd.h, "Top-k
+    neighbour selection": NaN loses in both directions and equal weights are ordered by edge id, which is one of the
+    orders the reference's unstable sort may produce.  A node that would yield more than 1024 edges is refused."""
+    who = "select_topk"
+    if edge_dir not in ("in", "out"):
+        raise ValueError("edge_dir must be 'in' or 'out'")
+    if not isinstance(weight, str):
+        raise _DGLError("%s: weight is the name of an edge feature, got %r" % (who, type(weight).__name__))
+    if nodes is None:
+        nodes = {n: torch.arange(g._graph.num_nodes(i)) for i, n in enumerate(g.ntypes)}
+    elif not isinstance(nodes, dict):
+        if len(g.ntypes) != 1:
+            raise _DGLError("Must specify node type when the graph is not homogeneous.")
+        nodes = {g.ntypes[0]: nodes}
+    for n in nodes:
+        if n not in g.ntypes:
+            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    if isinstance(k, dict) and len(k) != len(g.canonical_etypes):
+        raise _DGLError("K value must be specified for each edge type if a dict is provided.")
+    ks = _per_etype(g, k, "k")
+    weights = []
+    for etid, c in enumerate(g.canonical_etypes):
+        frame = g._edge_frames[etid]
+        if weight not in frame:
+            raise _DGLError('Edge weights "{}" do not exist for relation graph "{}".'.format(weight, c))
+        weights.append(frame[weight])
+    rels, picked = [], []
+    for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
+        rel = g._graph.relations[etid]
+        dev, idt = rel.device, rel.idtype
+        w = weights[etid]
+        if w.dim() == 0 or w.shape[0] != rel.num_edges or w.numel() != rel.num_edges:
+            raise _DGLError('%s: edge weights "%s" of relation graph "%s" must have one element per edge (%d), got shape %s'
+                            % (who, weight, g.canonical_etypes[etid], rel.num_edges, tuple(w.shape)))
+        seeds = nodes.get(d_t if edge_dir == "in" else s_t)
+        kk = int(ks[etid])
+        if seeds is None or kk == 0 or rel.num_edges == 0 or torch.as_tensor(seeds).numel() == 0:
+            own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
+        else:
+            seeds = _node_ids(seeds, dev, idt)
+            w = w.to(dev).reshape(-1).contiguous()
+            fmt = rel.csc() if edge_dir == "in" else rel.csr()
+            cols = rel.num_src if edge_dir == "in" else rel.num_dst
+            if dev.type == "cuda":
+                csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
+                indptr, nbr, eids = _capi.select_topk(csr, w, seeds, kk, ascending)
+            else:
+                csr = _capi.host_csr(fmt[0].contiguous(), fmt[1].contiguous(), None if fmt[2] is None else fmt[2].contiguous(),
+                                     cols)
+                indptr, nbr, eids = _capi.select_topk_host(csr, w, seeds, kk, ascending)
+            n_e = int(indptr[-1])
+            own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
+            nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
+        src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
+        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev))
+        picked.append(eids)
+    gi = g._graph
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
+                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
+    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
+        for i, fr in enumerate(g._node_frames):
+            for key, val in fr.items():
+                out._node_frames[i][key] = val
+    for etid, e in enumerate(picked):
+        if copy_edata:
+            for key, val in g._edge_frames[etid].items():
+                if key != EID:
+                    out._edge_frames[etid][key] = val[e.long()]
+        out._edge_frames[etid][EID] = e
+    return out if output_device is None else out.to(output_device)
+
+
+DGLGraph.select_topk = select_topk
 
 
 class LaborSampler:

@@ -1188,6 +1188,61 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
 int dgla_traverse_host(int mode, const dgla_csr* csr, const dgla_csr* opposite, const void* sources, int64_t num_sources,
                        void* ids, int64_t* sections, int64_t* num_ids, int64_t* num_sections);
 
+/* ---- Top-k neighbour selection (csrc/topk.hip) ------------------------------------------------------------
+ * dgl.sampling.select_topk: for every seed the k in- or out-edges with the largest (or smallest) weight.  The reference
+ * has no GPU form: python/dgl/sampling/neighbor.py asserts a CPU graph and sorts every row with std::sort
+ * (src/array/cpu/rowwise_topk.cc).  The rule (ONE definition for device and host, csrc/topk_step.h):
+ *
+ * Input.  One CSR (indptr[num_rows + 1], indices[nnz], data[nnz] = the edge-id map or NULL; int32 or int64 ids): the
+ * in-edge CSR for edge_dir = "in", the out-edge CSR for "out".  `weight` holds one value per EDGE ID.
+ *
+ * Key of an edge.  An order-preserving map of its weight to an unsigned integer: 32 bits for fp32 / fp16 / bf16 / int32,
+ * 64 bits for fp64 / int64.  Floats: -0.0 becomes +0.0, then a set sign bit complements the pattern and a clear one sets
+ * it (the sign-flip map).  fp16 and bf16 widen to the fp32 pattern first, exactly.  Signed integers have their sign bit
+ * flipped.  ascending complements the key.  NaN loses to every number in both directions: after the direction is applied
+ * its key is 0, below the key of every float that is a number.  An edge id outside [0, nnz) reads no weight and gets
+ * key 0 as well.
+ *
+ * Total order within a row.  Larger key first; among equal keys the smaller EDGE ID first (not the CSR position, so the
+ * result is a function of (graph, weights) whichever sparse format is read); among equal edge ids, which only a
+ * malformed edge-id map produces, the smaller position.  The order is strict.  The reference's std::sort is unstable:
+ * its order among equal weights is unspecified, and this order is one of its possible results; on tie-free weights the
+ * two agree element for element.
+ *
+ * Picks of seed i.  picks = min(k, deg); k = -1: deg; k = 0: none.  The picks are the first `picks` entries of the row in
+ * that order, emitted in rank order (best first).  Output is a CSR over the seeds: out_indptr[num_seeds + 1], out_nbr
+ * (the `indices` entry of every pick) and out_eids, of out_indptr[num_seeds] entries.  A seed listed twice is selected
+ * twice.  Row bounds are clamped into [0, nnz], so a malformed indptr reads nothing outside the arrays.  Integer
+ * comparisons only: device == host bit for bit, whatever the launch geometry.
+ *
+ * dgla_select_topk_max_picks: 1024, the largest number of picks one row may yield.
+ * dgla_select_topk_workspace_bytes: the optional workspace: one 64-bit word per seed, the scan's temporary and 8 flag
+ *   words.  0 for another id width or num_seeds <= 0.
+ * dgla_select_topk: all arrays are device memory.  weight_dtype is a dgla_dtype code, DGLA_TOPK_I32 or DGLA_TOPK_I64.
+ *   out_nbr == NULL: the sizes only (out_indptr).  For 0 <= k <= 1024 nothing is read back (the call can be captured when
+ *   a workspace is given; allocate num_seeds * k entries) and a seed outside [0, num_rows) is an empty row that touches
+ *   no memory.  For k = -1 or k > 1024 the pick counts depend on the degrees: the call reads 8 flag words back after the
+ *   count pass and before any selection launch, and refuses a seed outside [0, num_rows) and a row that yields more than
+ *   1024 picks ("a row yields N picks, which exceeds the limit of 1024"); the library stays usable afterwards.  A row is
+ *   selected by a group of 16 lanes (at most 32 picks, csr->nnz / csr->num_rows <= 32), a wavefront of 64 (at most 128
+ *   picks) or a workgroup of 256 (at most 1024), in ONE pass over the row: every selected row's edge ids and weights
+ *   are read once.  workspace == NULL: stream-ordered scratch is allocated for the call; a workspace that is given but
+ *   too small is refused with the bytes required.
+ * dgla_select_topk_host: the same rule run by the CPU on HOST pointers, no workspace and no stream.  It checks the seeds
+ *   and the pick counts before it writes anything, for every k.
+ * Both fail with -1 and a message that names the entry point, before any launch and before any array is read, for a NULL
+ *   csr, an invalid csr, an id width other than 32 / 64, a NULL weight, an unsupported weight dtype, NULL seeds or
+ *   outputs, k < -1 and a workspace that is too small. */
+#define DGLA_TOPK_I32 4
+#define DGLA_TOPK_I64 5
+int dgla_select_topk_max_picks(void);
+size_t dgla_select_topk_workspace_bytes(int idtype_bits, int64_t num_seeds);
+int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds, int64_t num_seeds,
+                     int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids, void* workspace,
+                     size_t workspace_bytes, void* hip_stream);
+int dgla_select_topk_host(const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds, int64_t num_seeds,
+                          int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
