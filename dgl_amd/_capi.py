@@ -51,6 +51,17 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _ws(workspace):
+    """(pointer, bytes) of an optional workspace.  Workspaces are uint8 tensors, so numel() is already the byte count;
+    the product with element_size() only keeps a caller's tensor of another dtype honest."""
+    return _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+
+
+def _id_bits(idtype):
+    """The id width of a torch id dtype, for the size queries that take no tensor."""
+    return 32 if idtype == torch.int32 else 64
+
+
 def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -123,8 +134,7 @@ def spmm_csr(op, reduce, csr, ufeat, efeat, out, arg_u=None, arg_e=None, workspa
         (_lib.DGLA_SPLIT_KEEP if split_keep else 0) | (_lib.DGLA_PREPARE_ONLY if prepare_only else 0)
     check_call(LIB.dgla_spmm_csr(
         op.encode(), reduce.encode(), ctypes.byref(csr), _DTYPES[out.dtype], ctypes.byref(tu),
-        ctypes.byref(te), ctypes.byref(to), _ptr(arg_u), _ptr(arg_e), _ptr(workspace),
-        0 if workspace is None else workspace.numel() * workspace.element_size(), flags,
+        ctypes.byref(te), ctypes.byref(to), _ptr(arg_u), _ptr(arg_e), *_ws(workspace), flags,
         _stream(out)))
 
 
@@ -159,8 +169,7 @@ def spmm_csr_stacked(op, csr, rel, ufeats, efeats, out, workspace, u_table=None,
     flags = (_lib.DGLA_ACCUMULATE if accumulate else 0) | (_lib.DGLA_PLAN_VALID if plan_valid else 0)
     check_call(LIB.dgla_spmm_csr_stacked(
         op.encode(), ctypes.byref(csr), rel.data_ptr(), n_rel, _DTYPES[out.dtype], ctypes.byref(tu),
-        ctypes.byref(te), _ptr(u_table), _ptr(e_table), ctypes.byref(to), _ptr(workspace),
-        0 if workspace is None else workspace.numel() * workspace.element_size(), flags,
+        ctypes.byref(te), _ptr(u_table), _ptr(e_table), ctypes.byref(to), *_ws(workspace), flags,
         _stream(out)))
     return u_table, e_table
 
@@ -194,8 +203,7 @@ def edge_softmax_workspace_bytes(csr, dtype, dim):
 
 
 def _ws_args(workspace, plan_valid):
-    return (_ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
-            _lib.DGLA_PLAN_VALID if plan_valid else 0)
+    return (*_ws(workspace), _lib.DGLA_PLAN_VALID if plan_valid else 0)
 
 
 def edge_softmax_forward(csr, score, out, workspace=None, plan_valid=False, out_position=False):
@@ -256,7 +264,7 @@ def gat_attention_forward(csc, ft, el, er, slope, out, mz, workspace):
         raise _lib.DGLAMDError("gat_attention: mz is fp32 whatever the operands' dtype")
     check_call(LIB.dgla_gat_attention_forward(ctypes.byref(csc), _DTYPES[ft.dtype], ctypes.byref(tf), ctypes.byref(tl),
                                               ctypes.byref(tr), float(slope), ctypes.byref(to), mz.data_ptr(),
-                                              _ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                              *_ws(workspace),
                                               _stream(out)))
 
 
@@ -269,7 +277,7 @@ def gat_attention_backward(csc, csr, ft, el, er, out, mz, dout, slope, d_ft, d_e
                                                ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
                                                ctypes.byref(ts[3]), mz.data_ptr(), ctypes.byref(ts[4]), float(slope),
                                                ctypes.byref(ts[5]), ctypes.byref(ts[6]), ctypes.byref(ts[7]),
-                                               _ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                               *_ws(workspace),
                                                _stream(d_ft)))
 
 
@@ -285,8 +293,7 @@ def gat_attention_train_forward(csc, ft, el, er, slope, p, seed, out, mz, worksp
         raise _lib.DGLAMDError("gat_attention: mz is fp32 whatever the operands' dtype")
     check_call(LIB.dgla_gat_attention_train_forward(ctypes.byref(csc), _DTYPES[ft.dtype], ctypes.byref(tf), ctypes.byref(tl),
                                                     ctypes.byref(tr), float(slope), float(p), int(seed), ctypes.byref(to),
-                                                    mz.data_ptr(), _ptr(workspace),
-                                                    0 if workspace is None else workspace.numel(), _stream(out)))
+                                                    mz.data_ptr(), *_ws(workspace), _stream(out)))
 
 
 def gat_attention_train_backward(csc, csr, ft, el, er, mz, dout, slope, p, seed, d_ft, d_el, d_er, workspace):
@@ -299,7 +306,7 @@ def gat_attention_train_backward(csc, csr, ft, el, er, mz, dout, slope, p, seed,
                                                      ctypes.byref(ts[0]), ctypes.byref(ts[1]), ctypes.byref(ts[2]),
                                                      mz.data_ptr(), ctypes.byref(ts[3]), float(slope), float(p), int(seed),
                                                      ctypes.byref(ts[4]), ctypes.byref(ts[5]), ctypes.byref(ts[6]),
-                                                     _ptr(workspace), 0 if workspace is None else workspace.numel(),
+                                                     *_ws(workspace),
                                                      _stream(d_ft)))
 
 
@@ -380,8 +387,7 @@ def segment_reduce(reduce, feat, offsets, out, arg=None, workspace=None, plan_va
     _require_gpu(offsets)
     check_call(LIB.dgla_segment_reduce(
         reduce.encode(), _idbits(offsets), _DTYPES[out.dtype], ctypes.byref(tf),
-        offsets.data_ptr(), offsets.shape[0] - 1, ctypes.byref(to), _ptr(arg), _ptr(workspace),
-        0 if workspace is None else workspace.numel() * workspace.element_size(),
+        offsets.data_ptr(), offsets.shape[0] - 1, ctypes.byref(to), _ptr(arg), *_ws(workspace),
         _lib.DGLA_PLAN_VALID if plan_valid else 0, _stream(out)))
 
 
@@ -463,8 +469,7 @@ def spmm_csr_masked(csr, ufeat, mask, out, workspace=None, accumulate=False, pla
     tu, to = _tensor(ufeat, keep), _tensor(out, keep)
     flags = (_lib.DGLA_ACCUMULATE if accumulate else 0) | (_lib.DGLA_PLAN_VALID if plan_valid else 0)
     check_call(LIB.dgla_spmm_csr_masked(ctypes.byref(csr), _DTYPES[out.dtype], ctypes.byref(tu), _ptr(mask),
-                                        ctypes.byref(to), _ptr(workspace),
-                                        0 if workspace is None else workspace.numel() * workspace.element_size(), flags,
+                                        ctypes.byref(to), *_ws(workspace), flags,
                                         _stream(out)))
 
 
@@ -546,10 +551,6 @@ def csr_mm_row_classes():
 
 def csr_mm_workspace_bytes(a, b):
     return LIB.dgla_csr_mm_workspace_bytes(ctypes.byref(a), ctypes.byref(b))
-
-
-def _ws(workspace):
-    return _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
 
 
 def csr_mm(a, a_w, b, b_w, workspace=None):
@@ -946,7 +947,7 @@ def _knn_args(who, x, y, x_offsets, y_offsets, k, idtype, with_dist, gpu):
     ids = torch.empty((2, slots), dtype=idtype, device=x.device)
     dist = torch.empty(slots, dtype=x.dtype, device=x.device) if with_dist else None
     args = [_ptr(x), x.shape[0], _ptr(y), num_y, _DTYPES[x.dtype], x.shape[1], xo, yo, num_segs, k,
-            32 if idtype == torch.int32 else 64, _ptr(ids), _ptr(dist)]
+            _id_bits(idtype), _ptr(ids), _ptr(dist)]
     return args, num_segs, ids, dist
 
 
@@ -1029,14 +1030,11 @@ def neighbor_matching(csr, weight=None, rng_seed=0, max_rounds=MATCHING_MAX_ROUN
     n = csr.num_rows
     label = torch.empty(n, dtype=indptr.dtype, device=indptr.device)
     rounds = ctypes.c_int64(0)
-    ws_bytes = workspace.numel() if workspace is not None else 0
     st = _stream(indptr)
-    check_call(LIB.dgla_neighbor_matching(*args, int(batch_rounds), _ptr(label), ctypes.byref(rounds), _ptr(workspace),
-                                          ws_bytes, st))
+    check_call(LIB.dgla_neighbor_matching(*args, int(batch_rounds), _ptr(label), ctypes.byref(rounds), *_ws(workspace), st))
     if relabel:
         out = torch.empty_like(label)
-        check_call(LIB.dgla_neighbor_matching_relabel(_ptr(label), csr.idtype_bits, n, _ptr(out), _ptr(workspace), ws_bytes,
-                                                      st))
+        check_call(LIB.dgla_neighbor_matching_relabel(_ptr(label), csr.idtype_bits, n, _ptr(out), *_ws(workspace), st))
         label = out
     return label, rounds.value
 
@@ -1088,6 +1086,12 @@ def _flag_error(who, flags):
         raise _lib.DGLAMDError("%s: duplicate node id" % who)
 
 
+def _id_tensor_ok(who, name, t, like):
+    """`t` is a contiguous 1-D tensor with the dtype and the device of `like`, an array of the csr."""
+    if t is None or t.dim() != 1 or not t.is_contiguous() or t.dtype != like.dtype or t.device != like.device:
+        raise _lib.DGLAMDError("%s: %s must be a contiguous 1-D tensor of the csr's id type on its device" % (who, name))
+
+
 def _subgraph_rows_ok(who, csr, rows):
     if rows.dim() != 1 or not rows.is_contiguous() or _idbits(rows) != csr.idtype_bits:
         raise _lib.DGLAMDError("%s: rows must be a contiguous 1-D tensor of the csr's id type" % who)
@@ -1119,7 +1123,7 @@ def induced_subgraph(csr, rows, col_map, eid_order=True, col_ids=None, flags=Non
         ws = workspace if workspace is not None else _workspace(need, dev)
         out_indptr = torch.empty(nr + 1, dtype=dt, device=dev)
         check_call(LIB.dgla_induced_subgraph_count(ctypes.byref(csr), _ptr(rows), nr, _ptr(col_map), _ptr(out_indptr),
-                                                   _ptr(ws), ws.numel() if ws is not None else 0, st))
+                                                   *_ws(ws), st))
         total, fl = torch.stack([out_indptr[nr].long(), flags[0].long()]).tolist()
         _flag_error(who, fl)
         row = torch.empty(total, dtype=dt, device=dev)
@@ -1128,8 +1132,7 @@ def induced_subgraph(csr, rows, col_map, eid_order=True, col_ids=None, flags=Non
         if workspace is None and eid_order:
             ws = _workspace(LIB.dgla_induced_subgraph_workspace_bytes(bits, nr, total), dev)
         check_call(LIB.dgla_induced_subgraph_fill(ctypes.byref(csr), _ptr(rows), nr, _ptr(col_map), _ptr(out_indptr), total,
-                                                  _ptr(row), _ptr(col), _ptr(eid), 1 if eid_order else 0, _ptr(ws),
-                                                  ws.numel() if ws is not None else 0, st))
+                                                  _ptr(row), _ptr(col), _ptr(eid), 1 if eid_order else 0, *_ws(ws), st))
     finally:
         if col_ids is not None:
             node_map_clear(col_ids, col_map)
@@ -1185,8 +1188,8 @@ def exclude_set(ids, num_edges, reverse=None, workspace=None):
     if n == 0:
         return out
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    check_call(LIB.dgla_exclude_set(bits, _ptr(ids), n, _ptr(reverse), int(num_edges), _ptr(out), _ptr(flags), _ptr(workspace),
-                                    workspace.numel() if workspace is not None else 0, _stream(ids)))
+    check_call(LIB.dgla_exclude_set(bits, _ptr(ids), n, _ptr(reverse), int(num_edges), _ptr(out), _ptr(flags),
+                                    *_ws(workspace), _stream(ids)))
     if int(flags.item()) & EXCLUDE_OUT_OF_RANGE:
         raise _lib.DGLAMDError("%s: edge id out of range" % who)
     return out
@@ -1215,8 +1218,7 @@ def frontier_exclude(indptr, src, eids, x, workspace=None):
         raise _lib.DGLAMDError("%s: indptr needs at least one entry, src and eids one length" % who)
     out_indptr, out_src, out_eids = torch.empty_like(indptr), torch.empty_like(src), torch.empty_like(eids)
     check_call(LIB.dgla_frontier_exclude(bits, _ptr(indptr), _ptr(src), _ptr(eids), nr, nnz, _ptr(x), x.shape[0],
-                                         _ptr(out_indptr), _ptr(out_src), _ptr(out_eids), _ptr(workspace),
-                                         workspace.numel() if workspace is not None else 0, _stream(indptr)))
+                                         _ptr(out_indptr), _ptr(out_src), _ptr(out_eids), *_ws(workspace), _stream(indptr)))
     return out_indptr, out_src, out_eids
 
 
@@ -1250,8 +1252,7 @@ def compact_nodes(preserve, ends, node_map, workspace=None):
     nodes = torch.empty(np_ + ne, dtype=dt, device=dev)
     words = torch.zeros(2, dtype=torch.int64, device=dev)       # [node count, flags (its low int32)]
     check_call(LIB.dgla_compact_nodes(bits, _ptr(preserve), np_, _ptr(ends), ne, _ptr(node_map), node_map.shape[0], _ptr(local),
-                                      _ptr(nodes), words.data_ptr(), words.data_ptr() + 8, _ptr(workspace),
-                                      workspace.numel() if workspace is not None else 0, _stream(ends)))
+                                      _ptr(nodes), words.data_ptr(), words.data_ptr() + 8, *_ws(workspace), _stream(ends)))
     num, fl = words.tolist()
     if fl & EXCLUDE_OUT_OF_RANGE:
         raise _lib.DGLAMDError("%s: node id out of range" % who)
@@ -1280,9 +1281,7 @@ def _traverse_args(who, mode, csr, opposite, sources, gpu):
     _all_on(gpu, who, indptr, sources, None if opposite is None else opposite._keep[0])
     ns = 0
     if mode != TRAVERSE_TOPO_NODES:
-        if sources is None or sources.dim() != 1 or not sources.is_contiguous() or sources.dtype != indptr.dtype \
-                or sources.device != indptr.device:
-            raise _lib.DGLAMDError("%s: sources must be a contiguous 1-D tensor of the csr's id type on its device" % who)
+        _id_tensor_ok(who, "sources", sources, indptr)
         ns = sources.shape[0]
     cap = csr.num_rows + (ns if mode == TRAVERSE_BFS_NODES else 0)
     ids = torch.empty(cap, dtype=indptr.dtype, device=indptr.device)
@@ -1295,7 +1294,7 @@ def _traverse_args(who, mode, csr, opposite, sources, gpu):
 
 def traverse_workspace_bytes(idtype, num_nodes):
     """The bytes of the optional workspace of :func:`traverse` (dgla_traverse_workspace_bytes; host query)."""
-    return int(LIB.dgla_traverse_workspace_bytes(32 if idtype == torch.int32 else 64, int(num_nodes)))
+    return int(LIB.dgla_traverse_workspace_bytes(_id_bits(idtype), int(num_nodes)))
 
 
 def traverse(mode, csr, opposite=None, sources=None, workspace=None):
@@ -1306,8 +1305,7 @@ def traverse(mode, csr, opposite=None, sources=None, workspace=None):
     the CSR of the other direction, whose row lengths are the counts).  Only sizes come back to the host: 24 bytes per
     level.  `workspace` (uint8, :func:`traverse_workspace_bytes`) is optional."""
     args, ids, num_ids, num_sections, sections = _traverse_args("traverse", mode, csr, opposite, sources, True)
-    check_call(LIB.dgla_traverse(*args, _ptr(workspace), workspace.numel() if workspace is not None else 0,
-                                 _stream(csr._keep[0])))
+    check_call(LIB.dgla_traverse(*args, *_ws(workspace), _stream(csr._keep[0])))
     return ids[:num_ids.value], list(sections[:num_sections.value])
 
 
@@ -1330,7 +1328,7 @@ def select_topk_max_picks():
 
 def select_topk_workspace_bytes(idtype, num_seeds):
     """The bytes of the optional workspace of :func:`select_topk` (dgla_select_topk_workspace_bytes; host query)."""
-    return int(LIB.dgla_select_topk_workspace_bytes(32 if idtype == torch.int32 else 64, int(num_seeds)))
+    return int(LIB.dgla_select_topk_workspace_bytes(_id_bits(idtype), int(num_seeds)))
 
 
 def _topk_args(who, csr, weight, seeds, k, ascending, gpu):
@@ -1342,8 +1340,7 @@ def _topk_args(who, csr, weight, seeds, k, ascending, gpu):
                                % (who, weight.dtype))
     if weight.dim() != 1 or not weight.is_contiguous() or weight.shape[0] != csr.nnz or weight.device != indptr.device:
         raise _lib.DGLAMDError("%s: weight must be a contiguous 1-D tensor with one value per edge on the csr's device" % who)
-    if seeds.dim() != 1 or not seeds.is_contiguous() or seeds.dtype != indptr.dtype or seeds.device != indptr.device:
-        raise _lib.DGLAMDError("%s: seeds must be a contiguous 1-D tensor of the csr's id type on its device" % who)
+    _id_tensor_ok(who, "seeds", seeds, indptr)
     return [ctypes.byref(csr), _ptr(weight), _TOPK_DTYPES[weight.dtype], _ptr(seeds), seeds.shape[0], int(k),
             1 if ascending else 0]
 
@@ -1387,7 +1384,7 @@ def select_topk_host(csr, weight, seeds, k, ascending=False):
 
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
-    return int(LIB.dgla_pinsage_max_samples(32 if idtype == torch.int32 else 64))
+    return int(LIB.dgla_pinsage_max_samples(_id_bits(idtype)))
 
 
 def pinsage_size_classes():

@@ -73,7 +73,7 @@ size_t dgla_coo_to_csr_workspace_bytes(int idtype_bits, int64_t num_rows, int64_
 static int coo_to_csr_impl(int idtype_bits, int64_t num_rows, int64_t num_minor, int64_t nnz, const void* row,
                            const void* col, const void* eids, void* indptr, void* indices, void* eids_out,
                            void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (!idbits_ok(idtype_bits)) return fail("idtype must be int32 or int64");
   if (num_rows < 0 || nnz < 0) return fail("negative size");
   if (!indptr) return fail("indptr is null");
   if (nnz > 0 && (!row || !col || !indices || !eids_out)) return fail("coo / output arrays are null");

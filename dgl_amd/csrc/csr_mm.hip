@@ -331,10 +331,8 @@ int count_rows(const Src& src, int64_t num_rows, bool any_terms, void* c_indptr,
   }
   hipLaunchKernelGGL(indptr_kernel<Idx>, dim3(static_cast<unsigned>((num_rows + 1 + 255) / 256)), dim3(256), 0, s, cnt,
                      num_rows + 1, static_cast<Idx*>(c_indptr));
-  DGLA_CHECK_HIP(hipGetLastError());
   int64_t nnz = 0;
-  if (any_terms) DGLA_CHECK_HIP(hipMemcpyAsync(&nnz, cnt + num_rows, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  DGLA_CHECK_HIP(hipStreamSynchronize(s));
+  if (read_back(&nnz, cnt + num_rows, sizeof(int64_t), s)) return -1;  // (0 without terms: cnt was cleared above)
   if (sizeof(Idx) == 4 && nnz > 0x7fffffffLL)
     return fail("csr_mm: the result has " + std::to_string(nnz) + " entries, which int32 ids cannot address; use int64 ids");
   *nnz_out = nnz;
@@ -351,23 +349,21 @@ int fill_rows(const Src& src, int64_t num_rows, const void* c_indptr, void* c_in
 
 template <typename Idx>
 Operand<Idx> operand_of(const dgla_csr* c, const void* w) {
-  return Operand<Idx>{static_cast<const Idx*>(c->indptr), static_cast<const Idx*>(c->indices), static_cast<const Idx*>(c->data), w};
+  const TypedCsr<Idx> g(c);
+  return Operand<Idx>{g.indptr, g.indices, g.data, w};
 }
 
-int check_csr(const dgla_csr* c, const char* name) {
-  if (!c) return fail(std::string(name) + " is null");
-  if (c->idtype_bits != 32 && c->idtype_bits != 64) return fail(std::string(name) + ": idtype must be int32 or int64");
-  if (c->num_rows < 0 || c->num_cols < 0 || c->nnz < 0) return fail(std::string(name) + ": negative size");
-  if (c->num_rows > 0 && !c->indptr) return fail(std::string(name) + ": indptr is null");
-  if (c->nnz > 0 && !c->indices) return fail(std::string(name) + ": indices is null");
+// one operand; `who` names the entry point and the operand
+int check_operand(const char* who, const dgla_csr* c) {
+  if (check_csr(who, c, kCsrCols | kCsrEmptyIndptr)) return -1;
   if (c->idtype_bits == 32 && (c->num_rows > 0x7fffffffLL || c->num_cols > 0x7fffffffLL || c->nnz > 0x7fffffffLL))
-    return fail(std::string(name) + ": int32 ids cannot address this matrix");
-  if (c->num_rows > 0x7fffffffLL) return fail(std::string(name) + ": more than 2^31 - 1 rows");   // (one workgroup per row)
+    return fail(who, "int32 ids cannot address this matrix");
+  if (c->num_rows > 0x7fffffffLL) return fail(who, "more than 2^31 - 1 rows");   // (one workgroup per row)
   return 0;
 }
 
 int check_mm(const dgla_csr* a, const dgla_csr* b) {
-  if (check_csr(a, "csr_mm: a") || check_csr(b, "csr_mm: b")) return -1;
+  if (check_operand("csr_mm: a", a) || check_operand("csr_mm: b", b)) return -1;
   if (a->idtype_bits != b->idtype_bits) return fail("csr_mm: the operands have different id types");
   if (a->num_cols != b->num_rows)
     return fail("csr_mm: a has " + std::to_string(a->num_cols) + " columns but b has " + std::to_string(b->num_rows) + " rows");
@@ -377,7 +373,7 @@ int check_mm(const dgla_csr* a, const dgla_csr* b) {
 int check_sum(const dgla_csr* const* ops, int n) {
   if (!ops || n < 1) return fail("csr_sum: at least one operand is required");
   for (int k = 0; k < n; ++k) {
-    if (check_csr(ops[k], "csr_sum: operand")) return -1;
+    if (check_operand("csr_sum: operand", ops[k])) return -1;
     if (ops[k]->idtype_bits != ops[0]->idtype_bits) return fail("csr_sum: the operands have different id types");
     if (ops[k]->num_rows != ops[0]->num_rows || ops[k]->num_cols != ops[0]->num_cols)
       return fail("csr_sum: the operands have different shapes");
@@ -614,7 +610,7 @@ int dgla_csr_sum_fill(const dgla_csr* const* ops, int n, dgla_dtype dtype, const
 }
 
 int dgla_csr_mask(const dgla_csr* a, dgla_dtype dtype, const void* a_w, const dgla_coo* b, void* out, void* hip_stream) {
-  if (check_csr(a, "csr_mask: a")) return -1;
+  if (check_operand("csr_mask: a", a)) return -1;
   if (!b) return fail("csr_mask: b is null");
   if (b->idtype_bits != a->idtype_bits) return fail("csr_mask: the operands have different id types");
   if (b->num_rows != a->num_rows || b->num_cols != a->num_cols) return fail("csr_mask: the operands have different shapes");

@@ -266,44 +266,41 @@ CompactLayout compact_layout(int idtype_bits, int64_t np, int64_t ne) {
 }
 
 bool sizes_ok(int idtype_bits, int64_t a, int64_t b) {
-  return (idtype_bits == 32 || idtype_bits == 64) && a >= 0 && b >= 0 && a < (int64_t(1) << 31) && b < (int64_t(1) << 31);
+  return idbits_ok(idtype_bits) && a >= 0 && b >= 0 && a < (int64_t(1) << 31) && b < (int64_t(1) << 31);
 }
 
 int check_set(const char* who, int idtype_bits, const void* ids, int64_t n, int64_t num_edges, const void* out,
               const void* flags) {
-  const std::string w = std::string(who) + ": ";
-  if (idtype_bits != 32 && idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (n < 0 || num_edges < 0) return fail(w + "negative size");
-  if (n >= (int64_t(1) << 30)) return fail(w + "n must be below 2^30, got " + std::to_string(n));
-  if (idtype_bits == 32 && num_edges > INT32_MAX) return fail(w + "num_edges does not fit the id type");
-  if (n > 0 && (!ids || !out)) return fail(w + "ids / out are null");
-  if (!flags) return fail(w + "flags is null");
+  if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
+  if (n < 0 || num_edges < 0) return fail(who, "negative size");
+  if (n >= (int64_t(1) << 30)) return fail(who, "n must be below 2^30, got " + std::to_string(n));
+  if (idtype_bits == 32 && num_edges > INT32_MAX) return fail(who, "num_edges does not fit the id type");
+  if (n > 0 && (!ids || !out)) return fail(who, "ids / out are null");
+  if (!flags) return fail(who, "flags is null");
   return 0;
 }
 
 int check_filter(const char* who, int idtype_bits, const void* indptr, const void* src, const void* eids, int64_t nr,
                  int64_t nnz, const void* x, int64_t n_x, const void* out_indptr, const void* out_src, const void* out_eids) {
-  const std::string w = std::string(who) + ": ";
-  if (idtype_bits != 32 && idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (nr < 0 || nnz < 0 || n_x < 0) return fail(w + "negative size");
-  if (nr >= (int64_t(1) << 31)) return fail(w + "the number of rows must be below 2^31, got " + std::to_string(nr));
-  if (!indptr || !out_indptr) return fail(w + "indptr / out_indptr are null");
-  if (nnz > 0 && (!src || !eids || !out_src || !out_eids)) return fail(w + "src / eids / out_src / out_eids are null");
-  if (n_x > 0 && !x) return fail(w + "x is null");
+  if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
+  if (nr < 0 || nnz < 0 || n_x < 0) return fail(who, "negative size");
+  if (nr >= (int64_t(1) << 31)) return fail(who, "the number of rows must be below 2^31, got " + std::to_string(nr));
+  if (!indptr || !out_indptr) return fail(who, "indptr / out_indptr are null");
+  if (nnz > 0 && (!src || !eids || !out_src || !out_eids)) return fail(who, "src / eids / out_src / out_eids are null");
+  if (n_x > 0 && !x) return fail(who, "x is null");
   return 0;
 }
 
 int check_compact(const char* who, int idtype_bits, const void* preserve, int64_t np, const void* ends, int64_t ne,
                   int64_t num_nodes, const void* local, const void* nodes, const void* num_out, const void* flags) {
-  const std::string w = std::string(who) + ": ";
-  if (idtype_bits != 32 && idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (np < 0 || ne < 0 || num_nodes < 0) return fail(w + "negative size");
-  if (np + ne >= (int64_t(1) << 31)) return fail(w + "preserve and ends together must stay below 2^31 ids (local ids are int32)");
-  if (idtype_bits == 32 && num_nodes > INT32_MAX) return fail(w + "num_nodes does not fit the id type");
-  if (np > 0 && !preserve) return fail(w + "preserve is null");
-  if (ne > 0 && (!ends || !local)) return fail(w + "ends / local are null");
-  if (np + ne > 0 && !nodes) return fail(w + "nodes is null");
-  if (!num_out || !flags) return fail(w + "num_out / flags are null");
+  if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
+  if (np < 0 || ne < 0 || num_nodes < 0) return fail(who, "negative size");
+  if (np + ne >= (int64_t(1) << 31)) return fail(who, "preserve and ends together must stay below 2^31 ids (local ids are int32)");
+  if (idtype_bits == 32 && num_nodes > INT32_MAX) return fail(who, "num_nodes does not fit the id type");
+  if (np > 0 && !preserve) return fail(who, "preserve is null");
+  if (ne > 0 && (!ends || !local)) return fail(who, "ends / local are null");
+  if (np + ne > 0 && !nodes) return fail(who, "nodes is null");
+  if (!num_out || !flags) return fail(who, "num_out / flags are null");
   return 0;
 }
 
@@ -384,18 +381,18 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_exclude_set_workspace_bytes(int idtype_bits, int64_t n, int with_reverse) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || n < 0 || n >= (int64_t(1) << 30)) return 0;
+  if (!idbits_ok(idtype_bits) || n < 0 || n >= (int64_t(1) << 30)) return 0;
   return set_layout(idtype_bits, with_reverse ? 2 * n : n).bytes;
 }
 
 int dgla_exclude_set(int idtype_bits, const void* ids, int64_t n, const void* rev, int64_t num_edges, void* out,
                      int32_t* flags, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_set("exclude_set", idtype_bits, ids, n, num_edges, out, flags)) return -1;
+  const char* who = "exclude_set";
+  if (check_set(who, idtype_bits, ids, n, num_edges, out, flags)) return -1;
   if (n == 0) return 0;
   const int64_t m = rev ? 2 * n : n;
   const SetLayout L = set_layout(idtype_bits, m);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("exclude_set: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
   Scratch ws(s);
@@ -426,19 +423,18 @@ int dgla_exclude_set_host(int idtype_bits, const void* ids, int64_t n, const voi
 }
 
 size_t dgla_frontier_exclude_workspace_bytes(int idtype_bits, int64_t num_rows, int64_t nnz) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || num_rows < 0 || num_rows >= (int64_t(1) << 31) || nnz < 0) return 0;
+  if (!idbits_ok(idtype_bits) || num_rows < 0 || num_rows >= (int64_t(1) << 31) || nnz < 0) return 0;
   return filter_layout(num_rows, nnz).bytes;
 }
 
 int dgla_frontier_exclude(int idtype_bits, const void* indptr, const void* src, const void* eids, int64_t num_rows,
                           int64_t nnz, const void* x, int64_t n_x, void* out_indptr, void* out_src, void* out_eids,
                           void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_filter("frontier_exclude", idtype_bits, indptr, src, eids, num_rows, nnz, x, n_x, out_indptr, out_src, out_eids))
-    return -1;
+  const char* who = "frontier_exclude";
+  if (check_filter(who, idtype_bits, indptr, src, eids, num_rows, nnz, x, n_x, out_indptr, out_src, out_eids)) return -1;
   const bool sweep = num_rows > 0 && nnz > 0;
   const FilterLayout L = filter_layout(num_rows, nnz);
-  if (sweep && workspace && workspace_bytes < L.bytes)
-    return fail("frontier_exclude: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (sweep && optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
   Scratch ws(s);
@@ -497,13 +493,12 @@ size_t dgla_compact_nodes_workspace_bytes(int idtype_bits, int64_t n_preserve, i
 int dgla_compact_nodes(int idtype_bits, const void* preserve, int64_t n_preserve, const void* ends, int64_t n_ends,
                        int32_t* node_map, int64_t num_nodes, void* local, void* nodes, int64_t* num_out, int32_t* flags,
                        void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_compact("compact_nodes", idtype_bits, preserve, n_preserve, ends, n_ends, num_nodes, local, nodes, num_out, flags))
-    return -1;
-  if (num_nodes > 0 && !node_map) return fail("compact_nodes: node_map is null");
+  const char* who = "compact_nodes";
+  if (check_compact(who, idtype_bits, preserve, n_preserve, ends, n_ends, num_nodes, local, nodes, num_out, flags)) return -1;
+  if (num_nodes > 0 && !node_map) return fail(who, "node_map is null");
   const int64_t np = n_preserve, ne = n_ends;
   const CompactLayout L = compact_layout(idtype_bits, np, ne);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("compact_nodes: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, num_out);
   Scratch ws(s);

@@ -295,63 +295,54 @@ FpsLayout fps_layout(int dtype, int64_t batch, int64_t n) {
   return L;
 }
 
-int check_float(const std::string& w, int dtype) {
+int check_float(const char* who, int dtype) {
   if (dtype == kF16 || dtype == kBF16)
-    return fail(w + "float16 / bfloat16 operands are not supported; use float32 or float64");
-  if (dtype != kF32 && dtype != kF64) return fail(w + "unknown dtype " + std::to_string(dtype));
+    return fail(who, "float16 / bfloat16 operands are not supported; use float32 or float64");
+  if (dtype != kF32 && dtype != kF64) return fail(who, "unknown dtype " + std::to_string(dtype));
   return 0;
 }
 
-int check_offsets(const std::string& w, const char* name, const int64_t* off, int64_t num_segs, int64_t rows) {
-  if (!off) return fail(w + name + "_offsets is null");
-  if (off[0] != 0) return fail(w + name + "_offsets do not match: they must start at 0");
+int check_offsets(const char* who, const std::string& name, const int64_t* off, int64_t num_segs, int64_t rows) {
+  if (!off) return fail(who, name + "_offsets is null");
+  if (off[0] != 0) return fail(who, name + "_offsets do not match: they must start at 0");
   for (int64_t s = 0; s < num_segs; ++s)
-    if (off[s + 1] < off[s]) return fail(w + name + "_offsets do not match: they descend at segment " + std::to_string(s));
+    if (off[s + 1] < off[s]) return fail(who, name + "_offsets do not match: they descend at segment " + std::to_string(s));
   if (off[num_segs] != rows)
-    return fail(w + name + "_offsets do not match: they end at " + std::to_string(off[num_segs]) + ", " + name + " has " +
-                std::to_string(rows) + " rows");
+    return fail(who, name + "_offsets do not match: they end at " + std::to_string(off[num_segs]) + ", " + name + " has " +
+                         std::to_string(rows) + " rows");
   return 0;
 }
 
 // everything dgla_knn and dgla_knn_host refuse
 int check_knn(const char* who, const void* x, int64_t num_x, const void* y, int64_t num_y, int dtype, int64_t dim,
               const int64_t* xo, const int64_t* yo, int64_t num_segs, int64_t k, int idbits, const void* out_ids) {
-  const std::string w = std::string(who) + ": ";
-  if (check_float(w, dtype)) return -1;
-  if (idbits != 32 && idbits != 64) return fail(w + "idtype must be int32 or int64");
-  if (num_x < 0 || num_y < 0 || num_segs < 0) return fail(w + "negative size");
-  if (dim < 1) return fail(w + "dim must be at least 1, got " + std::to_string(dim));
-  if (k < 1) return fail(w + "k must be at least 1, got " + std::to_string(k));
-  if (k > kKnnMaxK) return fail(w + "k = " + std::to_string(k) + " is above the limit kKnnMaxK = " + std::to_string(kKnnMaxK));
-  if (num_x > 0 && !x) return fail(w + "x is null");
-  if (!y && num_y != num_x) return fail(w + "y is null (a self-query has num_y == num_x)");
+  if (check_float(who, dtype)) return -1;
+  if (!idbits_ok(idbits)) return fail(who, "idtype must be int32 or int64");
+  if (num_x < 0 || num_y < 0 || num_segs < 0) return fail(who, "negative size");
+  if (dim < 1) return fail(who, "dim must be at least 1, got " + std::to_string(dim));
+  if (k < 1) return fail(who, "k must be at least 1, got " + std::to_string(k));
+  if (k > kKnnMaxK) return fail(who, "k = " + std::to_string(k) + " is above the limit kKnnMaxK = " + std::to_string(kKnnMaxK));
+  if (num_x > 0 && !x) return fail(who, "x is null");
+  if (!y && num_y != num_x) return fail(who, "y is null (a self-query has num_y == num_x)");
   if (num_x >= (int64_t(1) << 31) - kKnnMaxK || num_y >= (int64_t(1) << 31) - kKnnMaxK)
-    return fail(w + "num_x and num_y must be below 2^31 - " + std::to_string(kKnnMaxK));
-  if (idbits == 32 && num_y * k >= (int64_t(1) << 31)) return fail(w + "k * num_y does not fit int32 ids; use int64 ids");
-  if (check_offsets(w, "x", xo, num_segs, num_x) || check_offsets(w, "y", yo, num_segs, num_y)) return -1;
-  if (num_y > 0 && !out_ids) return fail(w + "out_ids is null");
+    return fail(who, "num_x and num_y must be below 2^31 - " + std::to_string(kKnnMaxK));
+  if (idbits == 32 && num_y * k >= (int64_t(1) << 31)) return fail(who, "k * num_y does not fit int32 ids; use int64 ids");
+  if (check_offsets(who, "x", xo, num_segs, num_x) || check_offsets(who, "y", yo, num_segs, num_y)) return -1;
+  if (num_y > 0 && !out_ids) return fail(who, "out_ids is null");
   return 0;
 }
 
 int check_fps(const char* who, const void* pos, int dtype, int64_t batch, int64_t n, int64_t dim, int64_t npoints,
               const int64_t* start, const int64_t* out) {
-  const std::string w = std::string(who) + ": ";
-  if (check_float(w, dtype)) return -1;
-  if (batch < 0 || n < 0) return fail(w + "negative size");
-  if (dim < 1) return fail(w + "dim must be at least 1, got " + std::to_string(dim));
+  if (check_float(who, dtype)) return -1;
+  if (batch < 0 || n < 0) return fail(who, "negative size");
+  if (dim < 1) return fail(who, "dim must be at least 1, got " + std::to_string(dim));
   if (npoints < 1 || npoints > n)
-    return fail(w + "npoints must be in [1, num_rows = " + std::to_string(n) + "], got " + std::to_string(npoints));
-  if (n >= (int64_t(1) << 31) - 1) return fail(w + "num_rows must be below 2^31 - 1");
-  if (batch >= (int64_t(1) << 31)) return fail(w + "batch must be below 2^31");
-  if (batch > 0 && (!pos || !start || !out)) return fail(w + "pos / start / out are null");
+    return fail(who, "npoints must be in [1, num_rows = " + std::to_string(n) + "], got " + std::to_string(npoints));
+  if (n >= (int64_t(1) << 31) - 1) return fail(who, "num_rows must be below 2^31 - 1");
+  if (batch >= (int64_t(1) << 31)) return fail(who, "batch must be below 2^31");
+  if (batch > 0 && (!pos || !start || !out)) return fail(who, "pos / start / out are null");
   return 0;
-}
-
-// f(T{}): the operand type of a call, checked to be fp32 or fp64
-template <typename F>
-decltype(auto) with_float(int dtype, F&& f) {
-  if (dtype == kF32) return f(float{});
-  return f(double{});
 }
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
@@ -424,12 +415,12 @@ size_t dgla_knn_workspace_bytes(int64_t num_segs) {
 int dgla_knn(const void* x, int64_t num_x, const void* y, int64_t num_y, int dtype, int64_t dim, const int64_t* x_offsets,
              const int64_t* y_offsets, int64_t num_segs, int64_t k, int idtype_bits, void* out_ids, void* out_dist,
              void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_knn("knn", x, num_x, y, num_y, dtype, dim, x_offsets, y_offsets, num_segs, k, idtype_bits, out_ids)) return -1;
+  const char* who = "knn";
+  if (check_knn(who, x, num_x, y, num_y, dtype, dim, x_offsets, y_offsets, num_segs, k, idtype_bits, out_ids)) return -1;
   if (num_y == 0) return 0;
   const int64_t S = num_segs;
   const KnnLayout L = knn_layout(S);
-  if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-    return fail("knn: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   std::vector<int64_t> tab(3 * (S + 1));
   int64_t tiles = 0;
   for (int64_t s = 0; s <= S; ++s) {
@@ -487,11 +478,11 @@ size_t dgla_fps_workspace_bytes(int dtype, int64_t batch, int64_t num_rows) {
 
 int dgla_fps(const void* pos, int dtype, int64_t batch, int64_t num_rows, int64_t dim, int64_t npoints, const int64_t* start,
              int64_t* out, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_fps("fps", pos, dtype, batch, num_rows, dim, npoints, start, out)) return -1;
+  const char* who = "fps";
+  if (check_fps(who, pos, dtype, batch, num_rows, dim, npoints, start, out)) return -1;
   if (batch == 0) return 0;
   const FpsLayout L = fps_layout(dtype, batch, num_rows);
-  if (L.bytes && (!workspace || workspace_bytes < L.bytes))
-    return fail("fps: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (L.bytes && need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(st, out);
   with_float(dtype, [&](auto ttag) {

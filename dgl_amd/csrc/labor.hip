@@ -255,26 +255,14 @@ LaborLayout labor_layout(int64_t n) {
 // everything the entry points refuse; `weighted_only`: the scale has no uniform form
 int check_labor(const char* who, const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, bool need_c,
                 const void* seeds, int64_t n, bool weighted_only) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0 || n < 0) return fail(w + "negative size");
-  if (n >= (int64_t(1) << 31)) return fail(w + "num_seeds must be below 2^31, got " + std::to_string(n));
-  if (n > 0 && !seeds) return fail(w + "seeds is null");
-  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
-  if (csr->nnz > 0 && !csr->indices) return fail(w + "indices is null");
-  if (weighted_only && !prob) return fail(w + "prob is null (the scale belongs to the weighted form)");
-  if (prob && prob_dtype != kF32 && prob_dtype != kF64) return fail(w + "prob must be float32 or float64");
-  if (prob && need_c && n > 0 && !c) return fail(w + "c is null (dgla_labor_scale writes it)");
+  if (check_csr(who, csr, kCsrCols | kCsrEmptyIndptr)) return -1;
+  if (n < 0) return fail(who, "negative size");
+  if (n >= (int64_t(1) << 31)) return fail(who, "num_seeds must be below 2^31, got " + std::to_string(n));
+  if (n > 0 && !seeds) return fail(who, "seeds is null");
+  if (weighted_only && !prob) return fail(who, "prob is null (the scale belongs to the weighted form)");
+  if (prob && prob_dtype != kF32 && prob_dtype != kF64) return fail(who, "prob must be float32 or float64");
+  if (prob && need_c && n > 0 && !c) return fail(who, "c is null (dgla_labor_scale writes it)");
   return 0;
-}
-
-// f(W{}, weighted): the weight type of a call
-template <typename F>
-decltype(auto) with_weight(const void* prob, int prob_dtype, F&& f) {
-  if (!prob) return f(float{}, std::false_type{});
-  if (prob_dtype == kF32) return f(float{}, std::true_type{});
-  return f(double{}, std::true_type{});
 }
 
 // f(integral_constant<int, G>): the group width of a call
@@ -286,19 +274,18 @@ decltype(auto) with_group(const dgla_csr* csr, F&& f) {
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx>
-void host_row(const dgla_csr* csr, const Idx* seeds, int64_t i, int64_t* lo, int64_t* hi) {
-  const Idx* indptr = static_cast<const Idx*>(csr->indptr);
+void host_row(const TypedCsr<Idx>& g, const Idx* seeds, int64_t i, int64_t* lo, int64_t* hi) {
   const int64_t s = static_cast<int64_t>(seeds[i]);
   *lo = *hi = 0;
-  if (s >= 0 && s < csr->num_rows) *lo = static_cast<int64_t>(indptr[s]), *hi = static_cast<int64_t>(indptr[s + 1]);
+  if (s >= 0 && s < g.num_rows) *lo = static_cast<int64_t>(g.indptr[s]), *hi = static_cast<int64_t>(g.indptr[s + 1]);
 }
 
 template <typename Idx, typename W>
-void scale_host(const dgla_csr* csr, const W* prob, const Idx* seeds, int64_t n, int64_t k, double* cs) {
-  const Idx* data = static_cast<const Idx*>(csr->data);
+void scale_host(const TypedCsr<Idx>& g, const W* prob, const Idx* seeds, int64_t n, int64_t k, double* cs) {
+  const Idx* data = g.data;
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
-    host_row(csr, seeds, i, &lo, &hi);
+    host_row(g, seeds, i, &lo, &hi);
     auto weight = [&](int64_t q) { return rw_weight(prob[data ? static_cast<int64_t>(data[q]) : q]); };
     cs[i] = labor_scale_row(
         k,
@@ -323,15 +310,15 @@ void scale_host(const dgla_csr* csr, const W* prob, const Idx* seeds, int64_t n,
 
 // out_nbr == NULL: out_indptr only (the sizes)
 template <typename Idx, typename W, bool WEIGHTED>
-void pick_host(const dgla_csr* csr, const W* prob, const double* cs, const Idx* seeds, int64_t n, int64_t k, uint64_t seed,
+void pick_host(const TypedCsr<Idx>& g, const W* prob, const double* cs, const Idx* seeds, int64_t n, int64_t k, uint64_t seed,
                Idx* out_indptr, Idx* out_nbr, Idx* out_eid, W* out_imp) {
-  const Idx *indices = static_cast<const Idx*>(csr->indices), *data = static_cast<const Idx*>(csr->data);
+  const Idx *indices = g.indices, *data = g.data;
   int64_t at = 0;
   std::vector<double> as;
   for (int64_t i = 0; i < n; ++i) {
     out_indptr[i] = static_cast<Idx>(at);
     int64_t lo, hi;
-    host_row(csr, seeds, i, &lo, &hi);
+    host_row(g, seeds, i, &lo, &hi);
     const int64_t d = hi - lo;
     const bool all = !WEIGHTED && (k < 0 || d <= k);
     double acc[kLaborClasses] = {};
@@ -369,7 +356,7 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_labor_workspace_bytes(int idtype_bits, int64_t num_seeds) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || num_seeds <= 0 || num_seeds >= (int64_t(1) << 31)) return 0;
+  if (!idbits_ok(idtype_bits) || num_seeds <= 0 || num_seeds >= (int64_t(1) << 31)) return 0;
   return labor_layout(num_seeds).bytes;
 }
 
@@ -381,13 +368,14 @@ int dgla_labor_scale(const dgla_csr* csr, const void* prob, int prob_dtype, cons
   const DeviceGuard dev(s, c);
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
+    const TypedCsr<Idx> g(csr);
     with_weight(prob, prob_dtype, [&](auto wtag, auto) {
       using W = decltype(wtag);
-      with_group(csr, [&](auto g) {
-        constexpr int G = decltype(g)::value;
+      with_group(csr, [&](auto grp) {
+        constexpr int G = decltype(grp)::value;
         hipLaunchKernelGGL((labor_scale_kernel<Idx, W, G>), dim3(grid1(num_seeds, kLaborBlock / G)), dim3(kLaborBlock), 0, s,
-                           static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->data),
-                           static_cast<const W*>(prob), static_cast<const Idx*>(seeds), num_seeds, csr->num_rows, fanout, c);
+                           g.indptr, g.data, static_cast<const W*>(prob), static_cast<const Idx*>(seeds), num_seeds, g.num_rows,
+                           fanout, c);
       });
     });
   });
@@ -398,16 +386,16 @@ int dgla_labor_scale(const dgla_csr* csr, const void* prob, int prob_dtype, cons
 int dgla_labor_count(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
                      int64_t num_seeds, int64_t fanout, uint64_t seed, void* out_indptr, int64_t* total, void* workspace,
                      size_t workspace_bytes, void* hip_stream) {
-  if (check_labor("labor_count", csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
-  if (!out_indptr || !total) return fail("labor_count: out_indptr / total are null");
+  const char* who = "labor_count";
+  if (check_labor(who, csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
+  if (!out_indptr || !total) return fail(who, "out_indptr / total are null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const int64_t n = num_seeds;
   const bool rows = n > 0 && csr->nnz > 0;  // otherwise every row is empty: no graph memory is read
   LaborLayout L{};
   if (rows) {
     L = labor_layout(n);
-    if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-      return fail("labor_count: workspace of " + std::to_string(L.bytes) + " bytes required");
+    if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   }
   const DeviceGuard dev(s, total);
   char* ws = static_cast<char*>(workspace);
@@ -416,15 +404,15 @@ int dgla_labor_count(const dgla_csr* csr, const void* prob, int prob_dtype, cons
     double* S = reinterpret_cast<double*>(ws + L.S);
     with_idx(csr->idtype_bits, [&](auto tag) {
       using Idx = decltype(tag);
+      const TypedCsr<Idx> g(csr);
       with_weight(prob, prob_dtype, [&](auto wtag, auto weighted) {
         using W = decltype(wtag);
         constexpr bool WEIGHTED = decltype(weighted)::value;
-        with_group(csr, [&](auto g) {
-          constexpr int G = decltype(g)::value;
+        with_group(csr, [&](auto grp) {
+          constexpr int G = decltype(grp)::value;
           hipLaunchKernelGGL((labor_count_kernel<Idx, W, WEIGHTED, G>), dim3(grid1(n, kLaborBlock / G)), dim3(kLaborBlock), 0,
-                             s, static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
-                             static_cast<const Idx*>(csr->data), static_cast<const W*>(prob), c,
-                             static_cast<const Idx*>(seeds), n, csr->num_rows, fanout, seed, offs, S);
+                             s, g.indptr, g.indices, g.data, static_cast<const W*>(prob), c, static_cast<const Idx*>(seeds), n,
+                             g.num_rows, fanout, seed, offs, S);
         });
       });
     });
@@ -443,14 +431,14 @@ int dgla_labor_count(const dgla_csr* csr, const void* prob, int prob_dtype, cons
 int dgla_labor_fill(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
                     int64_t num_seeds, int64_t fanout, uint64_t seed, int64_t capacity, void* out_nbr, void* out_eid,
                     void* out_imp, const void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_labor("labor_fill", csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
-  if (capacity < 0) return fail("labor_fill: negative capacity");
+  const char* who = "labor_fill";
+  if (check_labor(who, csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
+  if (capacity < 0) return fail(who, "negative capacity");
   if (num_seeds == 0 || csr->nnz == 0 || capacity == 0) return 0;  // nothing was counted
-  if (!out_nbr || !out_eid || (prob && !out_imp)) return fail("labor_fill: out_nbr / out_eid / out_imp are null");
+  if (!out_nbr || !out_eid || (prob && !out_imp)) return fail(who, "out_nbr / out_eid / out_imp are null");
   const int64_t n = num_seeds;
   const LaborLayout L = labor_layout(n);
-  if (!workspace || workspace_bytes < L.bytes)
-    return fail("labor_fill: the workspace of labor_count (" + std::to_string(L.bytes) + " bytes) is required");
+  if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;  // (the workspace labor_count filled)
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_nbr);
   const char* ws = static_cast<const char*>(workspace);
@@ -458,16 +446,16 @@ int dgla_labor_fill(const dgla_csr* csr, const void* prob, int prob_dtype, const
   const double* S = reinterpret_cast<const double*>(ws + L.S);
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
+    const TypedCsr<Idx> g(csr);
     with_weight(prob, prob_dtype, [&](auto wtag, auto weighted) {
       using W = decltype(wtag);
       constexpr bool WEIGHTED = decltype(weighted)::value;
-      with_group(csr, [&](auto g) {
-        constexpr int G = decltype(g)::value;
+      with_group(csr, [&](auto grp) {
+        constexpr int G = decltype(grp)::value;
         hipLaunchKernelGGL((labor_fill_kernel<Idx, W, WEIGHTED, G>), dim3(grid1(n, kLaborBlock / G)), dim3(kLaborBlock), 0, s,
-                           static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
-                           static_cast<const Idx*>(csr->data), static_cast<const W*>(prob), c,
-                           static_cast<const Idx*>(seeds), n, csr->num_rows, fanout, seed, offs, S,
-                           static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eid), static_cast<W*>(out_imp), capacity);
+                           g.indptr, g.indices, g.data, static_cast<const W*>(prob), c, static_cast<const Idx*>(seeds), n,
+                           g.num_rows, fanout, seed, offs, S, static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eid),
+                           static_cast<W*>(out_imp), capacity);
       });
     });
   });
@@ -482,7 +470,7 @@ int dgla_labor_scale_host(const dgla_csr* csr, const void* prob, int prob_dtype,
     using Idx = decltype(tag);
     with_weight(prob, prob_dtype, [&](auto wtag, auto) {
       using W = decltype(wtag);
-      scale_host<Idx, W>(csr, static_cast<const W*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, c);
+      scale_host<Idx, W>(TypedCsr<Idx>(csr), static_cast<const W*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, c);
     });
   });
   return 0;
@@ -491,15 +479,16 @@ int dgla_labor_scale_host(const dgla_csr* csr, const void* prob, int prob_dtype,
 int dgla_labor_pick_host(const dgla_csr* csr, const void* prob, int prob_dtype, const double* c, const void* seeds,
                          int64_t num_seeds, int64_t fanout, uint64_t seed, void* out_indptr, void* out_nbr, void* out_eid,
                          void* out_imp) {
-  if (check_labor("labor_pick_host", csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
-  if (!out_indptr) return fail("labor_pick_host: out_indptr is null");
-  if (out_nbr && !out_eid) return fail("labor_pick_host: out_eid is null");
+  const char* who = "labor_pick_host";
+  if (check_labor(who, csr, prob, prob_dtype, c, true, seeds, num_seeds, false)) return -1;
+  if (!out_indptr) return fail(who, "out_indptr is null");
+  if (out_nbr && !out_eid) return fail(who, "out_eid is null");
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
     with_weight(prob, prob_dtype, [&](auto wtag, auto weighted) {
       using W = decltype(wtag);
-      pick_host<Idx, W, decltype(weighted)::value>(csr, static_cast<const W*>(prob), c, static_cast<const Idx*>(seeds),
-                                                   num_seeds, fanout, seed, static_cast<Idx*>(out_indptr),
+      pick_host<Idx, W, decltype(weighted)::value>(TypedCsr<Idx>(csr), static_cast<const W*>(prob), c,
+                                                   static_cast<const Idx*>(seeds), num_seeds, fanout, seed, static_cast<Idx*>(out_indptr),
                                                    static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eid),
                                                    static_cast<W*>(out_imp));
     });

@@ -225,49 +225,34 @@ MatchLayout match_layout(int idbits, int64_t n) {
 // everything dgla_neighbor_matching and dgla_neighbor_matching_host refuse
 int check_matching(const char* who, const dgla_csr* csr, const void* weight, int weight_dtype, int64_t max_rounds,
                    const void* label, const int64_t* rounds) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return fail(w + "negative size");
-  if (!csr->indptr) return fail(w + "indptr is null");
-  if (csr->nnz > 0 && !csr->indices) return fail(w + "indices is null");
+  if (check_csr(who, csr)) return -1;
   if (weight && (weight_dtype == kF16 || weight_dtype == kBF16))
-    return fail(w + "float16 / bfloat16 weights are not supported; use float32 or float64");
-  if (weight && weight_dtype != kF32 && weight_dtype != kF64) return fail(w + "unknown weight dtype " + std::to_string(weight_dtype));
-  if (max_rounds < 1) return fail(w + "max_rounds must be at least 1, got " + std::to_string(max_rounds));
-  if (csr->num_rows > 0 && !label) return fail(w + "label is null");
-  if (!rounds) return fail(w + "rounds is null");
+    return fail(who, "float16 / bfloat16 weights are not supported; use float32 or float64");
+  if (weight && weight_dtype != kF32 && weight_dtype != kF64) return fail(who, "unknown weight dtype " + std::to_string(weight_dtype));
+  if (max_rounds < 1) return fail(who, "max_rounds must be at least 1, got " + std::to_string(max_rounds));
+  if (csr->num_rows > 0 && !label) return fail(who, "label is null");
+  if (!rounds) return fail(who, "rounds is null");
   return 0;
 }
 
 int check_relabel(const char* who, const void* label, int idbits, int64_t n, const void* out) {
-  const std::string w = std::string(who) + ": ";
-  if (idbits != 32 && idbits != 64) return fail(w + "idtype must be int32 or int64");
-  if (n < 0) return fail(w + "negative size");
-  if (n > 0 && (!label || !out)) return fail(w + "label / out are null");
+  if (!idbits_ok(idbits)) return fail(who, "idtype must be int32 or int64");
+  if (n < 0) return fail(who, "negative size");
+  if (n > 0 && (!label || !out)) return fail(who, "label / out are null");
   return 0;
 }
 
 int cap_reached(const char* who, int64_t max_rounds) {
-  return fail(std::string(who) + ": nodes are still unmatched after max_rounds = " + std::to_string(max_rounds) +
-              " rounds; the graph is probably not bi-directed (a CSR that is not symmetric can cycle for ever)");
-}
-
-// f(W{}, weighted): the weight type of a call
-template <typename F>
-decltype(auto) with_weight(const void* weight, int dtype, F&& f) {
-  if (!weight) return f(float{}, std::false_type{});
-  if (dtype == kF32) return f(float{}, std::true_type{});
-  return f(double{}, std::true_type{});
+  return fail(who, "nodes are still unmatched after max_rounds = " + std::to_string(max_rounds) +
+                       " rounds; the graph is probably not bi-directed (a CSR that is not symmetric can cycle for ever)");
 }
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 // returns the rounds used, or -1 when nodes are left at the cap
 template <typename Idx, typename W, bool WEIGHTED>
-int64_t matching_host(const dgla_csr* csr, const W* weight, uint64_t seed, int64_t max_rounds, Idx* label) {
-  const int64_t n = csr->num_rows;
-  const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-            *data = static_cast<const Idx*>(csr->data);
+int64_t matching_host(const TypedCsr<Idx>& g, const W* weight, uint64_t seed, int64_t max_rounds, Idx* label) {
+  const int64_t n = g.num_rows;
+  const Idx *indptr = g.indptr, *indices = g.indices, *data = g.data;
   std::vector<Idx> prop(n, static_cast<Idx>(kMatchNone));
   for (int64_t i = 0; i < n; ++i) label[i] = Idx(-1);
   for (int64_t t = 0;; ++t) {
@@ -322,24 +307,23 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_neighbor_matching_workspace_bytes(int idtype_bits, int64_t num_nodes) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || num_nodes <= 0) return 0;
+  if (!idbits_ok(idtype_bits) || num_nodes <= 0) return 0;
   return match_layout(idtype_bits, num_nodes).bytes;
 }
 
 int dgla_neighbor_matching(const dgla_csr* csr, const void* weight, int weight_dtype, uint64_t seed, int64_t max_rounds,
                            int64_t batch_rounds, void* label, int64_t* rounds, void* workspace, size_t workspace_bytes,
                            void* hip_stream) {
-  if (check_matching("neighbor_matching", csr, weight, weight_dtype, max_rounds, label, rounds)) return -1;
+  const char* who = "neighbor_matching";
+  if (check_matching(who, csr, weight, weight_dtype, max_rounds, label, rounds)) return -1;
   *rounds = 0;
   const int64_t n = csr->num_rows;
   if (n == 0) return 0;
   const MatchLayout L = match_layout(csr->idtype_bits, n);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("neighbor_matching: workspace of " + std::to_string(L.bytes) + " bytes required, got " +
-                std::to_string(workspace_bytes));
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, label);
-  Scratch scratch(s);  // the caller's workspace, else stream-ordered scratch for the duration of the call
+  Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
   int64_t* used = reinterpret_cast<int64_t*>(scratch.p + L.used);
   const int64_t batch = batch_rounds >= 1 ? batch_rounds : kMatchBatch;
@@ -352,11 +336,11 @@ int dgla_neighbor_matching(const dgla_csr* csr, const void* weight, int weight_d
     return with_weight(weight, weight_dtype, [&](auto wtag, auto weighted) -> int {
       using W = decltype(wtag);
       constexpr bool WEIGHTED = decltype(weighted)::value;
-      auto run = [&](auto g) -> int {
-        constexpr int G = decltype(g)::value;
+      auto run = [&](auto grp) -> int {
+        constexpr int G = decltype(grp)::value;
         const dim3 grid(grid1(n, kMatchBlock)), block(kMatchBlock);
-        const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-                  *data = static_cast<const Idx*>(csr->data);
+        const TypedCsr<Idx> g(csr);
+        const Idx *indptr = g.indptr, *indices = g.indices, *data = g.data;
         const W* wt = static_cast<const W*>(weight);
         int64_t queued = 0;
         while (queued < max_rounds) {
@@ -371,10 +355,8 @@ int dgla_neighbor_matching(const dgla_csr* csr, const void* weight, int weight_d
           if (queued == max_rounds)  // the cap: are nodes left?
             hipLaunchKernelGGL(matching_left_kernel<Idx>, dim3(grid1(n, kMatchBlock)), dim3(kMatchBlock), 0, s, lab, n,
                                max_rounds + 1, used);
-          DGLA_CHECK_HIP(hipGetLastError());
-          DGLA_CHECK_HIP(hipMemcpyAsync(&done, used, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-          DGLA_CHECK_HIP(hipStreamSynchronize(s));  // the one read-back of a batch
-          if (done < queued) break;                 // the last queued round found no active node
+          if (read_back(&done, used, sizeof(int64_t), s)) return -1;  // the one read-back of a batch
+          if (done < queued) break;  // the last queued round found no active node
         }
         return 0;
       };
@@ -383,20 +365,19 @@ int dgla_neighbor_matching(const dgla_csr* csr, const void* weight, int weight_d
     });
   });
   if (rc) return -1;
-  if (done > max_rounds) return cap_reached("neighbor_matching", max_rounds);
+  if (done > max_rounds) return cap_reached(who, max_rounds);
   *rounds = done;
   return 0;
 }
 
 int dgla_neighbor_matching_relabel(const void* label, int idtype_bits, int64_t num_nodes, void* out, void* workspace,
                                    size_t workspace_bytes, void* hip_stream) {
-  if (check_relabel("neighbor_matching_relabel", label, idtype_bits, num_nodes, out)) return -1;
+  const char* who = "neighbor_matching_relabel";
+  if (check_relabel(who, label, idtype_bits, num_nodes, out)) return -1;
   const int64_t n = num_nodes;
   if (n == 0) return 0;
   const MatchLayout L = match_layout(idtype_bits, n);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("neighbor_matching_relabel: workspace of " + std::to_string(L.bytes) + " bytes required, got " +
-                std::to_string(workspace_bytes));
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
   Scratch scratch(s);
@@ -422,8 +403,8 @@ int dgla_neighbor_matching_host(const dgla_csr* csr, const void* weight, int wei
     using Idx = decltype(tag);
     return with_weight(weight, weight_dtype, [&](auto wtag, auto weighted) -> int64_t {
       using W = decltype(wtag);
-      return matching_host<Idx, W, decltype(weighted)::value>(csr, static_cast<const W*>(weight), seed, max_rounds,
-                                                              static_cast<Idx*>(label));
+      return matching_host<Idx, W, decltype(weighted)::value>(TypedCsr<Idx>(csr), static_cast<const W*>(weight), seed,
+                                                              max_rounds, static_cast<Idx*>(label));
     });
   });
   if (used < 0) return cap_reached("neighbor_matching_host", max_rounds);

@@ -198,40 +198,36 @@ NegLayout neg_layout(int idtype_bits, int64_t n) {
   return L;
 }
 
+// the column ids are read from `member` (the csr with sorted columns), never from csr->indices
+constexpr unsigned kNegCsr = kCsrCols | kCsrEmptyIndptr | kCsrAnyIndices;
+
 int check_has_edges(const char* who, const dgla_csr* csr, const void* member, const void* u, const void* v, int64_t n,
                     const void* out) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0 || n < 0) return fail(w + "negative size");
-  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
-  if (csr->nnz > 0 && !member) return fail(w + "member is null");
-  if (n > 0 && (!u || !v || !out)) return fail(w + "u / v / out are null");
+  if (check_csr(who, csr, kNegCsr)) return -1;
+  if (n < 0) return fail(who, "negative size");
+  if (csr->nnz > 0 && !member) return fail(who, "member is null");
+  if (n > 0 && (!u || !v || !out)) return fail(who, "u / v / out are null");
   return 0;
 }
 
 // everything both sampling entry points refuse
 int check_neg(const char* who, const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
               const void* out_src, const void* out_dst, const void* out_count) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return fail(w + "negative size");
-  if (n_slots < 0 || num_samples < 0) return fail(w + "negative number of slots / samples");
+  if (check_csr(who, csr, kNegCsr)) return -1;
+  if (n_slots < 0 || num_samples < 0) return fail(who, "negative number of slots / samples");
   if (n_slots >= (int64_t(1) << 31) || num_samples >= (int64_t(1) << 31))
-    return fail(w + "n_slots and num_samples must be below 2^31, got " + std::to_string(n_slots) + " and " +
-                 std::to_string(num_samples));
+    return fail(who, "n_slots and num_samples must be below 2^31, got " + std::to_string(n_slots) + " and " +
+                         std::to_string(num_samples));
   if (num_trials < 1 || num_trials > kNegMaxTrials)
-    return fail(w + "num_trials must be in 1 .. " + std::to_string(kNegMaxTrials) + ", got " + std::to_string(num_trials));
-  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
-  if (csr->nnz > 0 && !member) return fail(w + "member is null");
-  if (num_samples > 0 && (!out_src || !out_dst)) return fail(w + "out_src / out_dst are null");
-  if (!out_count) return fail(w + "out_count is null");
+    return fail(who, "num_trials must be in 1 .. " + std::to_string(kNegMaxTrials) + ", got " + std::to_string(num_trials));
+  if (csr->nnz > 0 && !member) return fail(who, "member is null");
+  if (num_samples > 0 && (!out_src || !out_dst)) return fail(who, "out_src / out_dst are null");
+  if (!out_count) return fail(who, "out_count is null");
   return 0;
 }
 
 template <typename Idx>
-int run_neg(const dgla_csr* c, const void* member, int64_t n, int64_t num_samples, int T, bool excl, bool replace,
+int run_neg(const TypedCsr<Idx>& c, const void* member, int64_t n, int64_t num_samples, int T, bool excl, bool replace,
             uint64_t seed, void* out_src, void* out_dst, int64_t* out_count, char* ws, const NegLayout& L, hipStream_t s) {
   Idx *pu = reinterpret_cast<Idx*>(ws + L.pu), *pv = reinterpret_cast<Idx*>(ws + L.pv);
   int32_t *flag = reinterpret_cast<int32_t*>(ws + L.flag), *cnt = reinterpret_cast<int32_t*>(ws + L.cnt),
@@ -241,8 +237,8 @@ int run_neg(const dgla_csr* c, const void* member, int64_t n, int64_t num_sample
   const uint32_t mask = (1u << L.kb) - 1u;
 #define DGLA_NEG_DRAW(E, P)                                                                                             \
   hipLaunchKernelGGL((neg_draw_kernel<Idx, E, P>), dim3(grid1(n)), dim3(kNegBlock), 0, s,                               \
-                     static_cast<const Idx*>(c->indptr), static_cast<const Idx*>(member), c->num_rows, c->num_cols, T, \
-                     seed, n, pu, pv, flag, cnt, row, mask)
+                     c.indptr, static_cast<const Idx*>(member), c.num_rows, c.num_cols, T, seed, n, pu, pv, flag, cnt, \
+                     row, mask)
   if (excl) {
     if (replace) DGLA_NEG_DRAW(true, true); else DGLA_NEG_DRAW(true, false);
   } else {
@@ -273,15 +269,15 @@ struct PairHash {
 
 // the whole rule, slot by slot
 template <typename Idx, bool EXCL>
-void neg_host(const dgla_csr* c, const void* member, int64_t n, int64_t num_samples, int T, bool replace, uint64_t seed,
+void neg_host(const TypedCsr<Idx>& c, const void* member, int64_t n, int64_t num_samples, int T, bool replace, uint64_t seed,
               void* out_src, void* out_dst, int64_t* out_count) {
-  const Idx *indptr = static_cast<const Idx*>(c->indptr), *mem = static_cast<const Idx*>(member);
+  const Idx* mem = static_cast<const Idx*>(member);
   Idx *os = static_cast<Idx*>(out_src), *od = static_cast<Idx*>(out_dst);
   std::unordered_set<std::pair<int64_t, int64_t>, PairHash> seen;
   int64_t count = 0;
   for (int64_t i = 0; i < n && count < num_samples; ++i) {
     int64_t u, v;
-    if (!neg_draw<EXCL>(indptr, mem, c->num_rows, c->num_cols, T, seed, i, &u, &v)) continue;
+    if (!neg_draw<EXCL>(c.indptr, mem, c.num_rows, c.num_cols, T, seed, i, &u, &v)) continue;
     if (!replace && !seen.insert({u, v}).second) continue;
     os[count] = static_cast<Idx>(u), od[count] = static_cast<Idx>(v);
     ++count;
@@ -298,21 +294,21 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_negative_sample_workspace_bytes(int idtype_bits, int64_t n_slots) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || n_slots <= 0 || n_slots >= (int64_t(1) << 31)) return 0;
+  if (!idbits_ok(idtype_bits) || n_slots <= 0 || n_slots >= (int64_t(1) << 31)) return 0;
   return neg_layout(idtype_bits, n_slots).bytes;
 }
 
 int dgla_negative_sample(const dgla_csr* csr, const void* member, int64_t n_slots, int64_t num_samples, int num_trials,
                          int exclude_self_loops, int replace, uint64_t seed, void* out_src, void* out_dst,
                          int64_t* out_count, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_neg("negative_sample", csr, member, n_slots, num_samples, num_trials, out_src, out_dst, out_count)) return -1;
+  const char* who = "negative_sample";
+  if (check_neg(who, csr, member, n_slots, num_samples, num_trials, out_src, out_dst, out_count)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const bool drawable = n_slots > 0 && csr->num_rows > 0 && csr->num_cols > 0;
   NegLayout L{};
   if (drawable) {
     L = neg_layout(csr->idtype_bits, n_slots);
-    if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-      return fail("negative_sample: workspace of " + std::to_string(L.bytes) + " bytes required");
+    if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   }
   const DeviceGuard dev(s, out_count);
   if (!drawable) {
@@ -326,8 +322,9 @@ int dgla_negative_sample(const dgla_csr* csr, const void* member, int64_t n_slot
   }
   char* ws = static_cast<char*>(workspace);
   return with_idx(csr->idtype_bits, [&](auto tag) {
-    return run_neg<decltype(tag)>(csr, member, n_slots, num_samples, num_trials, exclude_self_loops != 0, replace != 0, seed,
-                                  out_src, out_dst, out_count, ws, L, s);
+    using Idx = decltype(tag);
+    return run_neg<Idx>(TypedCsr<Idx>(csr), member, n_slots, num_samples, num_trials, exclude_self_loops != 0, replace != 0,
+                        seed, out_src, out_dst, out_count, ws, L, s);
   });
 }
 
@@ -338,7 +335,7 @@ int dgla_negative_sample_host(const dgla_csr* csr, const void* member, int64_t n
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
     auto run = [&](auto excl) {
-      neg_host<Idx, decltype(excl)::value>(csr, member, n_slots, num_samples, num_trials, replace != 0, seed, out_src,
+      neg_host<Idx, decltype(excl)::value>(TypedCsr<Idx>(csr), member, n_slots, num_samples, num_trials, replace != 0, seed, out_src,
                                            out_dst, out_count);
     };
     if (exclude_self_loops) run(std::true_type{}); else run(std::false_type{});
@@ -354,7 +351,7 @@ int dgla_csr_has_edges(const dgla_csr* csr, const void* member, const void* u, c
   const DeviceGuard dev(s, out);
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
-    hipLaunchKernelGGL(has_edges_kernel<Idx>, dim3(grid1(n)), dim3(kNegBlock), 0, s, static_cast<const Idx*>(csr->indptr),
+    hipLaunchKernelGGL(has_edges_kernel<Idx>, dim3(grid1(n)), dim3(kNegBlock), 0, s, TypedCsr<Idx>(csr).indptr,
                        static_cast<const Idx*>(member), csr->num_rows, csr->num_cols, static_cast<const Idx*>(u),
                        static_cast<const Idx*>(v), n, out);
   });
@@ -366,10 +363,10 @@ int dgla_csr_has_edges_host(const dgla_csr* csr, const void* member, const void*
   if (check_has_edges("csr_has_edges_host", csr, member, u, v, n, out)) return -1;
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
-    const Idx *indptr = static_cast<const Idx*>(csr->indptr), *mem = static_cast<const Idx*>(member),
-              *us = static_cast<const Idx*>(u), *vs = static_cast<const Idx*>(v);
+    const TypedCsr<Idx> g(csr);
+    const Idx *mem = static_cast<const Idx*>(member), *us = static_cast<const Idx*>(u), *vs = static_cast<const Idx*>(v);
     for (int64_t i = 0; i < n; ++i)
-      out[i] = neg_has_edge(indptr, mem, csr->num_rows, csr->num_cols, static_cast<int64_t>(us[i]), static_cast<int64_t>(vs[i]));
+      out[i] = neg_has_edge(g.indptr, mem, csr->num_rows, csr->num_cols, static_cast<int64_t>(us[i]), static_cast<int64_t>(vs[i]));
   });
   return 0;
 }

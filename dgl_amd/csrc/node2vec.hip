@@ -87,14 +87,6 @@ SortedLayout sorted_layout(const dgla_csr* c) {
   return L;
 }
 
-int check_sorted(const dgla_csr* csr) {
-  if (!csr || !csr->indptr) return fail("csr_sorted_columns: csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail("csr_sorted_columns: idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return fail("csr_sorted_columns: negative size");
-  if (csr->nnz > 0 && !csr->indices) return fail("csr_sorted_columns: indices are null");
-  return 0;
-}
-
 template <typename Idx>
 int run_sorted(const dgla_csr* c, void* member, char* ws, const SortedLayout& L, hipStream_t s) {
   const int bits = c->idtype_bits;
@@ -103,8 +95,8 @@ int run_sorted(const dgla_csr* c, void* member, char* ws, const SortedLayout& L,
   Idx* t_indptr = reinterpret_cast<Idx*>(ws + L.t_indptr);
   const size_t sort_bytes = L.bytes - L.sort;
   // 1. the edges in CSC order: a stable sort by column id keeps the rows of a column in CSR order
-  hipLaunchKernelGGL(expand_rows_kernel<Idx>, dim3(grid1(c->nnz)), dim3(256), 0, s, static_cast<const Idx*>(c->indptr),
-                     c->num_rows, c->nnz, rows);
+  hipLaunchKernelGGL(expand_rows_kernel<Idx>, dim3(grid1(c->nnz)), dim3(256), 0, s, TypedCsr<Idx>(c).indptr, c->num_rows,
+                     c->nnz, rows);
   DGLA_CHECK_HIP(hipGetLastError());
   if (dgla_coo_to_csr_bounded(bits, c->num_cols, c->num_rows, c->nnz, c->indices, rows, nullptr, t_indptr,
                               ws + L.t_indices, ws + L.junk, ws + L.sort, sort_bytes, s))
@@ -120,36 +112,32 @@ int run_sorted(const dgla_csr* c, void* member, char* ws, const SortedLayout& L,
 // everything both walk entry points refuse
 int check_n2v(const char* who, const dgla_csr* csr, const void* member, const void* seeds, int64_t num_seeds,
               int64_t num_steps, double p, double q, const void* traces, N2vAccept* a) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr || !csr->indptr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return fail(w + "negative size");
+  if (check_csr(who, csr)) return -1;
   if (csr->num_rows != csr->num_cols)
-    return fail(w + "the relation must join one node set to itself (num_rows " + std::to_string(csr->num_rows) +
-                 " != num_cols " + std::to_string(csr->num_cols) + ")");
-  if (csr->nnz > 0 && (!csr->indices || !member)) return fail(w + "indices / member are null");
-  if (num_steps < 0 || num_seeds < 0) return fail(w + "negative number of steps / seeds");
-  if (num_seeds > 0 && (!seeds || !traces)) return fail(w + "seeds / traces are null");
+    return fail(who, "the relation must join one node set to itself (num_rows " + std::to_string(csr->num_rows) +
+                         " != num_cols " + std::to_string(csr->num_cols) + ")");
+  if (csr->nnz > 0 && !member) return fail(who, "member is null");
+  if (num_steps < 0 || num_seeds < 0) return fail(who, "negative number of steps / seeds");
+  if (num_seeds > 0 && (!seeds || !traces)) return fail(who, "seeds / traces are null");
   if (!n2v_accept(p, q, a))
-    return fail(w + "p and q must be finite and > 0 with usable acceptance probabilities (p = " + std::to_string(p) +
-                 ", q = " + std::to_string(q) + ")");
+    return fail(who, "p and q must be finite and > 0 with usable acceptance probabilities (p = " + std::to_string(p) +
+                         ", q = " + std::to_string(q) + ")");
   return 0;
 }
 
 template <typename Idx>
-void n2v_host(const dgla_csr* c, const double* cdf, const void* member, const void* seeds, int64_t num_seeds,
+void n2v_host(const TypedCsr<Idx>& c, const double* cdf, const void* member, const void* seeds, int64_t num_seeds,
               int64_t num_steps, const N2vAccept& a, uint64_t rng_seed, void* traces, void* eids, int64_t* stats) {
   const Idx* sd = static_cast<const Idx*>(seeds);
   Idx* tr = static_cast<Idx*>(traces);
   Idx* ev = static_cast<Idx*>(eids);
-  const Idx *indptr = static_cast<const Idx*>(c->indptr), *indices = static_cast<const Idx*>(c->indices),
-            *data = static_cast<const Idx*>(c->data), *mem = static_cast<const Idx*>(member);
+  const Idx* mem = static_cast<const Idx*>(member);
   for (int64_t i = 0; i < num_seeds; ++i) {  // the two instantiations of the kernel
     if (cdf)
-      n2v_walk<Idx>(indptr, indices, data, mem, N2vWeighted<const double*>{cdf}, c->num_rows, a, num_steps, rng_seed, i, sd[i],
+      n2v_walk<Idx>(c.indptr, c.indices, c.data, mem, N2vWeighted<const double*>{cdf}, c.num_rows, a, num_steps, rng_seed, i, sd[i],
                     tr + i * (num_steps + 1), ev ? ev + i * num_steps : nullptr, stats);
     else
-      n2v_walk<Idx>(indptr, indices, data, mem, N2vUniform{}, c->num_rows, a, num_steps, rng_seed, i, sd[i],
+      n2v_walk<Idx>(c.indptr, c.indices, c.data, mem, N2vUniform{}, c.num_rows, a, num_steps, rng_seed, i, sd[i],
                     tr + i * (num_steps + 1), ev ? ev + i * num_steps : nullptr, stats);
   }
 }
@@ -162,20 +150,20 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_csr_sorted_columns_workspace_bytes(const dgla_csr* csr) {
-  if (!csr || (csr->idtype_bits != 32 && csr->idtype_bits != 64) || csr->nnz <= 0 || csr->num_rows <= 0 ||
+  if (!csr || !idbits_ok(csr->idtype_bits) || csr->nnz <= 0 || csr->num_rows <= 0 ||
       csr->num_cols <= 0)
     return 0;
   return sorted_layout(csr).bytes;
 }
 
 int dgla_csr_sorted_columns(const dgla_csr* csr, void* member, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_sorted(csr)) return -1;
+  const char* who = "csr_sorted_columns";
+  if (check_csr(who, csr, kCsrCols)) return -1;
   if (csr->nnz == 0) return 0;
-  if (csr->num_rows == 0 || csr->num_cols == 0) return fail("csr_sorted_columns: edges without rows / columns");
-  if (!member) return fail("csr_sorted_columns: member is null");
+  if (csr->num_rows == 0 || csr->num_cols == 0) return fail(who, "edges without rows / columns");
+  if (!member) return fail(who, "member is null");
   const SortedLayout L = sorted_layout(csr);
-  if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-    return fail("csr_sorted_columns: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, member);
   char* ws = static_cast<char*>(workspace);
@@ -192,11 +180,11 @@ int dgla_node2vec_walk(const dgla_csr* csr, const double* cdf, const void* membe
   const DeviceGuard dev(s, traces);
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
+    const TypedCsr<Idx> g(csr);
     auto launch = [&](auto weighted) {
       hipLaunchKernelGGL((node2vec_walk_kernel<Idx, decltype(weighted)::value>), dim3(grid1(num_seeds)), dim3(256), 0, s,
-                         static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
-                         static_cast<const Idx*>(csr->data), static_cast<const Idx*>(member), cdf, csr->num_rows, a,
-                         num_steps, static_cast<const Idx*>(seeds), num_seeds, rng_seed, static_cast<Idx*>(traces),
+                         g.indptr, g.indices, g.data, static_cast<const Idx*>(member), cdf, g.num_rows, a, num_steps,
+                         static_cast<const Idx*>(seeds), num_seeds, rng_seed, static_cast<Idx*>(traces),
                          static_cast<Idx*>(eids));
     };
     if (cdf) launch(std::true_type{}); else launch(std::false_type{});
@@ -212,7 +200,9 @@ int dgla_node2vec_walk_host(const dgla_csr* csr, const double* cdf, const void* 
   if (check_n2v("node2vec_walk_host", csr, member, seeds, num_seeds, num_steps, p, q, traces, &a)) return -1;
   int64_t local[3] = {0, 0, 0};
   with_idx(csr->idtype_bits, [&](auto tag) {
-    n2v_host<decltype(tag)>(csr, cdf, member, seeds, num_seeds, num_steps, a, rng_seed, traces, eids, stats ? local : nullptr);
+    using Idx = decltype(tag);
+    n2v_host<Idx>(TypedCsr<Idx>(csr), cdf, member, seeds, num_seeds, num_steps, a, rng_seed, traces, eids,
+                  stats ? local : nullptr);
   });
   if (stats) stats[0] = local[0], stats[1] = local[1], stats[2] = local[2];
   return 0;

@@ -157,15 +157,14 @@ __global__ __launch_bounds__(256) void pinsage_compact_kernel(const Idx* __restr
 // ---- host side ------------------------------------------------------------------------------------------------------
 // what every entry point refuses; *kp = min(k, S)
 int check_args(const char* who, int idtype_bits, int64_t num_dst, int64_t S, int64_t k, bool device, int64_t* kp) {
-  const std::string w = std::string(who) + ": ";
-  if (idtype_bits != 32 && idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (num_dst < 0) return fail(w + "negative number of segments");
-  if (S < 1) return fail(w + "num_samples_per_node must be at least 1, got " + std::to_string(S));
-  if (k < 1) return fail(w + "k must be at least 1, got " + std::to_string(k));
+  if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
+  if (num_dst < 0) return fail(who, "negative number of segments");
+  if (S < 1) return fail(who, "num_samples_per_node must be at least 1, got " + std::to_string(S));
+  if (k < 1) return fail(who, "k must be at least 1, got " + std::to_string(k));
   if (device && S > kMaxSamples)
-    return fail(w + "num_samples_per_node = " + std::to_string(S) + " is above the largest segment the kernel holds in LDS (" +
-                std::to_string(kMaxSamples) + ", dgla_pinsage_max_samples); there is no CPU fallback");
-  if (device && num_dst > 0x7fffffffLL) return fail(w + "more than 2^31 - 1 segments in one call");
+    return fail(who, "num_samples_per_node = " + std::to_string(S) + " is above the largest segment the kernel holds in LDS (" +
+                         std::to_string(kMaxSamples) + ", dgla_pinsage_max_samples); there is no CPU fallback");
+  if (device && num_dst > 0x7fffffffLL) return fail(who, "more than 2^31 - 1 segments in one call");
   *kp = k < S ? k : S;
   return 0;
 }
@@ -213,9 +212,8 @@ int count_compact(const void* src, const void* dst, int64_t num_dst, int64_t S, 
   if (msd::exclusive_scan<Idx, int64_t>(num, off, num_dst, ws + l.off_scan, s)) return -1;
   int64_t last_off = 0;
   Idx last_num = 0;
-  DGLA_CHECK_HIP(hipMemcpyAsync(&last_off, off + num_dst - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  DGLA_CHECK_HIP(hipMemcpyAsync(&last_num, num + num_dst - 1, sizeof(Idx), hipMemcpyDeviceToHost, s));
-  DGLA_CHECK_HIP(hipStreamSynchronize(s));
+  if (read_back(&last_off, off + num_dst - 1, sizeof(int64_t), s) || read_back(&last_num, num + num_dst - 1, sizeof(Idx), s))
+    return -1;
   *total_out = last_off + static_cast<int64_t>(last_num);
   return 0;
 }
@@ -272,7 +270,7 @@ using namespace dgla::pinsage;
 extern "C" {
 
 int64_t dgla_pinsage_max_samples(int idtype_bits) {
-  return idtype_bits == 32 || idtype_bits == 64 ? kMaxSamples : 0;
+  return idbits_ok(idtype_bits) ? kMaxSamples : 0;
 }
 
 int dgla_pinsage_size_classes(int64_t* bounds, int max) {
@@ -285,10 +283,11 @@ int dgla_pinsage_select_padded(int idtype_bits, const void* src, const void* dst
                                int64_t num_samples_per_node, int64_t k, void* out_src, void* out_cnt, void* out_num,
                                void* out_dst, void* hip_stream) {
   int64_t kp = 0;
-  if (check_args("pinsage_select_padded", idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
+  const char* who = "pinsage_select_padded";
+  if (check_args(who, idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
   if (num_dst == 0) return 0;
-  if (!src || !out_src || !out_cnt || !out_num) return fail("pinsage_select_padded: src / out_src / out_cnt / out_num are null");
-  if (out_dst && !dst) return fail("pinsage_select_padded: out_dst asked for without dst");
+  if (!src || !out_src || !out_cnt || !out_num) return fail(who, "src / out_src / out_cnt / out_num are null");
+  if (out_dst && !dst) return fail(who, "out_dst asked for without dst");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_src);
   return with_idx(idtype_bits, [&](auto tag) {
@@ -306,14 +305,14 @@ int dgla_pinsage_select_count(int idtype_bits, const void* src, const void* dst,
                               int64_t num_samples_per_node, int64_t k, int64_t* total_out, void* workspace,
                               size_t workspace_bytes, void* hip_stream) {
   int64_t kp = 0;
-  if (check_args("pinsage_select_count", idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
-  if (!total_out) return fail("pinsage_select_count: total_out is null");
+  const char* who = "pinsage_select_count";
+  if (check_args(who, idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
+  if (!total_out) return fail(who, "total_out is null");
   *total_out = 0;
   if (num_dst == 0) return 0;
-  if (!src || !dst) return fail("pinsage_select_count: src / dst are null");
+  if (!src || !dst) return fail(who, "src / dst are null");
   const Layout l = make_layout(idtype_bits, num_dst, kp);
-  if (!workspace || workspace_bytes < l.bytes)   // no allocation here
-    return fail("pinsage_select_count: workspace of " + std::to_string(l.bytes) + " bytes required");
+  if (need_workspace(who, workspace, workspace_bytes, l.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, workspace);
   char* ws = static_cast<char*>(workspace);
@@ -326,11 +325,11 @@ int dgla_pinsage_select_fill(int idtype_bits, int64_t num_dst, int64_t num_sampl
                              void* res_dst, void* res_cnt, const void* workspace, size_t workspace_bytes,
                              void* hip_stream) {
   int64_t kp = 0;
-  if (check_args("pinsage_select_fill", idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
+  const char* who = "pinsage_select_fill";
+  if (check_args(who, idtype_bits, num_dst, num_samples_per_node, k, true, &kp)) return -1;
   if (num_dst == 0) return 0;
   const Layout l = make_layout(idtype_bits, num_dst, kp);
-  if (!workspace || workspace_bytes < l.bytes)
-    return fail("pinsage_select_fill: workspace of " + std::to_string(l.bytes) + " bytes required");
+  if (need_workspace(who, workspace, workspace_bytes, l.bytes)) return -1;
   // (a total of 0 leaves the result arrays empty, possibly null: the kernel then stores nothing)
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, workspace);
@@ -344,11 +343,12 @@ int dgla_pinsage_select_host(int idtype_bits, const void* src, const void* dst, 
                              int64_t num_samples_per_node, int64_t k, void* res_src, void* res_dst, void* res_cnt,
                              int64_t* total_out) {
   int64_t kp = 0;
-  if (check_args("pinsage_select_host", idtype_bits, num_dst, num_samples_per_node, k, false, &kp)) return -1;
-  if (!total_out) return fail("pinsage_select_host: total_out is null");
+  const char* who = "pinsage_select_host";
+  if (check_args(who, idtype_bits, num_dst, num_samples_per_node, k, false, &kp)) return -1;
+  if (!total_out) return fail(who, "total_out is null");
   *total_out = 0;
   if (num_dst == 0) return 0;
-  if (!src || !dst || !res_src || !res_dst || !res_cnt) return fail("pinsage_select_host: a null array");
+  if (!src || !dst || !res_src || !res_dst || !res_cnt) return fail(who, "a null array");
   *total_out = with_idx(idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
     return select_host<Idx>(static_cast<const Idx*>(src), static_cast<const Idx*>(dst), num_dst, num_samples_per_node, kp,

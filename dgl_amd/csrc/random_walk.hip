@@ -187,38 +187,33 @@ __global__ __launch_bounds__(256) void walk_cdf_kernel(const Idx* __restrict__ i
 int check_walk(const char* who, const dgla_walk_relation* rels, int num_rels, const int32_t* metapath, int64_t num_steps,
                const void* seeds, int64_t num_seeds, const void* restart_steps, dgla_dtype restart_dtype,
                const void* traces, int* idbits) {
-  const std::string w = std::string(who) + ": ";
-  if (!rels || num_rels < 1) return fail(w + "the relation table is null or empty");
-  if (num_steps < 0 || num_seeds < 0) return fail(w + "negative number of steps / seeds");
+  if (!rels || num_rels < 1) return fail(who, "the relation table is null or empty");
+  if (num_steps < 0 || num_seeds < 0) return fail(who, "negative number of steps / seeds");
   for (int r = 0; r < num_rels; ++r) {
-    const dgla_csr* c = rels[r].csr;
-    if (!c || !c->indptr) return fail(w + "relation " + std::to_string(r) + " has a null csr");
-    if (c->idtype_bits != 32 && c->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-    if (c->idtype_bits != rels[0].csr->idtype_bits) return fail(w + "the relations have mixed id widths");
-    if (c->nnz > 0 && !c->indices) return fail(w + "relation " + std::to_string(r) + " has null indices");
-    if (c->num_rows < 0 || c->nnz < 0) return fail(w + "relation " + std::to_string(r) + " has a negative size");
+    if (check_csr((std::string(who) + ": relation " + std::to_string(r)).c_str(), rels[r].csr)) return -1;
+    if (rels[r].csr->idtype_bits != rels[0].csr->idtype_bits) return fail(who, "the relations have mixed id widths");
   }
-  if (num_steps > 0 && !metapath) return fail(w + "metapath is null");
+  if (num_steps > 0 && !metapath) return fail(who, "metapath is null");
   for (int64_t t = 0; t < num_steps; ++t) {
     if (metapath[t] < 0 || metapath[t] >= num_rels)
-      return fail(w + "metapath[" + std::to_string(t) + "] = " + std::to_string(metapath[t]) + " is out of range");
+      return fail(who, "metapath[" + std::to_string(t) + "] = " + std::to_string(metapath[t]) + " is out of range");
     if (t > 0 && rels[metapath[t - 1]].csr->num_cols != rels[metapath[t]].csr->num_rows)
-      return fail(w + "the metapath does not chain at step " + std::to_string(t) + ": relation " +
-                   std::to_string(metapath[t - 1]) + " ends in " + std::to_string(rels[metapath[t - 1]].csr->num_cols) +
-                   " nodes, relation " + std::to_string(metapath[t]) + " starts from " +
-                   std::to_string(rels[metapath[t]].csr->num_rows));
+      return fail(who, "the metapath does not chain at step " + std::to_string(t) + ": relation " +
+                           std::to_string(metapath[t - 1]) + " ends in " + std::to_string(rels[metapath[t - 1]].csr->num_cols) +
+                           " nodes, relation " + std::to_string(metapath[t]) + " starts from " +
+                           std::to_string(rels[metapath[t]].csr->num_rows));
   }
   if (restart_steps && restart_dtype != DGLA_F32 && restart_dtype != DGLA_F64)
-    return fail(w + "restart_steps must be float32 or float64");
-  if (num_seeds > 0 && (!seeds || !traces)) return fail(w + "seeds / traces are null");
+    return fail(who, "restart_steps must be float32 or float64");
+  if (num_seeds > 0 && (!seeds || !traces)) return fail(who, "seeds / traces are null");
   *idbits = rels[0].csr->idtype_bits;
   return 0;
 }
 
 template <typename Idx>
 WalkRel<Idx> make_rel(const dgla_walk_relation& r) {
-  return WalkRel<Idx>{static_cast<const Idx*>(r.csr->indptr), static_cast<const Idx*>(r.csr->indices),
-                      static_cast<const Idx*>(r.csr->data), r.cdf, r.csr->num_rows};
+  const TypedCsr<Idx> g(r.csr);
+  return WalkRel<Idx>{g.indptr, g.indices, g.data, r.cdf, g.num_rows};
 }
 
 template <typename Idx>
@@ -290,24 +285,22 @@ size_t dgla_random_walk_cdf_workspace_bytes(const dgla_csr* csr) {
 int dgla_random_walk_cdf(const dgla_csr* csr, const void* prob, dgla_dtype prob_dtype, double* cdf, void* workspace,
                          size_t workspace_bytes, void* hip_stream) {
   (void)workspace;
-  if (!csr || !csr->indptr) return fail("random_walk_cdf: csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail("random_walk_cdf: idtype must be int32 or int64");
-  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("random_walk_cdf: prob must be float32 or float64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return fail("random_walk_cdf: negative size");
-  if (csr->nnz > 0 && (!prob || !cdf)) return fail("random_walk_cdf: prob / cdf are null");
-  if (workspace_bytes < dgla_random_walk_cdf_workspace_bytes(csr)) return fail("random_walk_cdf: workspace too small");
+  const char* who = "random_walk_cdf";
+  if (check_csr(who, csr, kCsrAnyIndices)) return -1;  // (the scan reads indptr and data, never indices)
+  if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail(who, "prob must be float32 or float64");
+  if (csr->nnz > 0 && (!prob || !cdf)) return fail(who, "prob / cdf are null");
+  if (workspace_bytes < dgla_random_walk_cdf_workspace_bytes(csr)) return fail(who, "workspace too small");
   if (csr->nnz == 0 || csr->num_rows == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, cdf);
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
-    auto launch = [&](auto w) {
+    const TypedCsr<Idx> g(csr);
+    with_float(prob_dtype, [&](auto w) {
       using W = decltype(w);
-      hipLaunchKernelGGL((walk_cdf_kernel<Idx, W>), dim3(grid1(csr->num_rows)), dim3(256), 0, s,
-                         static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->data),
-                         static_cast<const W*>(prob), csr->num_rows, cdf);
-    };
-    if (prob_dtype == DGLA_F32) launch(float{}); else launch(double{});
+      hipLaunchKernelGGL((walk_cdf_kernel<Idx, W>), dim3(grid1(g.num_rows)), dim3(256), 0, s, g.indptr, g.data,
+                         static_cast<const W*>(prob), g.num_rows, cdf);
+    });
   });
   DGLA_CHECK_HIP(hipGetLastError());
   return 0;
@@ -323,12 +316,11 @@ int dgla_random_walk(const dgla_walk_relation* rels, int num_rels, const int32_t
                      dgla_dtype restart_dtype, uint64_t rng_seed, void* traces, void* eids, void* workspace,
                      size_t workspace_bytes, void* hip_stream) {
   int idbits = 0;
-  if (check_walk("random_walk", rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_steps, restart_dtype,
-                 traces, &idbits))
+  const char* who = "random_walk";
+  if (check_walk(who, rels, num_rels, metapath, num_steps, seeds, num_seeds, restart_steps, restart_dtype, traces, &idbits))
     return -1;
   const WalkLayout L = walk_layout(num_rels, num_steps);
-  if (L.bytes > 0 && (!workspace || workspace_bytes < L.bytes))  // no allocation here
-    return fail("random_walk: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (L.bytes > 0 && need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   if (num_seeds == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, traces);

@@ -475,18 +475,17 @@ int run_sample(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fa
                uint64_t rng_seed, void* out_indptr, void* out_src, void* out_eids, char* ws, const SampleLayout& L,
                hipStream_t s, const int64_t* num_valid = nullptr, const int64_t* rng_counter = nullptr, int sinks = 0) {
   // counts -> exclusive scan in place of out_indptr (num_seeds + 1 entries)
+  const TypedCsr<Idx> g(csc);
   Idx* counts = reinterpret_cast<Idx*>(ws + L.counts);
-  hipLaunchKernelGGL(sample_count_kernel<Idx>, dim3(grid1(num_seeds + 1)), dim3(256), 0, s,
-                     static_cast<const Idx*>(csc->indptr), static_cast<const Idx*>(seeds), num_seeds,
-                     fanout, replace, counts, num_valid);
+  hipLaunchKernelGGL(sample_count_kernel<Idx>, dim3(grid1(num_seeds + 1)), dim3(256), 0, s, g.indptr,
+                     static_cast<const Idx*>(seeds), num_seeds, fanout, replace, counts, num_valid);
   if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, ws + L.scan, s)) return -1;
   if (out_src) {
-#define DGLA_PICK(FM)                                                                                      \
-  hipLaunchKernelGGL((sample_pick_kernel<Idx, FM>), dim3(grid1(num_seeds)), dim3(256), 0, s,                \
-                     static_cast<const Idx*>(csc->indptr), static_cast<const Idx*>(csc->indices),          \
-                     static_cast<const Idx*>(csc->data), static_cast<const Idx*>(seeds), num_seeds, fanout, \
-                     replace, rng_seed, static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_src),    \
-                     static_cast<Idx*>(out_eids), num_valid, rng_counter)
+#define DGLA_PICK(FM)                                                                                               \
+  hipLaunchKernelGGL((sample_pick_kernel<Idx, FM>), dim3(grid1(num_seeds)), dim3(256), 0, s, g.indptr, g.indices, g.data, \
+                     static_cast<const Idx*>(seeds), num_seeds, fanout, replace, rng_seed,                             \
+                     static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_src), static_cast<Idx*>(out_eids),     \
+                     num_valid, rng_counter)
     if (fanout > 0 && fanout <= 16)
       DGLA_PICK(16);
     else if (fanout > 0 && fanout <= 32)
@@ -505,19 +504,17 @@ int run_sample_weighted(const dgla_csr* csc, const void* prob, const void* seeds
                         int fanout, int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
                         void* out_eids, char* ws, const SampleLayout& L, hipStream_t s,
                         const int64_t* num_valid = nullptr, const int64_t* rng_counter = nullptr, int sinks = 0) {
+  const TypedCsr<Idx> g(csc);
   Idx* counts = reinterpret_cast<Idx*>(ws + L.counts);
   const unsigned blocks = static_cast<unsigned>((num_seeds + 1 + 3) / 4);  // 4 waves = 4 rows per block
-  hipLaunchKernelGGL((weighted_count_kernel<Idx, F>), dim3(blocks), dim3(256), 0, s,
-                     static_cast<const Idx*>(csc->indptr), static_cast<const Idx*>(csc->data),
-                     static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, replace,
-                     counts, num_valid);
+  hipLaunchKernelGGL((weighted_count_kernel<Idx, F>), dim3(blocks), dim3(256), 0, s, g.indptr, g.data,
+                     static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, replace, counts,
+                     num_valid);
   if (msd::exclusive_scan<Idx, Idx>(counts, static_cast<Idx*>(out_indptr), num_seeds + 1, ws + L.scan, s)) return -1;
   if (out_src && num_seeds > 0)
-    hipLaunchKernelGGL((weighted_pick_kernel<Idx, F>), dim3(static_cast<unsigned>((num_seeds + 3) / 4)),
-                       dim3(256), 0, s, static_cast<const Idx*>(csc->indptr),
-                       static_cast<const Idx*>(csc->indices), static_cast<const Idx*>(csc->data),
-                       static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds, fanout, replace,
-                       rng_seed, static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_src),
+    hipLaunchKernelGGL((weighted_pick_kernel<Idx, F>), dim3(static_cast<unsigned>((num_seeds + 3) / 4)), dim3(256), 0, s,
+                       g.indptr, g.indices, g.data, static_cast<const F*>(prob), static_cast<const Idx*>(seeds), num_seeds,
+                       fanout, replace, rng_seed, static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_src),
                        static_cast<Idx*>(out_eids), rng_counter);
   if (sinks > 0) launch_pad_tail<Idx>(seeds, num_seeds, fanout, sinks, num_valid, out_indptr, out_src, out_eids, s);
   DGLA_CHECK_HIP(hipGetLastError());
@@ -554,6 +551,9 @@ int run_to_block(const void* seeds, int64_t num_seeds, const void* src, int64_t 
 }
 
 // the sampler for the call's id width and, when `weighted`, its probability type
+// the samplers read indptr and, through the picks, indices and data; no size of the csc
+constexpr unsigned kSampleCsr = kCsrAnySizes | kCsrAnyIndices;
+
 int dispatch_sample(bool weighted, const dgla_csr* csc, const void* prob, dgla_dtype prob_dtype, const void* seeds,
                     int64_t num_seeds, int fanout, int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
                     void* out_eids, char* ws, const SampleLayout& L, hipStream_t s, const int64_t* num_valid = nullptr,
@@ -567,7 +567,7 @@ int dispatch_sample(bool weighted, const dgla_csr* csc, const void* prob, dgla_d
     if (!weighted)
       return run_sample<Idx>(csc, seeds, num_seeds, fanout, replace, rng_seed, out_indptr, out_src, out_eids, ws, L, s,
                              num_valid, rng_counter, sinks);
-    return prob_dtype == DGLA_F32 ? weighted_as(float{}) : weighted_as(double{});
+    return with_float(prob_dtype, weighted_as);
   });
 }
 
@@ -594,8 +594,7 @@ size_t dgla_sample_neighbors_workspace_bytes(int idtype_bits, int64_t num_seeds)
 int dgla_sample_neighbors(const dgla_csr* csc, const void* seeds, int64_t num_seeds, int fanout,
                           int replace, uint64_t rng_seed, void* out_indptr, void* out_src,
                           void* out_eids, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !csc->indptr) return fail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (check_csr("sample_neighbors", csc, kSampleCsr)) return -1;
   if (num_seeds < 0) return fail("negative number of seeds");
   if (fanout > kMaxFanout) return fail("fanout larger than " + std::to_string(kMaxFanout) + " is not supported");
   if (fanout == 0 || fanout < -1) return fail("fanout must be positive, or -1 for all neighbours");
@@ -614,8 +613,7 @@ int dgla_sample_neighbors_weighted(const dgla_csr* csc, const void* prob, dgla_d
                                    const void* seeds, int64_t num_seeds, int fanout, int replace,
                                    uint64_t rng_seed, void* out_indptr, void* out_src, void* out_eids,
                                    void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!csc || !csc->indptr) return fail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (check_csr("sample_neighbors_weighted", csc, kSampleCsr)) return -1;
   if (prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("probabilities must be float32 or float64");
   if (!prob && csc->nnz > 0) return fail("prob is null");
   if (num_seeds < 0) return fail("negative number of seeds");
@@ -637,10 +635,10 @@ int dgla_sample_neighbors_padded(const dgla_csr* csc, const void* prob, dgla_dty
                                  uint64_t rng_seed, const int64_t* rng_counter, int sink_rows, void* out_indptr,
                                  void* out_src, void* out_eids, void* workspace, size_t workspace_bytes,
                                  void* hip_stream) {
+  const char* who = "sample_neighbors_padded";
   if (sink_rows < 1 || sink_rows > 4096) return fail("sink_rows must be in [1, 4096]");
   if (prob && prob_dtype != DGLA_F32 && prob_dtype != DGLA_F64) return fail("probabilities must be float32 or float64");
-  if (!csc || !csc->indptr) return fail("csc is null");
-  if (csc->idtype_bits != 32 && csc->idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (check_csr(who, csc, kSampleCsr)) return -1;
   if (num_seeds < 1) return fail("the padded form needs at least one seed slot");
   if (fanout < 1 || fanout > kMaxFanout)
     return fail("the padded form needs 1 <= fanout <= " + std::to_string(kMaxFanout));
@@ -648,8 +646,7 @@ int dgla_sample_neighbors_padded(const dgla_csr* csc, const void* prob, dgla_dty
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
   const SampleLayout L = sample_layout(csc->idtype_bits, num_seeds);
-  if (!workspace || workspace_bytes < L.bytes)  // no allocation here: the call must be capturable
-    return fail("sample_neighbors_padded: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;  // (the call must be capturable)
   return dispatch_sample(prob != nullptr, csc, prob, prob_dtype, seeds, num_seeds, fanout, replace, rng_seed, out_indptr,
                          out_src, out_eids, static_cast<char*>(workspace), L, s, num_valid, rng_counter, sink_rows);
 }
@@ -665,7 +662,7 @@ int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, 
     key_bits = 1;
     while ((int64_t(1) << key_bits) < num_nodes) ++key_bits;
   }
-  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (!idbits_ok(idtype_bits)) return fail("idtype must be int32 or int64");
   if (num_seeds < 1 || nnz < 0) return fail("bad size");
   if (!node_map || !src_nodes || !num_src_out || !seeds) return fail("node_map / src_nodes / num_src_out / seeds is null");
   if (nnz > 0 && (!src || !local_src)) return fail("input arrays are null");
@@ -673,8 +670,7 @@ int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, 
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, node_map);
   const BlockLayout L = block_layout(idtype_bits, nnz);
-  if (!workspace || workspace_bytes < L.bytes)
-    return fail("to_block_padded: workspace of " + std::to_string(L.bytes) + " bytes required");
+  if (need_workspace("to_block_padded", workspace, workspace_bytes, L.bytes)) return -1;
   return dispatch_to_block(idtype_bits, seeds, num_seeds, src, nnz, node_map, local_src, src_nodes, num_src_out,
                            static_cast<char*>(workspace), L, s, num_valid, key_bits);
 }
@@ -682,7 +678,7 @@ int dgla_to_block_padded(int idtype_bits, const void* seeds, int64_t num_seeds, 
 int dgla_to_block(int idtype_bits, const void* seeds, int64_t num_seeds, const void* src, int64_t nnz,
                   void* node_map, void* local_src, void* src_nodes, int64_t* num_src_out,
                   void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (idtype_bits != 32 && idtype_bits != 64) return fail("idtype must be int32 or int64");
+  if (!idbits_ok(idtype_bits)) return fail("idtype must be int32 or int64");
   if (num_seeds < 0 || nnz < 0) return fail("negative size");
   if (!node_map || !src_nodes || !num_src_out) return fail("node_map / src_nodes / num_src_out is null");
   if ((num_seeds > 0 && !seeds) || (nnz > 0 && (!src || !local_src))) return fail("input arrays are null");

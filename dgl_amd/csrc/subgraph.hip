@@ -201,26 +201,21 @@ SubLayout subgraph_layout(int idtype_bits, int64_t nr, int64_t total) {
 }
 
 int check_map(const char* who, int idtype_bits, const void* ids, int64_t n, const void* map, int64_t map_len) {
-  const std::string w = std::string(who) + ": ";
-  if (idtype_bits != 32 && idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (n < 0 || map_len < 0) return fail(w + "negative size");
-  if (n >= (int64_t(1) << 31)) return fail(w + "n must be below 2^31 (local ids are int32), got " + std::to_string(n));
-  if (n > 0 && !ids) return fail(w + "ids is null");
-  if (n > 0 && map_len > 0 && !map) return fail(w + "map is null");
+  if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
+  if (n < 0 || map_len < 0) return fail(who, "negative size");
+  if (n >= (int64_t(1) << 31)) return fail(who, "n must be below 2^31 (local ids are int32), got " + std::to_string(n));
+  if (n > 0 && !ids) return fail(who, "ids is null");
+  if (n > 0 && map_len > 0 && !map) return fail(who, "map is null");
   return 0;
 }
 
 // everything the subgraph entry points refuse
 int check_subgraph(const char* who, const dgla_csr* csr, const void* rows, int64_t nr, const void* out_indptr) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0 || nr < 0) return fail(w + "negative size");
-  if (nr >= (int64_t(1) << 31)) return fail(w + "the number of rows must be below 2^31, got " + std::to_string(nr));
-  if (nr > 0 && !rows) return fail(w + "rows is null");
-  if (csr->num_rows > 0 && !csr->indptr) return fail(w + "indptr is null");
-  if (csr->nnz > 0 && !csr->indices) return fail(w + "indices is null");
-  if (!out_indptr) return fail(w + "out_indptr is null");
+  if (check_csr(who, csr, kCsrCols | kCsrEmptyIndptr)) return -1;
+  if (nr < 0) return fail(who, "negative size");
+  if (nr >= (int64_t(1) << 31)) return fail(who, "the number of rows must be below 2^31, got " + std::to_string(nr));
+  if (nr > 0 && !rows) return fail(who, "rows is null");
+  if (!out_indptr) return fail(who, "out_indptr is null");
   return 0;
 }
 
@@ -233,15 +228,13 @@ decltype(auto) with_group(const dgla_csr* csr, F&& f) {
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx>
-void subgraph_host(const dgla_csr* csr, const Idx* rows, int64_t nr, const Idx* cols, int64_t nc, int eid_order,
+void subgraph_host(const TypedCsr<Idx>& g, const Idx* rows, int64_t nr, const Idx* cols, int64_t nc, int eid_order,
                    Idx* out_indptr, Idx* out_row, Idx* out_col, Idx* out_eid, int64_t* total, int32_t* flags) {
-  const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-            *data = static_cast<const Idx*>(csr->data);
-  std::vector<int32_t> map(static_cast<size_t>(csr->num_cols), -1);
+  std::vector<int32_t> map(static_cast<size_t>(g.num_cols), -1);
   int32_t fl = 0;
   for (int64_t i = 0; i < nc; ++i) {
     const int64_t v = static_cast<int64_t>(cols[i]);
-    if (v < 0 || v >= csr->num_cols)
+    if (v < 0 || v >= g.num_cols)
       fl |= kSubgraphOutOfRange;
     else if (map[v] >= 0)
       fl |= kSubgraphDuplicate;   // (the first writer keeps the slot; a flagged call has no defined result)
@@ -250,20 +243,20 @@ void subgraph_host(const dgla_csr* csr, const Idx* rows, int64_t nr, const Idx* 
   }
   for (int64_t i = 0; i < nr; ++i) {
     const int64_t r = static_cast<int64_t>(rows[i]);
-    if (r < 0 || r >= csr->num_rows) fl |= kSubgraphOutOfRange;
+    if (r < 0 || r >= g.num_rows) fl |= kSubgraphOutOfRange;
   }
   int64_t at = 0;
   for (int64_t i = 0; i < nr; ++i) {
     out_indptr[i] = static_cast<Idx>(at);
     int64_t lo, hi;
-    subgraph_row(indptr, rows, csr->num_rows, i, &lo, &hi);
+    subgraph_row(g.indptr, rows, g.num_rows, i, &lo, &hi);
     for (int64_t j = lo; j < hi; ++j) {
-      const int32_t l = subgraph_entry(indices, map.data(), csr->num_cols, j);
+      const int32_t l = subgraph_entry(g.indices, map.data(), g.num_cols, j);
       if (l < 0) continue;
       if (out_row) {
         out_row[at] = static_cast<Idx>(i);
         out_col[at] = static_cast<Idx>(l);
-        out_eid[at] = subgraph_eid<Idx>(data, j);
+        out_eid[at] = subgraph_eid<Idx>(g.data, j);
       }
       ++at;
     }
@@ -288,8 +281,9 @@ extern "C" {
 
 int dgla_node_map_mark(int idtype_bits, const void* ids, int64_t n, int32_t* map, int64_t map_len, int32_t* flags,
                        void* hip_stream) {
-  if (check_map("node_map_mark", idtype_bits, ids, n, map, map_len)) return -1;
-  if (!flags) return fail("node_map_mark: flags is null");
+  const char* who = "node_map_mark";
+  if (check_map(who, idtype_bits, ids, n, map, map_len)) return -1;
+  if (!flags) return fail(who, "flags is null");
   if (n == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, flags);
@@ -319,21 +313,21 @@ int dgla_node_map_clear(int idtype_bits, const void* ids, int64_t n, int32_t* ma
 }
 
 size_t dgla_induced_subgraph_workspace_bytes(int idtype_bits, int64_t nr, int64_t total) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || nr < 0 || nr >= (int64_t(1) << 31) || total < 0) return 0;
+  if (!idbits_ok(idtype_bits) || nr < 0 || nr >= (int64_t(1) << 31) || total < 0) return 0;
   return subgraph_layout(idtype_bits, nr, total).bytes;
 }
 
 int dgla_induced_subgraph_count(const dgla_csr* csr, const void* rows, int64_t nr, const int32_t* col_map, void* out_indptr,
                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_subgraph("induced_subgraph_count", csr, rows, nr, out_indptr)) return -1;
-  if (!col_map) return fail("induced_subgraph_count: col_map is null");
+  const char* who = "induced_subgraph_count";
+  if (check_subgraph(who, csr, rows, nr, out_indptr)) return -1;
+  if (!col_map) return fail(who, "col_map is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const bool sweep = nr > 0 && csr->nnz > 0 && csr->num_cols > 0;  // otherwise every row is empty: no graph memory is read
   SubLayout L{};
   if (sweep) {
     L = subgraph_layout(csr->idtype_bits, nr, 0);
-    if (!workspace || workspace_bytes < L.bytes)  // no allocation here
-      return fail("induced_subgraph_count: workspace of " + std::to_string(L.bytes) + " bytes required");
+    if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   }
   const DeviceGuard dev(s, out_indptr);
   char* ws = static_cast<char*>(workspace);
@@ -341,11 +335,11 @@ int dgla_induced_subgraph_count(const dgla_csr* csr, const void* rows, int64_t n
   if (sweep) {
     with_idx(csr->idtype_bits, [&](auto tag) {
       using Idx = decltype(tag);
-      with_group(csr, [&](auto g) {
-        constexpr int G = decltype(g)::value;
-        hipLaunchKernelGGL((subgraph_count_kernel<Idx, G>), dim3(grid1(nr, kSubBlock / G)), dim3(kSubBlock), 0, s,
-                           static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
-                           static_cast<const Idx*>(rows), nr, csr->num_rows, csr->num_cols, col_map, offs);
+      const TypedCsr<Idx> g(csr);
+      with_group(csr, [&](auto grp) {
+        constexpr int G = decltype(grp)::value;
+        hipLaunchKernelGGL((subgraph_count_kernel<Idx, G>), dim3(grid1(nr, kSubBlock / G)), dim3(kSubBlock), 0, s, g.indptr,
+                           g.indices, static_cast<const Idx*>(rows), nr, g.num_rows, g.num_cols, col_map, offs);
       });
     });
     DGLA_CHECK_HIP(hipGetLastError());
@@ -363,21 +357,21 @@ int dgla_induced_subgraph_count(const dgla_csr* csr, const void* rows, int64_t n
 int dgla_induced_subgraph_fill(const dgla_csr* csr, const void* rows, int64_t nr, const int32_t* col_map,
                                const void* out_indptr, int64_t total, void* out_row, void* out_col, void* out_eid,
                                int eid_order, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (check_subgraph("induced_subgraph_fill", csr, rows, nr, out_indptr)) return -1;
-  if (!col_map) return fail("induced_subgraph_fill: col_map is null");
-  if (total < 0) return fail("induced_subgraph_fill: negative total");
-  if (total > csr->nnz) return fail("induced_subgraph_fill: total exceeds the csr's nnz");
+  const char* who = "induced_subgraph_fill";
+  if (check_subgraph(who, csr, rows, nr, out_indptr)) return -1;
+  if (!col_map) return fail(who, "col_map is null");
+  if (total < 0) return fail(who, "negative total");
+  if (total > csr->nnz) return fail(who, "total exceeds the csr's nnz");
   if (nr == 0 || total == 0) return 0;  // nothing was counted
-  if (!out_row || !out_col || !out_eid) return fail("induced_subgraph_fill: out_row / out_col / out_eid are null");
+  if (!out_row || !out_col || !out_eid) return fail(who, "out_row / out_col / out_eid are null");
   const int pb = msd::bits_for(total), eb = msd::bits_for(csr->nnz);
   SubLayout L{};
   if (eid_order) {
     if (pb + eb > 63)
-      return fail("induced_subgraph_fill: the eid order packs (edge id, position) into 63 bits; " + std::to_string(eb) +
-                  " + " + std::to_string(pb) + " bits do not fit");
+      return fail(who, "the eid order packs (edge id, position) into 63 bits; " + std::to_string(eb) + " + " +
+                           std::to_string(pb) + " bits do not fit");
     L = subgraph_layout(csr->idtype_bits, nr, total);
-    if (!workspace || workspace_bytes < L.bytes)
-      return fail("induced_subgraph_fill: workspace of " + std::to_string(L.bytes) + " bytes required");
+    if (need_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   }
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_row);
@@ -385,19 +379,18 @@ int dgla_induced_subgraph_fill(const dgla_csr* csr, const void* rows, int64_t nr
   int rc = 0;
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
-    const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-              *data = static_cast<const Idx*>(csr->data), *rws = static_cast<const Idx*>(rows),
-              *optr = static_cast<const Idx*>(out_indptr);
+    const TypedCsr<Idx> g(csr);
+    const Idx *rws = static_cast<const Idx*>(rows), *optr = static_cast<const Idx*>(out_indptr);
     Idx *o_row = static_cast<Idx*>(out_row), *o_col = static_cast<Idx*>(out_col), *o_eid = static_cast<Idx*>(out_eid);
-    with_group(csr, [&](auto g) {
-      constexpr int G = decltype(g)::value;
+    with_group(csr, [&](auto grp) {
+      constexpr int G = decltype(grp)::value;
       const dim3 grid(grid1(nr, kSubBlock / G)), block(kSubBlock);
       if (!eid_order) {
-        hipLaunchKernelGGL((subgraph_fill_kernel<Idx, G, false>), grid, block, 0, s, indptr, indices, data, rws, nr,
-                           csr->num_rows, csr->num_cols, col_map, optr, o_row, o_col, o_eid, static_cast<int64_t*>(nullptr), 0, total);
+        hipLaunchKernelGGL((subgraph_fill_kernel<Idx, G, false>), grid, block, 0, s, g.indptr, g.indices, g.data, rws, nr,
+                           g.num_rows, g.num_cols, col_map, optr, o_row, o_col, o_eid, static_cast<int64_t*>(nullptr), 0, total);
       } else {
-        hipLaunchKernelGGL((subgraph_fill_kernel<Idx, G, true>), grid, block, 0, s, indptr, indices, data, rws, nr,
-                           csr->num_rows, csr->num_cols, col_map, optr, reinterpret_cast<Idx*>(ws + L.tmp_row),
+        hipLaunchKernelGGL((subgraph_fill_kernel<Idx, G, true>), grid, block, 0, s, g.indptr, g.indices, g.data, rws, nr,
+                           g.num_rows, g.num_cols, col_map, optr, reinterpret_cast<Idx*>(ws + L.tmp_row),
                            reinterpret_cast<Idx*>(ws + L.tmp_col), static_cast<Idx*>(nullptr), reinterpret_cast<int64_t*>(ws + L.keys), pb,
                            total);
       }
@@ -419,15 +412,16 @@ int dgla_induced_subgraph_fill(const dgla_csr* csr, const void* rows, int64_t nr
 int dgla_induced_subgraph_host(const dgla_csr* csr, const void* rows, int64_t nr, const void* cols, int64_t nc,
                                int eid_order, void* out_indptr, void* out_row, void* out_col, void* out_eid, int64_t* total,
                                int32_t* flags) {
-  if (check_subgraph("induced_subgraph_host", csr, rows, nr, out_indptr)) return -1;
-  if (nc < 0) return fail("induced_subgraph_host: negative size");
-  if (nc >= (int64_t(1) << 31)) return fail("induced_subgraph_host: the number of columns must be below 2^31");
-  if (nc > 0 && !cols) return fail("induced_subgraph_host: cols is null");
-  if (!total || !flags) return fail("induced_subgraph_host: total / flags are null");
-  if (out_row && (!out_col || !out_eid)) return fail("induced_subgraph_host: out_col / out_eid are null");
+  const char* who = "induced_subgraph_host";
+  if (check_subgraph(who, csr, rows, nr, out_indptr)) return -1;
+  if (nc < 0) return fail(who, "negative size");
+  if (nc >= (int64_t(1) << 31)) return fail(who, "the number of columns must be below 2^31");
+  if (nc > 0 && !cols) return fail(who, "cols is null");
+  if (!total || !flags) return fail(who, "total / flags are null");
+  if (out_row && (!out_col || !out_eid)) return fail(who, "out_col / out_eid are null");
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
-    subgraph_host<Idx>(csr, static_cast<const Idx*>(rows), nr, static_cast<const Idx*>(cols), nc, eid_order,
+    subgraph_host<Idx>(TypedCsr<Idx>(csr), static_cast<const Idx*>(rows), nr, static_cast<const Idx*>(cols), nc, eid_order,
                        static_cast<Idx*>(out_indptr), static_cast<Idx*>(out_row), static_cast<Idx*>(out_col),
                        static_cast<Idx*>(out_eid), total, flags);
   });

@@ -257,30 +257,25 @@ bool topk_dtype_ok(int dt) { return dt >= kTopkF32 && dt <= kTopkI64; }
 // everything dgla_select_topk and dgla_select_topk_host refuse before they read an array
 int check_topk(const char* who, const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds,
                int64_t num_seeds, int64_t k, const void* out_indptr) {
-  const std::string w = std::string(who) + ": ";
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->nnz < 0) return fail(w + "invalid csr: negative size");
-  if (!csr->indptr) return fail(w + "invalid csr: indptr is null");
-  if (csr->nnz > 0 && !csr->indices) return fail(w + "invalid csr: indices is null");
-  if (!weight && csr->nnz > 0) return fail(w + "weight is null");
+  if (check_csr(who, csr)) return -1;
+  if (!weight && csr->nnz > 0) return fail(who, "weight is null");
   if (!topk_dtype_ok(weight_dtype))
-    return fail(w + "unsupported weight dtype " + std::to_string(weight_dtype) +
-                " (fp32, fp64, fp16, bf16, int32 and int64 are accepted)");
-  if (num_seeds < 0) return fail(w + "negative number of seeds");
-  if (num_seeds > 0 && !seeds) return fail(w + "seeds is null");
-  if (k < -1) return fail(w + "k must be -1 (all), 0 or positive, got " + std::to_string(k));
-  if (!out_indptr) return fail(w + "out_indptr is null");
+    return fail(who, "unsupported weight dtype " + std::to_string(weight_dtype) +
+                         " (fp32, fp64, fp16, bf16, int32 and int64 are accepted)");
+  if (num_seeds < 0) return fail(who, "negative number of seeds");
+  if (num_seeds > 0 && !seeds) return fail(who, "seeds is null");
+  if (k < -1) return fail(who, "k must be -1 (all), 0 or positive, got " + std::to_string(k));
+  if (!out_indptr) return fail(who, "out_indptr is null");
   return 0;
 }
 
 int topk_over(const char* who, int64_t picks) {
-  return fail(std::string(who) + ": a row yields " + std::to_string(picks) + " picks, which exceeds the limit of " +
-              std::to_string(kTopkMaxPicks) + " picks per row (select_topk_max_picks)");
+  return fail(who, "a row yields " + std::to_string(picks) + " picks, which exceeds the limit of " +
+                       std::to_string(kTopkMaxPicks) + " picks per row (select_topk_max_picks)");
 }
 
 int topk_bad_seed(const char* who, int64_t num_rows) {
-  return fail(std::string(who) + ": a seed lies outside [0, " + std::to_string(num_rows) + ")");
+  return fail(who, "a seed lies outside [0, " + std::to_string(num_rows) + ")");
 }
 
 // f(std::integral_constant<int, DT>{}) for the weight type of a call, checked by the caller
@@ -298,20 +293,18 @@ int with_topk_dtype(int dt, F&& f) {
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx, int DT>
-int select_topk_host(const char* who, const dgla_csr* csr, const void* weight, const Idx* seeds, int64_t n, int64_t k,
+int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight, const Idx* seeds, int64_t n, int64_t k,
                      bool asc, Idx* out_indptr, Idx* out_nbr, Idx* out_eids) {
   using K = typename TopkTypes<DT>::key;
   using Word = typename TopkTypes<DT>::word;
   using U = typename std::make_unsigned<Idx>::type;
-  const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-            *data = static_cast<const Idx*>(csr->data);
   const Word* w = static_cast<const Word*>(weight);
   // refusals that need the arrays, before anything is written
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
-    topk_row(indptr, seeds, csr->num_rows, csr->nnz, i, &lo, &hi, &bad);
-    if (bad) return topk_bad_seed(who, csr->num_rows);
+    topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
+    if (bad) return topk_bad_seed(who, g.num_rows);
     const int64_t p = topk_picks(hi - lo, k);
     if (p > kTopkMaxPicks) return topk_over(who, p);
   }
@@ -325,7 +318,7 @@ int select_topk_host(const char* who, const dgla_csr* csr, const void* weight, c
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
-    topk_row(indptr, seeds, csr->num_rows, csr->nnz, i, &lo, &hi, &bad);
+    topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
     const int64_t p = topk_picks(hi - lo, k);
     out_indptr[i] = static_cast<Idx>(at);
     if (p == 0 || !out_nbr) {
@@ -334,15 +327,15 @@ int select_topk_host(const char* who, const dgla_csr* csr, const void* weight, c
     }
     row.resize(static_cast<size_t>(hi - lo));
     for (int64_t q = lo; q < hi; ++q) {
-      const int64_t e = topk_eid(data, q);
-      row[q - lo] = Entry{topk_edge_key<DT>(w, csr->nnz, e, asc), static_cast<U>(e), static_cast<uint32_t>(q - lo)};
+      const int64_t e = topk_eid(g.data, q);
+      row[q - lo] = Entry{topk_edge_key<DT>(w, g.nnz, e, asc), static_cast<U>(e), static_cast<uint32_t>(q - lo)};
     }
     std::partial_sort(row.begin(), row.begin() + p, row.end(), [](const Entry& a, const Entry& b) {
       return topk_before(a.key, a.eid, a.pos, b.key, b.eid, b.pos);
     });
     for (int64_t r = 0; r < p; ++r) {
       out_eids[at + r] = static_cast<Idx>(row[r].eid);
-      out_nbr[at + r] = indices[lo + row[r].pos];
+      out_nbr[at + r] = g.indices[lo + row[r].pos];
     }
     at += p;
   }
@@ -353,10 +346,10 @@ int select_topk_host(const char* who, const dgla_csr* csr, const void* weight, c
 template <typename Idx, int DT, int NT, int G, int CAP>
 void launch_select(const dgla_csr* csr, const void* weight, const void* seeds, int64_t n, int64_t k, int asc, void* out_indptr,
                    void* out_nbr, void* out_eids, hipStream_t s) {
-  hipLaunchKernelGGL((topk_select_kernel<Idx, DT, NT, G, CAP>), dim3(grid1(n, NT / G)), dim3(NT), 0, s,
-                     static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(csr->indices),
-                     static_cast<const Idx*>(csr->data), weight, static_cast<const Idx*>(seeds), n, csr->num_rows, csr->nnz, k,
-                     asc, static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eids));
+  const TypedCsr<Idx> g(csr);
+  hipLaunchKernelGGL((topk_select_kernel<Idx, DT, NT, G, CAP>), dim3(grid1(n, NT / G)), dim3(NT), 0, s, g.indptr, g.indices,
+                     g.data, weight, static_cast<const Idx*>(seeds), n, g.num_rows, g.nnz, k, asc,
+                     static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eids));
 }
 
 }  // namespace
@@ -369,7 +362,7 @@ extern "C" {
 int dgla_select_topk_max_picks(void) { return kTopkMaxPicks; }
 
 size_t dgla_select_topk_workspace_bytes(int idtype_bits, int64_t num_seeds) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || num_seeds <= 0) return 0;
+  if (!idbits_ok(idtype_bits) || num_seeds <= 0) return 0;
   return topk_layout(num_seeds).bytes;
 }
 
@@ -378,7 +371,7 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
                      size_t workspace_bytes, void* hip_stream) {
   const char* who = "select_topk";
   if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr)) return -1;
-  if (out_nbr && !out_eids) return fail(std::string(who) + ": out_eids is null");
+  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
   const int64_t n = num_seeds;
@@ -388,10 +381,8 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
     return 0;
   }
   const TopkLayout L = topk_layout(n);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("select_topk: workspace of " + std::to_string(L.bytes) + " bytes required, got " +
-                std::to_string(workspace_bytes));
-  Scratch scratch(s);  // the caller's workspace, else stream-ordered scratch for the duration of the call
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
+  Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
   int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.picks);
   int64_t* flags = reinterpret_cast<int64_t*>(scratch.p + L.flags);
@@ -399,8 +390,7 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
   const int rc = with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
     hipLaunchKernelGGL(topk_count_kernel<Idx>, dim3(grid1(n + 1, kTopkCountBlock)), dim3(kTopkCountBlock), 0, s,
-                       static_cast<const Idx*>(csr->indptr), static_cast<const Idx*>(seeds), n, csr->num_rows, csr->nnz, k, picks,
-                       flags);
+                       TypedCsr<Idx>(csr).indptr, static_cast<const Idx*>(seeds), n, csr->num_rows, csr->nnz, k, picks, flags);
     return msd::exclusive_scan<int64_t, Idx>(picks, static_cast<Idx*>(out_indptr), n + 1, scratch.p + L.scan, s);
   });
   if (rc) return -1;
@@ -409,9 +399,7 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
   int64_t bound = k;
   if (k < 0 || k > kTopkMaxPicks) {
     int64_t fl[kFlWords];
-    DGLA_CHECK_HIP(hipGetLastError());
-    DGLA_CHECK_HIP(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
-    DGLA_CHECK_HIP(hipStreamSynchronize(s));
+    if (read_back(fl, flags, sizeof(fl), s)) return -1;
     if (fl[kFlBadSeed]) return topk_bad_seed(who, csr->num_rows);
     if (fl[kFlOver]) return topk_over(who, fl[kFlOverPicks]);
     bound = fl[kFlAboveB] ? kTopkCapC : (fl[kFlAboveA] ? kTopkCapB : kTopkCapA);
@@ -443,12 +431,12 @@ int dgla_select_topk_host(const dgla_csr* csr, const void* weight, int weight_dt
                           int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids) {
   const char* who = "select_topk_host";
   if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr)) return -1;
-  if (out_nbr && !out_eids) return fail(std::string(who) + ": out_eids is null");
+  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
   return with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
     return with_topk_dtype(weight_dtype, [&](auto dt) -> int {
       constexpr int DT = decltype(dt)::value;
-      return select_topk_host<Idx, DT>(who, csr, weight, static_cast<const Idx*>(seeds), num_seeds, k, ascending != 0,
+      return select_topk_host<Idx, DT>(who, TypedCsr<Idx>(csr), weight, static_cast<const Idx*>(seeds), num_seeds, k, ascending != 0,
                                        static_cast<Idx*>(out_indptr), static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eids));
     });
   });

@@ -249,61 +249,55 @@ TravLayout trav_layout(int idtype_bits, int64_t n) {
 int check_traverse(const char* who, int mode, const dgla_csr* csr, const dgla_csr* opposite, const void* sources,
                    int64_t num_sources, const void* ids, const int64_t* sections, const int64_t* num_ids,
                    const int64_t* num_sections) {
-  const std::string w = std::string(who) + ": ";
   if (mode != DGLA_TRAVERSE_BFS_NODES && mode != DGLA_TRAVERSE_BFS_EDGES && mode != DGLA_TRAVERSE_TOPO_NODES)
-    return fail(w + "unknown mode " + std::to_string(mode));
-  if (!csr) return fail(w + "csr is null");
-  if (csr->idtype_bits != 32 && csr->idtype_bits != 64) return fail(w + "idtype must be int32 or int64");
-  if (csr->num_rows < 0 || csr->num_cols < 0 || csr->nnz < 0) return fail(w + "invalid csr: negative size");
+    return fail(who, "unknown mode " + std::to_string(mode));
+  if (check_csr(who, csr, kCsrCols)) return -1;
   if (csr->num_rows != csr->num_cols)
-    return fail(w + "invalid csr: traversal needs a square CSR, got " + std::to_string(csr->num_rows) + " x " +
-                std::to_string(csr->num_cols));
-  if (!csr->indptr) return fail(w + "invalid csr: indptr is null");
-  if (csr->nnz > 0 && !csr->indices) return fail(w + "invalid csr: indices is null");
-  if (!num_ids || !num_sections) return fail(w + "num_ids / num_sections are null");
+    return fail(who, "invalid csr: traversal needs a square CSR, got " + std::to_string(csr->num_rows) + " x " +
+                         std::to_string(csr->num_cols));
+  if (!num_ids || !num_sections) return fail(who, "num_ids / num_sections are null");
   if (mode == DGLA_TRAVERSE_TOPO_NODES) {
     if (!opposite || !opposite->indptr)
-      return fail(w + "the topological order needs the opposite CSR: its row lengths are the counts");
-    if (opposite->idtype_bits != csr->idtype_bits) return fail(w + "csr and the opposite CSR differ in id type");
+      return fail(who, "the topological order needs the opposite CSR: its row lengths are the counts");
+    if (opposite->idtype_bits != csr->idtype_bits) return fail(who, "csr and the opposite CSR differ in id type");
     if (opposite->num_rows != csr->num_rows || opposite->nnz != csr->nnz)
-      return fail(w + "the count array does not match: the opposite CSR has " + std::to_string(opposite->num_rows) +
-                  " rows and " + std::to_string(opposite->nnz) + " entries, the csr " + std::to_string(csr->num_rows) +
-                  " and " + std::to_string(csr->nnz));
+      return fail(who, "the count array does not match: the opposite CSR has " + std::to_string(opposite->num_rows) +
+                           " rows and " + std::to_string(opposite->nnz) + " entries, the csr " +
+                           std::to_string(csr->num_rows) + " and " + std::to_string(csr->nnz));
   } else {
-    if (num_sources < 0) return fail(w + "negative number of sources");
-    if (num_sources > 0 && !sources) return fail(w + "sources is null");
+    if (num_sources < 0) return fail(who, "negative number of sources");
+    if (num_sources > 0 && !sources) return fail(who, "sources is null");
   }
   const int64_t cap = mode == DGLA_TRAVERSE_BFS_NODES ? csr->num_rows + num_sources : csr->num_rows;
-  if (cap > 0 && (!ids || !sections)) return fail(w + "ids / sections are null");
+  if (cap > 0 && (!ids || !sections)) return fail(who, "ids / sections are null");
   return 0;
 }
 
 int bad_source(const char* who, int64_t n) {
-  return fail(std::string(who) + ": a source lies outside [0, " + std::to_string(n) + ")");
+  return fail(who, "a source lies outside [0, " + std::to_string(n) + ")");
 }
 
 int loop_detected(const char* who, int64_t emitted, int64_t n) {
-  return fail(std::string(who) + ": loop detected in the graph: only " + std::to_string(emitted) + " of " +
-              std::to_string(n) + " nodes have a topological order");
+  return fail(who, "loop detected in the graph: only " + std::to_string(emitted) + " of " + std::to_string(n) +
+                       " nodes have a topological order");
 }
 
 int count_mismatch(const char* who) {
-  return fail(std::string(who) + ": the count array does not match the csr: more nodes were emitted than the graph has");
+  return fail(who, "the count array does not match the csr: more nodes were emitted than the graph has");
 }
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx>
-int traverse_host(const char* who, int mode, const dgla_csr* csr, const dgla_csr* opposite, const Idx* sources, int64_t ns,
+int traverse_host(const char* who, int mode, const TypedCsr<Idx>& g, const dgla_csr* opposite, const Idx* sources, int64_t ns,
                   Idx* ids, int64_t* sections, int64_t* num_ids, int64_t* num_sections) {
-  const int64_t n = csr->num_rows;
-  const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-            *data = static_cast<const Idx*>(csr->data);
+  const int64_t n = g.num_rows;
+  const Idx *indptr = g.indptr, *indices = g.indices, *data = g.data;
   const bool topo = mode == DGLA_TRAVERSE_TOPO_NODES, edges = mode == DGLA_TRAVERSE_BFS_EDGES;
   // refusals that need the arrays: nothing below reads through an id that failed here
   for (int64_t i = 0; i < n; ++i)
-    if (indptr[i + 1] < indptr[i]) return fail(std::string(who) + ": invalid csr: indptr decreases at row " + std::to_string(i));
-  if (static_cast<int64_t>(indptr[0]) != 0 || static_cast<int64_t>(indptr[n]) != csr->nnz)
-    return fail(std::string(who) + ": invalid csr: indptr does not span [0, nnz]");
+    if (indptr[i + 1] < indptr[i]) return fail(who, "invalid csr: indptr decreases at row " + std::to_string(i));
+  if (static_cast<int64_t>(indptr[0]) != 0 || static_cast<int64_t>(indptr[n]) != g.nnz)
+    return fail(who, "invalid csr: indptr does not span [0, nnz]");
   if (!topo)
     for (int64_t i = 0; i < ns; ++i)
       if (sources[i] < 0 || static_cast<int64_t>(sources[i]) >= n) return bad_source(who, n);
@@ -381,7 +375,7 @@ using namespace dgla;
 extern "C" {
 
 size_t dgla_traverse_workspace_bytes(int idtype_bits, int64_t num_nodes) {
-  if ((idtype_bits != 32 && idtype_bits != 64) || num_nodes <= 0) return 0;
+  if (!idbits_ok(idtype_bits) || num_nodes <= 0) return 0;
   return trav_layout(idtype_bits, num_nodes).bytes;
 }
 
@@ -397,11 +391,10 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
   if (n == 0) return ns > 0 ? bad_source(who, n) : 0;  // (no node: every source is outside, and none is read)
   if (!topo && ns == 0) return 0;
   const TravLayout L = trav_layout(csr->idtype_bits, n);
-  if (workspace && workspace_bytes < L.bytes)
-    return fail("traverse: workspace of " + std::to_string(L.bytes) + " bytes required, got " + std::to_string(workspace_bytes));
+  if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, ids);
-  Scratch scratch(s);  // the caller's workspace, else stream-ordered scratch for the duration of the call
+  Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
   // a source list longer than n: the row arrays of frontier 0 do not fit the workspace and take scratch of their own
   Scratch wide(s);
@@ -421,18 +414,13 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
   bool bad = false, over = false;
   const int rc = with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
-    const Idx *indptr = static_cast<const Idx*>(csr->indptr), *indices = static_cast<const Idx*>(csr->indices),
-              *data = static_cast<const Idx*>(csr->data);
+    const TypedCsr<Idx> g(csr);
+    const Idx *indptr = g.indptr, *indices = g.indices, *data = g.data;
     Idx* out = static_cast<Idx*>(ids);
     Idx* nodes = edges ? reinterpret_cast<Idx*>(scratch.p + L.nodes) : out;
     const dim3 block(kTravBlock);
     int64_t st[3] = {0, 0, 0};
-    auto read_back = [&]() -> int {  // the one read-back of a level
-      DGLA_CHECK_HIP(hipGetLastError());
-      DGLA_CHECK_HIP(hipMemcpyAsync(st, state, sizeof(st), hipMemcpyDeviceToHost, s));
-      DGLA_CHECK_HIP(hipStreamSynchronize(s));
-      return 0;
-    };
+    auto read_state = [&]() { return read_back(st, state, sizeof(st), s); };  // the one read-back of a level
     const Idx* f = nullptr;
     int64_t m = 0;
     if (topo) {
@@ -441,7 +429,7 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
                          static_cast<const Idx*>(opposite->indptr), n, key, count, flag, state);
       if (msd::exclusive_scan<int64_t, int64_t>(flag, flag, n + 1, scratch.p + L.rows.scan, s)) return -1;
       hipLaunchKernelGGL(traverse_roots_kernel<Idx>, dim3(grid1(n, kTravBlock)), block, 0, s, count, flag, n, nodes, state);
-      if (read_back()) return -1;
+      if (read_state()) return -1;
       f = nodes, m = st[kStNext], done = m;
     } else {
       const Idx* src = static_cast<const Idx*>(sources);
@@ -476,7 +464,7 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
         if (msd::exclusive_scan<int64_t, int64_t>(cnt, cnt, m + 1, rp + R.scan, s)) return -1;
         hipLaunchKernelGGL((traverse_select_kernel<Idx, G, TOPO, true, EDGES>), rows_grid, block, 0, s, indptr, indices, data, f,
                            m, n, len, off, key, count, cnt, nodes, out, done, cap, state);
-        if (read_back()) return -1;
+        if (read_state()) return -1;
         if (st[kStBad]) {
           bad = true;
           return 0;
@@ -519,7 +507,7 @@ int dgla_traverse_host(int mode, const dgla_csr* csr, const dgla_csr* opposite, 
   *num_ids = *num_sections = 0;
   return with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
-    return traverse_host<Idx>(who, mode, csr, opposite, static_cast<const Idx*>(sources),
+    return traverse_host<Idx>(who, mode, TypedCsr<Idx>(csr), opposite, static_cast<const Idx*>(sources),
                               mode == DGLA_TRAVERSE_TOPO_NODES ? 0 : num_sources, static_cast<Idx*>(ids), sections, num_ids,
                               num_sections);
   });

@@ -34,7 +34,13 @@ def build(force=False):
         os.path.getmtime(os.path.join(_HERE, f)) for f in ("oracle.c", "kernels_impl.inc")
     )
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < src_m:
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
+        # One make at a time: the ranks of a multi-process test all arrive here when nothing is built yet, and the ref
+        # rule removes its object files at its end, under the feet of a second make that is about to link them.
+        import fcntl
+
+        with open(os.path.join(_HERE, ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            subprocess.check_call(["make", "-C", _HERE, "-s"])
     return _LIB_PATH
 
 

@@ -36,6 +36,10 @@ def available():
 def lib():
     global _lib
     if _lib is None:
+        if not available():  # (a tree in which only the oracle was built, or nothing yet: make builds both)
+            from . import build
+
+            build(force=True)
         if not available():
             raise RuntimeError("oracle/_ref/libdglref.so is not built (make -C oracle ref needs "
                                "the reference checkout at /root/reference)")

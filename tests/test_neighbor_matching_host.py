@@ -151,8 +151,8 @@ def test_refusals():
     refused(host(w=w.data_ptr(), wd=2), "neighbor_matching_host", "float16 / bfloat16")
     refused(host(w=w.data_ptr(), wd=3), "neighbor_matching_host", "float16 / bfloat16")
     refused(host(w=w.data_ptr(), wd=9), "neighbor_matching_host: unknown weight dtype 9")
-    for field, msg in (("idtype_bits", "idtype must be int32 or int64"), ("indptr", "indptr is null"),
-                       ("indices", "indices is null")):
+    for field, msg in (("idtype_bits", "idtype must be int32 or int64"), ("indptr", "invalid csr: indptr is null"),
+                       ("indices", "invalid csr: indices is null")):
         broken = host_csr(case, torch.int64)
         setattr(broken, field, 16 if field == "idtype_bits" else None)
         refused(host(csr=ctypes.byref(broken)), "neighbor_matching_host: " + msg)

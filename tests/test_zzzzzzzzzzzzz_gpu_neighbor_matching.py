@@ -71,6 +71,30 @@ def test_batching_and_workspace_change_nothing(dev, batch):
                 assert np.array_equal(got.cpu().numpy(), relabelled)
 
 
+@pytest.mark.parametrize("idtype", [torch.int32, torch.int64], ids=str)
+def test_short_workspace_is_refused(dev, idtype):
+    """need - 256 bytes: the matching and the relabelling both refuse it, in the one wording, before any launch."""
+    from dgl_amd import DGLAMDError, _capi, _lib
+
+    case = min(CASES, key=lambda c: c["n"])
+    csr = device_csr(case, idtype, dev)
+    n = case["n"]
+    need = _lib.LIB.dgla_neighbor_matching_workspace_bytes(csr.idtype_bits, n)
+    assert need > 256
+    short = torch.empty(need - 256, dtype=torch.uint8, device=dev)
+    with pytest.raises(DGLAMDError, match="neighbor_matching: workspace of %d bytes required, got %d" % (need, need - 256)):
+        _capi.neighbor_matching(csr, None, 1, workspace=short)
+    label = torch.arange(n, dtype=idtype, device=dev)
+    out = torch.full_like(label, -7)
+    with pytest.raises(DGLAMDError, match="neighbor_matching_relabel: workspace of %d bytes required, got %d"
+                                          % (need, need - 256)):
+        _lib.check_call(_lib.LIB.dgla_neighbor_matching_relabel(label.data_ptr(), csr.idtype_bits, n, out.data_ptr(),
+                                                                short.data_ptr(), need - 256,
+                                                                torch.cuda.current_stream(dev).cuda_stream))
+    torch.cuda.synchronize(dev)
+    assert bool((out == -7).all())
+
+
 def test_round_cap_on_the_device(dev):
     from dgl_amd import DGLAMDError, _capi
 

@@ -91,6 +91,27 @@ def test_set_equals_the_host_twin(dev, idtype):
 
 
 @pytest.mark.parametrize("idtype", xc.IDTYPES, ids=str)
+def test_a_workspace_256_bytes_short_is_refused(dev, idtype):
+    """need - 256 bytes: exclude_set and compact_nodes refuse it in the one wording, before any launch."""
+    from dgl_amd import _capi, _lib
+
+    name, ids, rev, num_edges, _ = next(c for c in xc.set_cases() if len(c[1]) and not c[4])
+    need = _lib.LIB.dgla_exclude_set_workspace_bytes(_bits(idtype), len(ids), 0 if rev is None else 1)
+    assert need > 256
+    with pytest.raises(_lib.DGLAMDError, match="exclude_set: workspace of %d bytes required, got %d" % (need, need - 256)):
+        _capi.exclude_set(t_(ids, idtype, dev), num_edges, None if rev is None else t_(rev, idtype, dev),
+                          workspace=torch.empty(need - 256, dtype=torch.uint8, device=dev))
+    name, preserve, ends, num_nodes = next(c for c in xc.compact_cases() if len(c[1]) + len(c[2]))
+    node_map = torch.full((num_nodes,), -1, dtype=torch.int32, device=dev)
+    need = _lib.LIB.dgla_compact_nodes_workspace_bytes(_bits(idtype), len(preserve), len(ends))
+    assert need > 256
+    with pytest.raises(_lib.DGLAMDError, match="compact_nodes: workspace of %d bytes required, got %d" % (need, need - 256)):
+        _capi.compact_nodes(t_(preserve, idtype, dev), t_(ends, idtype, dev), node_map,
+                            workspace=torch.empty(need - 256, dtype=torch.uint8, device=dev))
+    assert bool((node_map == -1).all()), name
+
+
+@pytest.mark.parametrize("idtype", xc.IDTYPES, ids=str)
 def test_compaction_equals_the_host_twin_and_cleans_the_map(dev, idtype):
     from dgl_amd import _capi, _lib
 

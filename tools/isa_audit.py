@@ -26,8 +26,9 @@ _LABEL = re.compile(r"^[0-9a-f]+ <(.*)>:$")
 _VMCNT = re.compile(r"vmcnt\((\d+)\)")
 
 
-def disassemble(obj):
-    """Disassembly text of the gfx950 code object bundled in `obj` (None when there is none)."""
+def disassemble(obj, sections=()):
+    """Disassembly text of the gfx950 code object bundled in `obj` (None when there is none): the code sections,
+    or the named `sections` (".rodata" holds the kernel descriptors, printed as .amdhsa_* blocks)."""
     tmp = tempfile.mkdtemp(prefix="isa_audit_")
     try:
         local = os.path.join(tmp, os.path.basename(obj))
@@ -37,7 +38,8 @@ def disassemble(obj):
         cos = glob.glob(local + ".*gfx950*")
         if not cos:
             return None
-        return subprocess.run([OBJDUMP, "-d", cos[0]], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+        only = [a for s in sections for a in ("-j", s)]
+        return subprocess.run([OBJDUMP, "-d"] + only + [cos[0]], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
                               check=True, text=True).stdout
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
