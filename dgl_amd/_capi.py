@@ -1382,6 +1382,103 @@ def select_topk_host(csr, weight, seeds, k, ascending=False):
     return indptr, nbr, eids
 
 
+def _tag_sort(who, csr, tag, num_tags, gpu, into):
+    """The checks and the outputs the two tag-sort entry points share: ``(args, out_indices, out_data, tag_pos)``."""
+    indptr = csr._keep[0]
+    _all_on(gpu, who, indptr, tag)
+    if tag.dtype not in (torch.int32, torch.int64):
+        raise _lib.DGLAMDError("%s: unsupported tag dtype %s (int32 and int64 are accepted)" % (who, tag.dtype))
+    if tag.dim() != 1 or not tag.is_contiguous() or tag.shape[0] != csr.nnz or tag.device != indptr.device:
+        raise _lib.DGLAMDError("%s: tag must be a contiguous 1-D tensor with one value per edge on the csr's device" % who)
+    dev, dt, t = indptr.device, indptr.dtype, int(num_tags)
+    if into is None:
+        into = (torch.empty(csr.nnz, dtype=dt, device=dev), torch.empty(csr.nnz, dtype=dt, device=dev),
+                torch.empty((csr.num_rows, max(t, 0) + 1), dtype=dt, device=dev))
+    args = [ctypes.byref(csr), _ptr(tag), _id_bits(tag.dtype), t] + [_ptr(o) for o in into]
+    return args, into
+
+
+def sort_csr_by_tag(csr, tag, num_tags, into=None):
+    """The rows of `csr` stably sorted by tag (dgla_sort_csr_by_tag; the rule: include/dgl_amd.h "Tag-biased neighbour
+    sampling").  `tag` (int32 / int64) has one value per EDGE ID in ``[0, num_tags)``.  Returns ``(indices, data,
+    tag_pos)``: the sorted neighbour ids, the edge ids in the same order (always materialised) and the row-relative
+    offsets ``[num_rows, num_tags + 1]``; the indptr is the csr's own.  One set of flag words is read back; a tag outside
+    the range raises ``DGLAMDError``.  `into` places the three outputs in the caller's tensors."""
+    args, outs = _tag_sort("sort_csr_by_tag", csr, tag, num_tags, True, into)
+    check_call(LIB.dgla_sort_csr_by_tag(*args, _stream(tag)))
+    return outs
+
+
+def sort_csr_by_tag_host(csr, tag, num_tags):
+    """:func:`sort_csr_by_tag` run by the CPU on CPU tensors (dgla_sort_csr_by_tag_host; CSRs built with
+    :func:`host_csr`).  Needs no GPU."""
+    args, outs = _tag_sort("sort_csr_by_tag_host", csr, tag, num_tags, False, None)
+    check_call(LIB.dgla_sort_csr_by_tag_host(*args))
+    return outs
+
+
+def sample_neighbors_biased_workspace_bytes(idtype, num_seeds):
+    """The bytes of the optional workspace of :func:`sample_neighbors_biased` (host query)."""
+    return int(LIB.dgla_sample_neighbors_biased_workspace_bytes(_id_bits(idtype), int(num_seeds)))
+
+
+def _biased_args(who, csr, tag_offset, bias, seeds, fanout, replace, rng_seed, gpu):
+    """The checks the two biased-sampling entry points share, and their leading arguments."""
+    indptr = csr._keep[0]
+    _all_on(gpu, who, indptr, tag_offset, bias, seeds)
+    if bias.dtype not in (torch.float32, torch.float64):
+        raise _lib.DGLAMDError("%s: unsupported bias dtype %s (fp32 and fp64 are accepted)" % (who, bias.dtype))
+    if bias.dim() != 1 or not bias.is_contiguous() or bias.shape[0] < 1 or bias.device != indptr.device:
+        raise _lib.DGLAMDError("%s: bias must be a contiguous 1-D tensor with one value per tag on the csr's device" % who)
+    t = bias.shape[0]
+    if (tag_offset.dim() != 2 or not tag_offset.is_contiguous() or tag_offset.dtype != indptr.dtype
+            or tag_offset.device != indptr.device or tuple(tag_offset.shape) != (csr.num_rows, t + 1)):
+        raise _lib.DGLAMDError("%s: tag_offset must be a contiguous [%d, %d] tensor of the csr's id type on its device, one "
+                               "row per node and one column more than bias has tags" % (who, csr.num_rows, t + 1))
+    _id_tensor_ok(who, "seeds", seeds, indptr)
+    return [ctypes.byref(csr), _ptr(tag_offset), t, _ptr(bias), _DTYPES[bias.dtype], _ptr(seeds), seeds.shape[0], int(fanout),
+            1 if replace else 0, _u64(rng_seed)]
+
+
+def sample_neighbors_biased(csr, tag_offset, bias, seeds, fanout, replace=False, rng_seed=0, ws=None, into=None):
+    """For every seed row of the tag-sorted `csr`, `fanout` entries drawn with probability proportional to the bias of
+    their tag (dgla_sample_neighbors_biased; the rule: include/dgl_amd.h "Tag-biased neighbour sampling").  Returns
+    ``(indptr, nbr, eids)``, a CSR over the seeds.  For ``fanout >= 0`` the outputs are allocated at ``num_seeds *
+    fanout``, the first ``indptr[-1]`` entries are the result and nothing is read back; for ``fanout = -1`` the sizes
+    come first.  `ws` (uint8, :func:`sample_neighbors_biased_workspace_bytes`) is the optional workspace of the call;
+    `into` places the three outputs in tensors the caller has sized."""
+    args = _biased_args("sample_neighbors_biased", csr, tag_offset, bias, seeds, fanout, replace, rng_seed, True)
+    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
+    wp, wb = _ws(ws)
+    st = _stream(seeds)
+    if into is not None:
+        indptr, nbr, eids = into
+    else:
+        indptr = torch.empty(n + 1, dtype=dt, device=dev)
+        if fanout >= 0:
+            cap = n * int(fanout)
+        else:
+            check_call(LIB.dgla_sample_neighbors_biased(*args, indptr.data_ptr(), None, None, wp, wb, st))
+            cap = int(indptr[-1])
+        nbr = torch.empty(cap, dtype=dt, device=dev)
+        eids = torch.empty(cap, dtype=dt, device=dev)
+    check_call(LIB.dgla_sample_neighbors_biased(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), wp, wb, st))
+    return indptr, nbr, eids
+
+
+def sample_neighbors_biased_host(csr, tag_offset, bias, seeds, fanout, replace=False, rng_seed=0):
+    """:func:`sample_neighbors_biased` run by the CPU on CPU tensors (dgla_sample_neighbors_biased_host): the same rule
+    compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs no GPU."""
+    args = _biased_args("sample_neighbors_biased_host", csr, tag_offset, bias, seeds, fanout, replace, rng_seed, False)
+    n, dt = seeds.shape[0], seeds.dtype
+    indptr = torch.empty(n + 1, dtype=dt)
+    check_call(LIB.dgla_sample_neighbors_biased_host(*args, indptr.data_ptr(), None, None))
+    total = int(indptr[-1])
+    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
+    check_call(LIB.dgla_sample_neighbors_biased_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr()))
+    return indptr, nbr, eids
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(_id_bits(idtype)))

@@ -364,6 +364,22 @@ LIB.dgla_select_topk.restype = c_int
 LIB.dgla_select_topk.argtypes = _TOPK + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_select_topk_host.restype = c_int
 LIB.dgla_select_topk_host.argtypes = _TOPK
+# the tag sort: csr, tag, tag bits, num_tags, out_indices, out_data, tag_pos
+_TAG_SORT = [P(CSR), c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]
+LIB.dgla_sort_csr_by_tag.restype = c_int
+LIB.dgla_sort_csr_by_tag.argtypes = _TAG_SORT + [c_void_p]
+LIB.dgla_sort_csr_by_tag_host.restype = c_int
+LIB.dgla_sort_csr_by_tag_host.argtypes = _TAG_SORT
+# the biased sampler: csr, tag_offset, num_tags, bias, bias dtype, seeds, num_seeds, fanout, replace, rng seed, out_indptr,
+# out_nbr, out_eids
+_BIASED = [P(CSR), c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, ctypes.c_uint64, c_void_p, c_void_p,
+           c_void_p]
+LIB.dgla_sample_neighbors_biased_workspace_bytes.restype = c_size_t
+LIB.dgla_sample_neighbors_biased_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_sample_neighbors_biased.restype = c_int
+LIB.dgla_sample_neighbors_biased.argtypes = _BIASED + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_sample_neighbors_biased_host.restype = c_int
+LIB.dgla_sample_neighbors_biased_host.argtypes = _BIASED
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int

@@ -795,6 +795,74 @@ def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False, copy_n
 DGLGraph.select_topk = select_topk
 
 
+def sample_neighbors_biased(g, nodes, fanout, bias, edge_dir="in", tag_offset_name="_TAG_OFFSET", replace=False,
+                            copy_ndata=True, copy_edata=True, output_device=None, seed=None):
+    """``dgl.sampling.sample_neighbors_biased`` (python/dgl/sampling/neighbor.py:690): for every node in ``nodes``,
+    ``fanout`` inbound (``edge_dir="out"``: outbound) edges, each neighbour drawn with a probability proportional to the
+    bias of its tag; ``fanout == -1`` takes every edge whose tag has a positive bias.
+
+    The graph must have its CSC (``"out"``: CSR) sorted with :func:`dgl_amd.sort_csc_by_tag` (``sort_csr_by_tag``), which
+    also stores the tag offsets under ``tag_offset_name``; like the reference, this function does not test that.  ``bias``
+    holds one non-negative fp32 / fp64 value per tag.  One edge type only.  ``seed`` fixes the draws (default: one drawn
+    from torch's generator); a node listed twice draws the same edges twice.
+
+    Returns a graph with all nodes of ``g`` and only the sampled edges, as :func:`select_topk` assembles it.  A GPU graph
+    runs the kernels of csrc/biased.hip, whose cost per node does not depend on its degree; a CPU graph runs the same
+    rule compiled for the host (the reference has the CPU form only).  The rule is written in include/dgl_amd.h,
+    "Tag-biased neighbour sampling"."""
+    who = "sample_neighbors_biased"
+    if edge_dir not in ("in", "out"):
+        raise _DGLError("edge_dir can only be 'in' or 'out'")
+    if len(g.canonical_etypes) != 1:
+        raise _DGLError("%s: only homogeneous and bipartite graphs (one edge type) are supported" % who)
+    rel = g._graph.relations[0]
+    dev, idt = rel.device, rel.idtype
+    s_id, d_id = g._graph.metagraph.find_edge(0)
+    frame = g._node_frames[d_id if edge_dir == "in" else s_id]
+    if tag_offset_name not in frame:
+        raise _DGLError('%s: the graph has no tag offsets "%s"; sort it with sort_%s_by_tag first'
+                        % (who, tag_offset_name, "csc" if edge_dir == "in" else "csr"))
+    offsets = frame[tag_offset_name].to(device=dev, dtype=idt).contiguous()
+    bias = torch.as_tensor(bias)
+    if not bias.dtype.is_floating_point:
+        bias = bias.float()
+    bias = bias.to(dev).reshape(-1).contiguous()
+    seeds = _node_ids(nodes, dev, idt)
+    rng_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+    fmt = rel.csc() if edge_dir == "in" else rel.csr()
+    cols = rel.num_src if edge_dir == "in" else rel.num_dst
+    if seeds.numel() == 0 or int(fanout) == 0 or rel.num_edges == 0:
+        own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
+    else:
+        if dev.type == "cuda":
+            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
+            indptr, nbr, eids = _capi.sample_neighbors_biased(csr, offsets, bias, seeds, int(fanout), replace, rng_seed)
+        else:
+            csr = _capi.host_csr(fmt[0].contiguous(), fmt[1].contiguous(), None if fmt[2] is None else fmt[2].contiguous(), cols)
+            indptr, nbr, eids = _capi.sample_neighbors_biased_host(csr, offsets, bias, seeds, int(fanout), replace, rng_seed)
+        n_e = int(indptr[-1])
+        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
+        nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
+    src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
+    gi = g._graph
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges),
+                              [Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev)]),
+                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
+    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
+        for i, fr in enumerate(g._node_frames):
+            for key, val in fr.items():
+                out._node_frames[i][key] = val
+    if copy_edata:
+        for key, val in g._edge_frames[0].items():
+            if key != EID:
+                out._edge_frames[0][key] = val[eids.long()]
+    out._edge_frames[0][EID] = eids
+    return out if output_device is None else out.to(output_device)
+
+
+DGLGraph.sample_neighbors_biased = sample_neighbors_biased
+
+
 class LaborSampler:
     """``dgl.dataloading.LaborSampler`` (python/dgl/dataloading/labor_sampler.py): one block per layer, built from the
     output nodes inwards; a layer is :func:`sample_labors` followed by :func:`to_block` on the seeds.

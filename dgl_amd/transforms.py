@@ -863,6 +863,65 @@ def segmented_knn_graph(x, k, segs, algorithm="bruteforce-blas", dist="euclidean
     return _knn_graph_of(x, k, _segment_list(segs), algorithm, dist, exclude_self, True)
 
 
+def _sort_by_tag(g, tag, tag_offset_name, tag_type, by_src):
+    """sort_csr_by_tag (``by_src``) / sort_csc_by_tag: the relation's CSR or CSC stably sorted by tag, in a new graph."""
+    from . import _capi
+
+    who = "sort_csr_by_tag" if by_src else "sort_csc_by_tag"
+    if len(g.canonical_etypes) > 1:
+        raise DGLAMDError("Only support homograph and bipartite graph")
+    if tag_type not in ("node", "edge"):
+        raise DGLAMDError("tag_type should be either 'node' or 'edge'.")
+    rel = g._graph.relations[0]
+    dev, idt = rel.device, rel.idtype
+    row, col, eids = rel.coo()
+    if eids is not None:                       # the COO in edge-id order, so that it needs no map
+        order = torch.argsort(eids)
+        row, col = row[order], col[order]
+    tag = torch.as_tensor(tag).to(dev)
+    if tag.dtype not in (torch.int32, torch.int64):
+        raise DGLAMDError("%s: unsupported tag dtype %s (int32 and int64 are accepted)" % (who, tag.dtype))
+    if tag_type == "node":                     # the tag of the neighbour that the row lists
+        tag = tag[(col if by_src else row).long()]
+    if tag.dim() != 1 or tag.shape[0] != rel.num_edges:
+        raise DGLAMDError("%s: %d tags for %d edges" % (who, tag.shape[0] if tag.dim() else 0, rel.num_edges))
+    tag = tag.contiguous()
+    num_tags = int(tag.max()) + 1 if tag.numel() else 1
+    fmt = rel.csr() if by_src else rel.csc()
+    cols = rel.num_dst if by_src else rel.num_src
+    if dev.type == "cuda":
+        csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
+        indices, data, tag_pos = _capi.sort_csr_by_tag(csr, tag, num_tags)
+    else:
+        csr = _capi.host_csr(fmt[0].contiguous(), fmt[1].contiguous(), None if fmt[2] is None else fmt[2].contiguous(), cols)
+        indices, data, tag_pos = _capi.sort_csr_by_tag_host(csr, tag, num_tags)
+    sorted_fmt = (fmt[0], indices, data)
+    new_rel = Relation(rel.num_src, rel.num_dst, row, col, csr=sorted_fmt if by_src else None,
+                       csc=None if by_src else sorted_fmt, idtype=idt, device=dev, formats=rel.formats)
+    gi = g._graph
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), [new_rel]),
+                   g._ntypes, g.canonical_etypes, [DGLGraph._copy_frame(f) for f in g._node_frames],
+                   [DGLGraph._copy_frame(f) for f in g._edge_frames], g._src_ntype_ids, g._dst_ntype_ids)
+    s, d = gi.metagraph.find_edge(0)
+    out._node_frames[s if by_src else d][tag_offset_name] = tag_pos
+    return out
+
+
+def sort_csr_by_tag(g, tag, tag_offset_name="_TAG_OFFSET", tag_type="node"):
+    """``dgl.sort_csr_by_tag`` (python/dgl/transforms/functional.py): a new graph whose CSR lists every node's out-edges
+    by the tag of the out-neighbour (``tag_type="node"``, one tag per destination node) or of the edge (``"edge"``),
+    edges of one tag in their former order.  Edge ids and features are unchanged and shared; ``srcdata[tag_offset_name]``
+    holds the ``(N, max_tag + 2)`` offsets of the tag ranges.  One edge type only.  A GPU graph runs the kernel of
+    csrc/biased.hip, a CPU graph the same rule compiled for the host (the reference has the CPU form only)."""
+    return _sort_by_tag(g, tag, tag_offset_name, tag_type, True)
+
+
+def sort_csc_by_tag(g, tag, tag_offset_name="_TAG_OFFSET", tag_type="node"):
+    """``dgl.sort_csc_by_tag``: :func:`sort_csr_by_tag` on the in-edge CSR; node tags are those of the source nodes and
+    the offsets go to ``dstdata[tag_offset_name]``."""
+    return _sort_by_tag(g, tag, tag_offset_name, tag_type, False)
+
+
 __all__ = ["adj_product_graph", "adj_sum_graph", "add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
            "node_subgraph", "edge_subgraph", "in_subgraph", "out_subgraph", "khop_in_subgraph", "khop_out_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
-           "adj_external", "knn", "knn_graph", "segmented_knn_graph", "DGLWarning"]
+           "adj_external", "knn", "knn_graph", "segmented_knn_graph", "sort_csr_by_tag", "sort_csc_by_tag", "DGLWarning"]

@@ -1243,6 +1243,63 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
 int dgla_select_topk_host(const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds, int64_t num_seeds,
                           int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids);
 
+/* ---- Tag-biased neighbour sampling (csrc/biased.hip) ------------------------------------------------------
+ * dgl.sort_csr_by_tag / sort_csc_by_tag and dgl.sampling.sample_neighbors_biased.  The reference has CPU forms only
+ * (CSRSortByTag, src/array/cpu/csr_sort.cc; CSRRowWiseSamplingBiased, src/array/cpu/rowwise_sampling.cc).  The rules (ONE
+ * definition for device and host, csrc/biased_step.h):
+ *
+ * Tag sort.  Input: one CSR (indptr, indices, data = the edge-id map or NULL; int32 or int64 ids), tag[nnz] indexed by
+ * EDGE ID (int32 or int64, tag_bits) and T = num_tags >= 1.  Output: out_indices[nnz], out_data[nnz] (always
+ * materialised: the edge id, or the old position when data was NULL) and tag_pos[num_rows, T + 1] in the id type, row-
+ * relative offsets: the entries of row r with tag t lie at [indptr[r] + tag_pos[r][t], indptr[r] + tag_pos[r][t + 1]).
+ * indptr is unchanged and shared.  Within a row the order is by tag and, among equal tags, by the original position: a
+ * stable counting sort, so the result is a function of the inputs and equals the reference's element for element.  A
+ * tag outside [0, T) ("a tag lies outside [0, T)") and an edge id outside [0, nnz) are refused; the device form reads
+ * one set of flag words back.  Row bounds are clamped into [0, nnz].
+ *
+ * Biased picks.  Input: a CSR already sorted by tag, tag_offset[num_rows, T + 1] indexed by NODE ID (not by seed slot),
+ * bias[T] (fp32 or fp64), the seeds, fanout, replace and an rng seed.  For seed row u with deg entries:
+ *  - range of tag t: start = clamp(tag_offset[u][t], 0, deg), end = max(start, clamp(tag_offset[u][t + 1], 0, deg)),
+ *    n_t = end - start, so malformed offsets address nothing outside the row;
+ *  - b_t = bias[t] as a double when it is positive and finite, else 0 (NaN, negative and infinite count as 0);
+ *  - P = sum of n_t over the tags with b_t > 0; picks = P (fanout == -1), fanout if P > 0 else 0 (replace),
+ *    min(fanout, P) otherwise;
+ *  - fanout == -1: every entry of the positive-bias ranges, by ascending tag and position, no draw;
+ *  - generator: the counter-based one of "Random walks", keyed by (rng seed, ROW ID, pick, slot): slot 0 draws the tag,
+ *    slot 1 the position.  Picks do not depend on the launch geometry and a seed listed twice draws the same picks;
+ *  - tag of a pick: weights w_t = (n_t - taken_t) * b_t in double (taken_t = 0 with replacement), summed in chunks of W
+ *    tags (W = 16 for T <= 16, else 64) by the Hillis-Steele network within a chunk and a carry between chunks, in a
+ *    fixed order of additions; target = u * total; the first tag with w_t > 0 and prefix > target, else (rounding) the
+ *    last tag with w_t > 0;
+ *  - position with replacement: start + index(r, n_t); without: Floyd's subset step per tag, bounded, no rejection
+ *    loop: with k_t picks of the row drawing the tag and j of them earlier, m = n_t - k_t + j, c = index(r, m + 1), the
+ *    position is start + m when an earlier pick of the tag took c, else start + c.  The law is that of successive
+ *    sampling (the reference's BiasedChoice).
+ * Output is a CSR over the seeds, as for select_topk.  No multiply feeds an add with contraction allowed: device == host
+ * bit for bit.
+ *
+ * dgla_sort_csr_by_tag: device memory.  A unit owns a row: 16 lanes (csr->nnz / csr->num_rows <= 32), a wavefront, or a
+ *   256-lane workgroup for rows of 2048 entries and more.  T + 1 <= 256 counters per unit live in LDS, more in the row's
+ *   own tag_pos slice.  No workspace.
+ * dgla_sample_neighbors_biased_workspace_bytes: one 64-bit word per seed, the scan's temporary and the flag words.
+ * dgla_sample_neighbors_biased: device memory.  num_tags <= 1024.  out_nbr == NULL: the sizes only.  fanout >= 0 reads
+ *   nothing back (allocate num_seeds * fanout entries; the call can be captured when a workspace is given) and a seed
+ *   outside [0, num_rows) is an empty row; fanout == -1 reads the flag words back and refuses such a seed.  A workspace
+ *   that is given but too small is refused with the bytes required.
+ * The *_host forms run the same rules on HOST pointers and check tags and seeds before they write anything. */
+int dgla_sort_csr_by_tag(const dgla_csr* csr, const void* tag, int tag_bits, int64_t num_tags, void* out_indices, void* out_data,
+                         void* tag_pos, void* hip_stream);
+int dgla_sort_csr_by_tag_host(const dgla_csr* csr, const void* tag, int tag_bits, int64_t num_tags, void* out_indices,
+                              void* out_data, void* tag_pos);
+size_t dgla_sample_neighbors_biased_workspace_bytes(int idtype_bits, int64_t num_seeds);
+int dgla_sample_neighbors_biased(const dgla_csr* csr, const void* tag_offset, int64_t num_tags, const void* bias, int bias_dtype,
+                                 const void* seeds, int64_t num_seeds, int64_t fanout, int replace, uint64_t rng_seed,
+                                 void* out_indptr, void* out_nbr, void* out_eids, void* workspace, size_t workspace_bytes,
+                                 void* hip_stream);
+int dgla_sample_neighbors_biased_host(const dgla_csr* csr, const void* tag_offset, int64_t num_tags, const void* bias,
+                                      int bias_dtype, const void* seeds, int64_t num_seeds, int64_t fanout, int replace,
+                                      uint64_t rng_seed, void* out_indptr, void* out_nbr, void* out_eids);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
