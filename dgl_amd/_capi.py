@@ -1479,6 +1479,126 @@ def sample_neighbors_biased_host(csr, tag_offset, bias, seeds, fanout, replace=F
     return indptr, nbr, eids
 
 
+_ETYPE_PROB = {torch.float32: 0, torch.float64: 1, torch.uint8: _lib.DGLA_ETYPE_U8, torch.bool: _lib.DGLA_ETYPE_U8}
+
+
+class EtypeProbs:
+    """What :meth:`EtypeTable.probs` prepares: the table of T pointers, the dtype code and the tensors kept alive."""
+
+    def __init__(self, pointers, dtype_code, keep):
+        self.pointers, self.dtype_code, self.keep = pointers, dtype_code, keep
+
+
+class EtypeTable:
+    """The edge-type table of :func:`sample_etype_neighbors`, checked ON THE HOST once and then uploaded: `etype_offset`
+    (a list or CPU tensor of T + 1 edge ids, non-decreasing from 0) and, through :meth:`probs`, the per-type weights.
+    `device=None` keeps everything on the host, for :func:`sample_etype_neighbors_host`.  Build it outside a captured
+    region; the calls that take it copy nothing from the host."""
+
+    def __init__(self, etype_offset, device=None, who="sample_etype_neighbors"):
+        off = torch.as_tensor(etype_offset).detach().cpu().to(torch.int64).reshape(-1)
+        if off.numel() < 2 or int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()):
+            raise _lib.DGLAMDError("%s: etype_offset must be non-decreasing and start at 0" % who)
+        self.who, self.host, self.num_etypes = who, off.contiguous(), off.numel() - 1
+        if self.num_etypes > 1024:
+            raise _lib.DGLAMDError("%s: num_etypes %d exceeds the limit of 1024 edge types" % (who, self.num_etypes))
+        self.device = torch.device("cpu") if device is None else torch.device(device)
+        self.offsets = self.host.to(self.device)
+
+    def fanouts(self, fanout):
+        """`fanout` as the int64 tensor of the call, one value per edge type (-1 = all)."""
+        f = torch.as_tensor(fanout)
+        if f.dim() != 1 or f.numel() != self.num_etypes or f.dtype.is_floating_point:
+            raise _lib.DGLAMDError("%s: fanout must hold one integer per edge type (%d), got %s of shape %s"
+                                   % (self.who, self.num_etypes, f.dtype, tuple(f.shape)))
+        return f.to(device=self.device, dtype=torch.int64).contiguous()
+
+    def probs(self, prob):
+        """The :class:`EtypeProbs` of a per-type weight list (tensors or None, one dtype), or None when all are None."""
+        if prob is None:
+            return None
+        who, T = self.who, self.num_etypes
+        if not isinstance(prob, (list, tuple)) or len(prob) != T:
+            raise _lib.DGLAMDError("%s: prob must list one tensor or None per edge type (%d)" % (who, T))
+        given = [p for p in prob if p is not None]
+        if not given:
+            return None
+        dt = given[0].dtype
+        if dt not in _ETYPE_PROB:
+            raise _lib.DGLAMDError("%s: unsupported prob dtype %s (fp32, fp64 and uint8 / bool are accepted)" % (who, dt))
+        keep, ptrs = [], []
+        for t, p in enumerate(prob):
+            if p is None:
+                ptrs.append(0)
+                continue
+            need = int(self.host[t + 1] - self.host[t])
+            if p.dtype != dt or p.dim() != 1 or p.numel() != need or p.device != self.device:
+                raise _lib.DGLAMDError("%s: prob[%d] must be a 1-D %s tensor with one value per edge of the type (%d) on the "
+                                       "table's device" % (who, t, dt, need))
+            p = p.contiguous()
+            keep.append(p)
+            ptrs.append(p.data_ptr() if need else 0)
+        return EtypeProbs(torch.tensor(ptrs, dtype=torch.int64).to(self.device), _ETYPE_PROB[dt], keep)
+
+
+def sample_etype_neighbors_workspace_bytes(idtype, num_seeds):
+    """The bytes of the optional workspace of :func:`sample_etype_neighbors` (host query)."""
+    return int(LIB.dgla_sample_etype_neighbors_workspace_bytes(_id_bits(idtype), int(num_seeds)))
+
+
+def _etype_args(who, csr, table, fanout, prob, seeds, replace, rng_seed, gpu):
+    """The checks the two per-edge-type entry points share, and their leading arguments."""
+    indptr = csr._keep[0]
+    if prob is not None and not isinstance(prob, EtypeProbs):
+        prob = table.probs(prob)
+    _all_on(gpu, who, indptr, table.offsets, fanout, seeds, None if prob is None else prob.pointers)
+    if fanout.dtype != torch.int64 or fanout.dim() != 1 or fanout.numel() != table.num_etypes or not fanout.is_contiguous():
+        raise _lib.DGLAMDError("%s: fanout must hold one integer per edge type (%d), got %s of shape %s"
+                               % (who, table.num_etypes, fanout.dtype, tuple(fanout.shape)))
+    _id_tensor_ok(who, "seeds", seeds, indptr)
+    args = [ctypes.byref(csr), _ptr(table.offsets), _ptr(fanout), table.num_etypes, None if prob is None else _ptr(prob.pointers),
+            0 if prob is None else prob.dtype_code, _ptr(seeds), seeds.shape[0], 1 if replace else 0, _u64(rng_seed)]
+    return args, prob
+
+
+def sample_etype_neighbors(csr, table, fanout, seeds, replace=False, rng_seed=0, prob=None, ws=None, into=None, capacity=None):
+    """For every seed row of `csr`, whose rows are ordered by edge type, ``fanout[t]`` entries of every type `t`
+    (dgla_sample_etype_neighbors; the rule: include/dgl_amd.h "Per-edge-type neighbour sampling").  `table` is an
+    :class:`EtypeTable` on the csr's device, `fanout` an int64 device tensor (``table.fanouts``), `prob` a per-type list
+    or what ``table.probs`` returned.  Returns ``(indptr, nbr, eids)``, a CSR over the seeds whose first ``indptr[-1]``
+    entries are the result.  With `capacity` (``num_seeds * sum(fanout)`` when every fan-out is >= 0) or `into` nothing
+    is read back; otherwise the sizes come first.  `ws` (uint8, :func:`sample_etype_neighbors_workspace_bytes`) is the
+    optional workspace of the call."""
+    args, prob = _etype_args("sample_etype_neighbors", csr, table, fanout, prob, seeds, replace, rng_seed, True)
+    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
+    wp, wb = _ws(ws)
+    st = _stream(seeds)
+    if into is not None:
+        indptr, nbr, eids = into
+    else:
+        indptr = torch.empty(n + 1, dtype=dt, device=dev)
+        if capacity is None:
+            check_call(LIB.dgla_sample_etype_neighbors(*args, indptr.data_ptr(), None, None, 0, wp, wb, st))
+            capacity = int(indptr[-1])
+        nbr = torch.empty(int(capacity), dtype=dt, device=dev)
+        eids = torch.empty(int(capacity), dtype=dt, device=dev)
+    check_call(LIB.dgla_sample_etype_neighbors(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), nbr.numel(), wp, wb, st))
+    return indptr, nbr, eids
+
+
+def sample_etype_neighbors_host(csr, table, fanout, seeds, replace=False, rng_seed=0, prob=None):
+    """:func:`sample_etype_neighbors` run by the CPU on CPU tensors (dgla_sample_etype_neighbors_host): the same rule
+    compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs no GPU."""
+    args, prob = _etype_args("sample_etype_neighbors_host", csr, table, fanout, prob, seeds, replace, rng_seed, False)
+    n, dt = seeds.shape[0], seeds.dtype
+    indptr = torch.empty(n + 1, dtype=dt)
+    check_call(LIB.dgla_sample_etype_neighbors_host(*args, indptr.data_ptr(), None, None, 0))
+    total = int(indptr[-1])
+    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
+    check_call(LIB.dgla_sample_etype_neighbors_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), total))
+    return indptr, nbr, eids
+
+
 def pinsage_max_samples(idtype=torch.int64):
     """The largest ``num_samples_per_node`` the selection kernel accepts for ids of `idtype` (host query)."""
     return int(LIB.dgla_pinsage_max_samples(_id_bits(idtype)))

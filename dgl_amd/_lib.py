@@ -380,6 +380,16 @@ LIB.dgla_sample_neighbors_biased.restype = c_int
 LIB.dgla_sample_neighbors_biased.argtypes = _BIASED + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_sample_neighbors_biased_host.restype = c_int
 LIB.dgla_sample_neighbors_biased_host.argtypes = _BIASED
+# the per-edge-type sampler: csr, etype_offset, fanout, num_etypes, prob pointers, prob dtype, seeds, num_seeds, replace,
+# rng seed, out_indptr, out_nbr, out_eids, out_capacity
+_ETYPE = [P(CSR), c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, ctypes.c_uint64, c_void_p, c_void_p,
+          c_void_p, c_int64]
+LIB.dgla_sample_etype_neighbors_workspace_bytes.restype = c_size_t
+LIB.dgla_sample_etype_neighbors_workspace_bytes.argtypes = [c_int, c_int64]
+LIB.dgla_sample_etype_neighbors.restype = c_int
+LIB.dgla_sample_etype_neighbors.argtypes = _ETYPE + [c_void_p, c_size_t, c_void_p]
+LIB.dgla_sample_etype_neighbors_host.restype = c_int
+LIB.dgla_sample_etype_neighbors_host.argtypes = _ETYPE
 LIB.dgla_pinsage_max_samples.restype = c_int64
 LIB.dgla_pinsage_max_samples.argtypes = [c_int]
 LIB.dgla_pinsage_size_classes.restype = c_int
@@ -439,3 +449,4 @@ DEFAULT_TUNING = DGLA_TUNE_XCD | DGLA_TUNE_SPLIT | DGLA_TUNE_GLDS  # csrc/common
 def check_call(ret):
     if ret != 0:
         raise DGLAMDError(LIB.dgla_last_error().decode("utf-8", "replace"))
+DGLA_ETYPE_U8 = 4   # the prob dtype code of a bool / uint8 mask (dgla_sample_etype_neighbors)

@@ -863,6 +863,111 @@ def sample_neighbors_biased(g, nodes, fanout, bias, edge_dir="in", tag_offset_na
 DGLGraph.sample_neighbors_biased = sample_neighbors_biased
 
 
+def _etype_sorted_rows(rel, fmt, cols, table, edge_dir):
+    """``(indices, data)`` of ``fmt`` with every row ordered by edge type: the per-edge type is computed once, the rows go
+    through the stable tag sort, and the result stays in ONE slot on the relation, keyed by direction and offsets.  The
+    ``(N, T + 1)`` offset table of the sort is dropped: the sampler finds its ranges by bisection."""
+    key = (edge_dir, tuple(table.host.tolist()))
+    slot = getattr(rel, "_etype_sorted", None)
+    if slot is None or slot[0] != key:
+        dev = fmt[0].device
+        tag = torch.bucketize(torch.arange(rel.num_edges, device=dev), table.host[1:].to(dev), right=True)
+        num_tags = table.num_etypes + (1 if int(table.host[-1]) < rel.num_edges else 0)   # (ids past the last type sort last)
+        if dev.type == "cuda":
+            indices, data, _ = _capi.sort_csr_by_tag(_capi.make_csr(fmt[0], fmt[1], fmt[2], cols), tag, num_tags)
+        else:
+            indices, data, _ = _capi.sort_csr_by_tag_host(_capi.host_csr(*fmt, cols), tag, num_tags)
+        slot = (key, (indices, data))
+        rel._etype_sorted = slot
+    return slot[1]
+
+
+def sample_etype_neighbors(g, nodes, etype_offset, fanout, edge_dir="in", prob=None, exclude_edges=None, replace=False,
+                           copy_ndata=True, copy_edata=True, etype_sorted=False, _dist_training=False, output_device=None,
+                           seed=None):
+    """``dgl.sampling.sample_etype_neighbors`` (python/dgl/sampling/neighbor.py:69): on a homogenised graph, whose edge
+    ``e`` has type ``t`` iff ``etype_offset[t] <= e < etype_offset[t + 1]``, ``fanout[t]`` inbound (``edge_dir="out"``:
+    outbound) edges of every type ``t`` for every node in ``nodes``; ``-1`` takes all edges of the type.
+
+    ``fanout`` is a tensor with one value per type.  ``prob`` lists, per type, an edge-feature name, a tensor or ``None``
+    (uniform): fp32 / fp64 weights or a bool / uint8 mask, one dtype per call, either one value per edge of the graph or
+    one per edge of the type.  ``etype_sorted=True`` promises that every row of the CSC (``"out"``: CSR) lists its edges
+    by type and, like the reference's fast path, is not tested; otherwise the rows are sorted once with the tag sort and
+    kept on the relation.  ``seed`` fixes the draws; a node listed twice draws the same edges twice.
+
+    Returns a graph with all nodes of ``g`` and only the sampled edges, as :func:`sample_neighbors_biased` assembles it.
+    A GPU graph runs the kernels of csrc/etype.hip; a CPU graph runs the same rule compiled for the host.  The rule is
+    written in include/dgl_amd.h, "Per-edge-type neighbour sampling"."""
+    who = "sample_etype_neighbors"
+    if exclude_edges is not None:
+        raise _DGLError("exclude_edges is not supported for sample_etype_neighbors")
+    if edge_dir not in ("in", "out"):
+        raise _DGLError("edge_dir can only be 'in' or 'out'")
+    if len(g.canonical_etypes) != 1 or len(g._ntypes) != 1:
+        raise _DGLError("%s: the input graph should have one node type and one edge type (a homogenised graph)" % who)
+    if not torch.is_tensor(fanout):
+        raise _DGLError("The fanout should be a tensor")
+    if isinstance(nodes, dict):
+        if len(nodes) != 1:
+            raise _DGLError("%s: the input graph should not have node types" % who)
+        nodes = list(nodes.values())[0]
+    rel = g._graph.relations[0]
+    dev, idt = rel.device, rel.idtype
+    gpu = dev.type == "cuda"
+    table = _capi.EtypeTable(etype_offset, dev if gpu else None, who)
+    fan = table.fanouts(fanout.detach().cpu())
+    if prob is not None:
+        if not isinstance(prob, (list, tuple)) or len(prob) != table.num_etypes:
+            raise _DGLError("%s: prob must list one tensor or None per edge type (%d)" % (who, table.num_etypes))
+        views = []
+        for t, p in enumerate(prob):
+            if isinstance(p, str):
+                p = g._edge_frames[0][p]
+            if p is not None and p.dim() == 1 and p.numel() == rel.num_edges:
+                p = p[int(table.host[t]):int(table.host[t + 1])]
+            views.append(None if p is None else p.to(dev))
+        prob = table.probs(views)
+    seeds = _node_ids(nodes, dev, idt)
+    rng_seed = _call_seed(seed)
+    fmt = rel.csc() if edge_dir == "in" else rel.csr()
+    fmt = tuple(None if t is None else t.contiguous() for t in fmt)
+    cols = rel.num_src if edge_dir == "in" else rel.num_dst
+    if seeds.numel() == 0 or rel.num_edges == 0:
+        own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
+    else:
+        if not etype_sorted:
+            fmt = (fmt[0],) + _etype_sorted_rows(rel, fmt, cols, table, edge_dir)
+        if gpu:
+            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
+            f = fan.cpu()
+            cap = None if bool((f < 0).any()) else int(f.sum()) * seeds.numel()
+            indptr, nbr, eids = _capi.sample_etype_neighbors(csr, table, fan, seeds, replace, rng_seed, prob=prob, capacity=cap)
+        else:
+            indptr, nbr, eids = _capi.sample_etype_neighbors_host(_capi.host_csr(*fmt, cols), table, fan, seeds, replace, rng_seed,
+                                                                  prob=prob)
+        n_e = int(indptr[-1])
+        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
+        nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
+    src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
+    gi = g._graph
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges),
+                              [Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev)]),
+                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
+    if copy_ndata and not _dist_training:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
+        for i, fr in enumerate(g._node_frames):
+            for key, val in fr.items():
+                out._node_frames[i][key] = val
+    if copy_edata and not _dist_training:
+        for key, val in g._edge_frames[0].items():
+            if key != EID:
+                out._edge_frames[0][key] = val[eids.long()]
+    out._edge_frames[0][EID] = eids
+    return out if output_device is None else out.to(output_device)
+
+
+DGLGraph.sample_etype_neighbors = sample_etype_neighbors
+
+
 class LaborSampler:
     """``dgl.dataloading.LaborSampler`` (python/dgl/dataloading/labor_sampler.py): one block per layer, built from the
     output nodes inwards; a layer is :func:`sample_labors` followed by :func:`to_block` on the seeds.

@@ -1300,6 +1300,57 @@ int dgla_sample_neighbors_biased_host(const dgla_csr* csr, const void* tag_offse
                                       int bias_dtype, const void* seeds, int64_t num_seeds, int64_t fanout, int replace,
                                       uint64_t rng_seed, void* out_indptr, void* out_nbr, void* out_eids);
 
+/* ---- Per-edge-type neighbour sampling (csrc/etype.hip) ----------------------------------------------------
+ * dgl.sampling.sample_etype_neighbors on a homogenised graph: one node space, one edge list, the edge type carried by
+ * the edge id.  The reference has the CPU form only (CSRRowWisePerEtypePick, src/array/cpu/rowwise_pick.h:334).  The rule
+ * (ONE definition for device and host, csrc/etype_step.h):
+ *
+ * Input: one CSR (indptr, indices, data = the edge-id map or NULL; int32 or int64 ids), etype_offset[T + 1] (int64, non-
+ * decreasing from 0: edge id e has type t iff etype_offset[t] <= e < etype_offset[t + 1]), fanout[T] (int64, negative =
+ * all), optionally prob[T] (an array of T pointers, NULL entries allowed; prob[t] is indexed by e - etype_offset[t];
+ * prob_dtype = DGLA_F32, DGLA_F64 or DGLA_ETYPE_U8 for a bool / uint8 mask, one type per call), replace, the seeds and an
+ * rng seed.  Every row is taken to be ordered by edge type.  For seed row u with deg entries:
+ *  - range of type t: lower(b) = the first row-relative position whose edge id is >= b, by bisection over the row;
+ *    start_t = lower(etype_offset[t]), end_t = max(start_t, lower(etype_offset[t + 1])), n_t = end_t - start_t.  On a row
+ *    that is not ordered the picks are unspecified, but nothing outside the row is addressed and no range is negative;
+ *  - weight of an entry when prob[t] is given: prob[t][e - etype_offset[t]] as a double when positive and finite, else
+ *    0 (an entry of the range whose edge id is not of type t weighs 0 and reads nothing); P_t = the number of entries
+ *    with a positive weight, n_t without prob[t];
+ *  - picks of (u, t) with f = fanout[t]: P_t (f < 0), f if P_t > 0 else 0 (replace), min(f, P_t) otherwise;
+ *  - generator: the counter-based one of "Random walks", keyed by (rng seed, ROW ID, type, draw index or range-relative
+ *    position).  The picks do not depend on the launch geometry, on the seed's place in the list or on the fan-outs of
+ *    other types, and a seed listed twice draws the same picks;
+ *  - unweighted: the whole range in position order when picks == n_t without replacement; with replacement pick k is
+ *    start_t + index(r(k), n_t); else Floyd's subset: for m = 0 .. f - 1, j = n_t - f + m, c = index(r(m), j + 1), the
+ *    pick is j when an earlier pick of the range took c, else c;
+ *  - weighted: every positive entry in position order when picks == P_t without replacement; otherwise, without
+ *    replacement, the picks smallest (key, position) in that order with key = -ln(u) / weight, u in (0, 1] drawn per
+ *    position and -ln evaluated by the fixed series of etype_neglog; with replacement the weights are summed in chunks
+ *    of W positions (W = 16 for T <= 16, else 64) by the Hillis-Steele network and a carry, target = u * total, and the
+ *    pick is the first positive position whose prefix exceeds the target, else (rounding) the last positive one.
+ * Output is a CSR over the seeds; the picks of a seed follow each other by ascending type, then pick order.  Slots at or
+ * beyond out_capacity are neither written nor read.  Contraction is off wherever a weight is formed or added: device ==
+ * host bit for bit.
+ *
+ * dgla_sample_etype_neighbors_workspace_bytes: one 64-bit word per seed and the scan's temporary.
+ * dgla_sample_etype_neighbors: device memory throughout (etype_offset, fanout and the pointer array prob included).
+ *   num_etypes <= 1024.  out_nbr == NULL: the sizes only.  A lane group owns a seed and a lane an edge type; a count
+ *   pass, the device scan and a pick pass.  Nothing is read back, and with a workspace nothing is allocated, so a call
+ *   whose capacity the caller knows (num_seeds * sum(fanout) when every fan-out is >= 0) can be captured.  A seed outside
+ *   [0, num_rows) is an empty row.  The device form cannot read etype_offset, so its order is the caller's to check.
+ * dgla_sample_etype_neighbors_host: the same rule on HOST pointers; refuses an etype_offset that is not non-decreasing
+ *   from 0. */
+#define DGLA_ETYPE_U8 4
+size_t dgla_sample_etype_neighbors_workspace_bytes(int idtype_bits, int64_t num_seeds);
+int dgla_sample_etype_neighbors(const dgla_csr* csr, const int64_t* etype_offset, const int64_t* fanout, int64_t num_etypes,
+                                const void* const* prob, int prob_dtype, const void* seeds, int64_t num_seeds, int replace,
+                                uint64_t rng_seed, void* out_indptr, void* out_nbr, void* out_eids, int64_t out_capacity,
+                                void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_sample_etype_neighbors_host(const dgla_csr* csr, const int64_t* etype_offset, const int64_t* fanout,
+                                     int64_t num_etypes, const void* const* prob, int prob_dtype, const void* seeds,
+                                     int64_t num_seeds, int replace, uint64_t rng_seed, void* out_indptr, void* out_nbr,
+                                     void* out_eids, int64_t out_capacity);
+
 /* ---- PinSAGE neighbour selection: visit-count top-k over walk traces (csrc/pinsage.hip) -----------
  * Replace SelectPinSageNeighbors<kDGLCUDA> (src/graph/sampling/randomwalks/randomwalk_gpu.cu:443 over
  * frequency_hashmap.cu, behind python/dgl/sampling/pinsage.py).  The reference's GPU form fills a global hash table with
