@@ -1317,6 +1317,26 @@ def traverse_host(mode, csr, opposite=None, sources=None):
     return ids[:num_ids.value], list(sections[:num_sections.value])
 
 
+def _seed_csr(call, args, seeds, capacity=None, tail=(), into=None, pass_capacity=False):
+    """``(indptr, nbr, eids)``, a CSR over `seeds`, from an entry point of the form ``call(*args, out_indptr, out_nbr,
+    out_eids, *tail)``.  With a `capacity` the outputs are allocated at it and the entry is called once; ``None`` asks
+    first, with null outputs, and allocates at ``indptr[-1]``, the result's length.  `into` is the three outputs sized
+    by the caller: nothing is allocated or asked.  `pass_capacity`: the entry takes the length of `nbr` after
+    ``out_eids`` (0 with the null outputs)."""
+    if into is None:
+        n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
+        indptr = torch.empty(n + 1, dtype=dt, device=dev)
+        if capacity is None:
+            check_call(call(*args, indptr.data_ptr(), None, None, *((0,) + tail if pass_capacity else tail)))
+            capacity = int(indptr[-1])
+        into = (indptr, torch.empty(capacity, dtype=dt, device=dev), torch.empty(capacity, dtype=dt, device=dev))
+    indptr, nbr, eids = into
+    if pass_capacity:
+        tail = (nbr.numel(),) + tail
+    check_call(call(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), *tail))
+    return indptr, nbr, eids
+
+
 _TOPK_DTYPES = dict(_DTYPES)       # the weight types of dgla_select_topk: dgla_dtype, DGLA_TOPK_I32, DGLA_TOPK_I64
 _TOPK_DTYPES.update({torch.int32: 4, torch.int64: 5})
 
@@ -1353,19 +1373,8 @@ def select_topk(csr, weight, seeds, k, ascending=False, workspace=None):
     ``k > 1024`` the sizes come first and the outputs have the result's length.  `workspace` (uint8,
     :func:`select_topk_workspace_bytes`) is optional."""
     args = _topk_args("select_topk", csr, weight, seeds, k, ascending, True)
-    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
-    indptr = torch.empty(n + 1, dtype=dt, device=dev)
-    wp, wb = _ws(workspace)
-    st = _stream(seeds)
-    if 0 <= k <= select_topk_max_picks():
-        cap = n * int(k)
-    else:
-        check_call(LIB.dgla_select_topk(*args, indptr.data_ptr(), None, None, wp, wb, st))
-        cap = int(indptr[-1])
-    nbr = torch.empty(cap, dtype=dt, device=dev)
-    eids = torch.empty(cap, dtype=dt, device=dev)
-    check_call(LIB.dgla_select_topk(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), wp, wb, st))
-    return indptr, nbr, eids
+    cap = seeds.shape[0] * int(k) if 0 <= k <= select_topk_max_picks() else None
+    return _seed_csr(LIB.dgla_select_topk, args, seeds, cap, (*_ws(workspace), _stream(seeds)))
 
 
 def select_topk_host(csr, weight, seeds, k, ascending=False):
@@ -1373,13 +1382,7 @@ def select_topk_host(csr, weight, seeds, k, ascending=False):
     same rule compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs
     no GPU."""
     args = _topk_args("select_topk_host", csr, weight, seeds, k, ascending, False)
-    n, dt = seeds.shape[0], seeds.dtype
-    indptr = torch.empty(n + 1, dtype=dt)
-    check_call(LIB.dgla_select_topk_host(*args, indptr.data_ptr(), None, None))
-    total = int(indptr[-1])
-    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
-    check_call(LIB.dgla_select_topk_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr()))
-    return indptr, nbr, eids
+    return _seed_csr(LIB.dgla_select_topk_host, args, seeds)
 
 
 def _tag_sort(who, csr, tag, num_tags, gpu, into):
@@ -1448,35 +1451,15 @@ def sample_neighbors_biased(csr, tag_offset, bias, seeds, fanout, replace=False,
     come first.  `ws` (uint8, :func:`sample_neighbors_biased_workspace_bytes`) is the optional workspace of the call;
     `into` places the three outputs in tensors the caller has sized."""
     args = _biased_args("sample_neighbors_biased", csr, tag_offset, bias, seeds, fanout, replace, rng_seed, True)
-    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
-    wp, wb = _ws(ws)
-    st = _stream(seeds)
-    if into is not None:
-        indptr, nbr, eids = into
-    else:
-        indptr = torch.empty(n + 1, dtype=dt, device=dev)
-        if fanout >= 0:
-            cap = n * int(fanout)
-        else:
-            check_call(LIB.dgla_sample_neighbors_biased(*args, indptr.data_ptr(), None, None, wp, wb, st))
-            cap = int(indptr[-1])
-        nbr = torch.empty(cap, dtype=dt, device=dev)
-        eids = torch.empty(cap, dtype=dt, device=dev)
-    check_call(LIB.dgla_sample_neighbors_biased(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), wp, wb, st))
-    return indptr, nbr, eids
+    cap = seeds.shape[0] * int(fanout) if fanout >= 0 else None
+    return _seed_csr(LIB.dgla_sample_neighbors_biased, args, seeds, cap, (*_ws(ws), _stream(seeds)), into)
 
 
 def sample_neighbors_biased_host(csr, tag_offset, bias, seeds, fanout, replace=False, rng_seed=0):
     """:func:`sample_neighbors_biased` run by the CPU on CPU tensors (dgla_sample_neighbors_biased_host): the same rule
     compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs no GPU."""
     args = _biased_args("sample_neighbors_biased_host", csr, tag_offset, bias, seeds, fanout, replace, rng_seed, False)
-    n, dt = seeds.shape[0], seeds.dtype
-    indptr = torch.empty(n + 1, dtype=dt)
-    check_call(LIB.dgla_sample_neighbors_biased_host(*args, indptr.data_ptr(), None, None))
-    total = int(indptr[-1])
-    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
-    check_call(LIB.dgla_sample_neighbors_biased_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr()))
-    return indptr, nbr, eids
+    return _seed_csr(LIB.dgla_sample_neighbors_biased_host, args, seeds)
 
 
 _ETYPE_PROB = {torch.float32: 0, torch.float64: 1, torch.uint8: _lib.DGLA_ETYPE_U8, torch.bool: _lib.DGLA_ETYPE_U8}
@@ -1570,33 +1553,15 @@ def sample_etype_neighbors(csr, table, fanout, seeds, replace=False, rng_seed=0,
     is read back; otherwise the sizes come first.  `ws` (uint8, :func:`sample_etype_neighbors_workspace_bytes`) is the
     optional workspace of the call."""
     args, prob = _etype_args("sample_etype_neighbors", csr, table, fanout, prob, seeds, replace, rng_seed, True)
-    n, dev, dt = seeds.shape[0], seeds.device, seeds.dtype
-    wp, wb = _ws(ws)
-    st = _stream(seeds)
-    if into is not None:
-        indptr, nbr, eids = into
-    else:
-        indptr = torch.empty(n + 1, dtype=dt, device=dev)
-        if capacity is None:
-            check_call(LIB.dgla_sample_etype_neighbors(*args, indptr.data_ptr(), None, None, 0, wp, wb, st))
-            capacity = int(indptr[-1])
-        nbr = torch.empty(int(capacity), dtype=dt, device=dev)
-        eids = torch.empty(int(capacity), dtype=dt, device=dev)
-    check_call(LIB.dgla_sample_etype_neighbors(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), nbr.numel(), wp, wb, st))
-    return indptr, nbr, eids
+    cap = None if capacity is None else int(capacity)
+    return _seed_csr(LIB.dgla_sample_etype_neighbors, args, seeds, cap, (*_ws(ws), _stream(seeds)), into, pass_capacity=True)
 
 
 def sample_etype_neighbors_host(csr, table, fanout, seeds, replace=False, rng_seed=0, prob=None):
     """:func:`sample_etype_neighbors` run by the CPU on CPU tensors (dgla_sample_etype_neighbors_host): the same rule
     compiled for the host, bit for bit what the kernels write.  The outputs have the result's length.  Needs no GPU."""
     args, prob = _etype_args("sample_etype_neighbors_host", csr, table, fanout, prob, seeds, replace, rng_seed, False)
-    n, dt = seeds.shape[0], seeds.dtype
-    indptr = torch.empty(n + 1, dtype=dt)
-    check_call(LIB.dgla_sample_etype_neighbors_host(*args, indptr.data_ptr(), None, None, 0))
-    total = int(indptr[-1])
-    nbr, eids = torch.empty(total, dtype=dt), torch.empty(total, dtype=dt)
-    check_call(LIB.dgla_sample_etype_neighbors_host(*args, indptr.data_ptr(), nbr.data_ptr(), eids.data_ptr(), total))
-    return indptr, nbr, eids
+    return _seed_csr(LIB.dgla_sample_etype_neighbors_host, args, seeds, pass_capacity=True)
 
 
 def pinsage_max_samples(idtype=torch.int64):

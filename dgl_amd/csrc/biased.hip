@@ -377,14 +377,14 @@ __global__ __launch_bounds__(64) void biased_pick_kernel(const Idx* __restrict__
 
 // ---- host side --------------------------------------------------------------------------------------
 struct BiasedLayout {  // offsets into the workspace of dgla_sample_neighbors_biased
-  size_t picks, scan, flags, bytes;
+  SeedScan head;
+  size_t flags, bytes;
 };
 
 BiasedLayout biased_layout(int64_t n) {
   BiasedLayout L{};
   Carver c;
-  L.picks = c.take(sizeof(int64_t) * static_cast<size_t>(n + 1));
-  L.scan = c.take(msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
+  L.head = take_seed_scan(c, n, msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
   L.flags = c.take(sizeof(int) * kFwWords);
   L.bytes = c.bytes();
   return L;
@@ -393,9 +393,6 @@ BiasedLayout biased_layout(int64_t n) {
 int biased_bad_tag(const char* who, int64_t T) { return fail(who, "a tag lies outside [0, " + std::to_string(T) + ")"); }
 int biased_bad_eid(const char* who, int64_t nnz) {
   return fail(who, "an edge id of the csr lies outside [0, " + std::to_string(nnz) + ")");
-}
-int biased_bad_seed(const char* who, int64_t num_rows) {
-  return fail(who, "a seed lies outside [0, " + std::to_string(num_rows) + ")");
 }
 
 // everything the two sort entry points refuse before they read an array
@@ -422,12 +419,9 @@ int check_biased(const char* who, const dgla_csr* csr, const void* tag_offset, i
     return fail(who, "num_tags " + std::to_string(num_tags) + " exceeds the limit of " + std::to_string(kBiasedMaxTags) + " tags");
   if (!bias) return fail(who, "bias is null");
   if (!tag_offset && csr->num_rows > 0) return fail(who, "tag_offset is null");
-  if (num_seeds < 0) return fail(who, "negative number of seeds");
-  if (num_seeds > 0 && !seeds) return fail(who, "seeds is null");
+  if (check_seeds(who, seeds, num_seeds)) return -1;
   if (fanout < -1) return fail(who, "fanout must be -1 (all), 0 or positive, got " + std::to_string(fanout));
-  if (!out_indptr) return fail(who, "out_indptr is null");
-  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
-  return 0;
+  return check_seed_outputs(who, out_indptr, out_nbr, out_eids);
 }
 
 // ---- the rules run by the CPU -----------------------------------------------------------------------
@@ -473,13 +467,14 @@ int sort_by_tag_host(const char* who, const TypedCsr<Idx>& g, const Tag* tag, in
 }
 
 template <typename Idx, typename B>
-int sample_biased_host(const char* who, const TypedCsr<Idx>& g, const Idx* tag_offset, int64_t T, const B* bias, const Idx* seeds,
-                       int64_t n, int64_t fanout, bool rep, uint64_t rng_seed, Idx* out_indptr, Idx* out_nbr, Idx* out_eids) {
+int sample_biased_host(const char* who, const TypedCsr<Idx>& g, const Idx* tag_offset, int64_t T, const B* bias,
+                       const SeedCsrOut<Idx>& o, int64_t n, int64_t fanout, bool rep, uint64_t rng_seed) {
+  const Idx* seeds = o.seeds;
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
     topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
-    if (bad) return biased_bad_seed(who, g.num_rows);
+    if (bad) return bad_seed(who, g.num_rows);
   }
   const int W = biased_width(T);
   const int64_t TP = (T + W - 1) / W * W;
@@ -493,8 +488,8 @@ int sample_biased_host(const char* who, const TypedCsr<Idx>& g, const Idx* tag_o
     const int64_t u = static_cast<int64_t>(seeds[i]), deg = hi - lo;
     const Idx* off = tag_offset + u * (T + 1);
     const int64_t picks = biased_picks(biased_positive(off, bias, T, deg), fanout, rep);
-    out_indptr[i] = static_cast<Idx>(at);
-    if (picks == 0 || !out_nbr) {
+    o.indptr[i] = static_cast<Idx>(at);
+    if (picks == 0 || !o.nbr) {
       at += picks;
       continue;
     }
@@ -504,8 +499,8 @@ int sample_biased_host(const char* who, const TypedCsr<Idx>& g, const Idx* tag_o
     }
     auto emit = [&](int64_t p, int64_t pos) {
       if (pos >= deg) pos = deg - 1;
-      out_nbr[at + p] = g.indices[lo + pos];
-      out_eids[at + p] = static_cast<Idx>(topk_eid(g.data, lo + pos));
+      o.nbr[at + p] = g.indices[lo + pos];
+      o.eids[at + p] = static_cast<Idx>(topk_eid(g.data, lo + pos));
     };
     if (fanout < 0) {
       int64_t p = 0;
@@ -565,7 +560,7 @@ int sample_biased_host(const char* who, const TypedCsr<Idx>& g, const Idx* tag_o
     }
     at += picks;
   }
-  out_indptr[n] = static_cast<Idx>(at);
+  o.indptr[n] = static_cast<Idx>(at);
   return 0;
 }
 
@@ -579,13 +574,6 @@ void launch_sort(const TypedCsr<Idx>& g, const Tag* tag, int64_t T, Idx* out_ind
   else
     hipLaunchKernelGGL((tag_sort_kernel<Idx, Tag, NT, G, false>), grid, block, 0, s, g.indptr, g.indices, g.data, tag, g.num_rows,
                        g.nnz, T, out_indices, out_data, tag_pos, flags);
-}
-
-// f(Tag{}) with Tag = int32_t or int64_t
-template <typename F>
-int with_tag(int bits, F&& f) {
-  if (bits == 32) return f(int32_t{});
-  return f(int64_t{});
 }
 
 }  // namespace
@@ -611,7 +599,7 @@ int dgla_sort_csr_by_tag(const dgla_csr* csr, const void* tag, int tag_bits, int
   int fl[kFwWords];
   const int rc = with_idx(csr->idtype_bits, [&](auto id) -> int {
     using Idx = decltype(id);
-    return with_tag(tag_bits, [&](auto tg) -> int {
+    return with_idx(tag_bits, [&](auto tg) -> int {
       using Tag = decltype(tg);
       const TypedCsr<Idx> g(csr);
       const Tag* tp = static_cast<const Tag*>(tag);
@@ -640,7 +628,7 @@ int dgla_sort_csr_by_tag_host(const dgla_csr* csr, const void* tag, int tag_bits
   if (check_sort(who, csr, tag, tag_bits, num_tags, out_indices, out_data, tag_pos)) return -1;
   return with_idx(csr->idtype_bits, [&](auto id) -> int {
     using Idx = decltype(id);
-    return with_tag(tag_bits, [&](auto tg) -> int {
+    return with_idx(tag_bits, [&](auto tg) -> int {
       using Tag = decltype(tg);
       return sort_by_tag_host<Idx, Tag>(who, TypedCsr<Idx>(csr), static_cast<const Tag*>(tag), num_tags,
                                         static_cast<Idx*>(out_indices), static_cast<Idx*>(out_data), static_cast<Idx*>(tag_pos));
@@ -672,7 +660,7 @@ int dgla_sample_neighbors_biased(const dgla_csr* csr, const void* tag_offset, in
   if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
-  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.picks);
+  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.head.picks);
   int* flags = reinterpret_cast<int*>(scratch.p + L.flags);
   hipLaunchKernelGGL(biased_clear_kernel, dim3(1), dim3(64), 0, s, flags, static_cast<int>(kFwWords));
   const int rc = with_idx(csr->idtype_bits, [&](auto id) -> int {
@@ -680,29 +668,27 @@ int dgla_sample_neighbors_biased(const dgla_csr* csr, const void* tag_offset, in
     return with_float(bias_dtype, [&](auto bt) -> int {
       using B = decltype(bt);
       const TypedCsr<Idx> g(csr);
+      const SeedCsrOut<Idx> o(seeds, out_indptr, out_nbr, out_eids);
       const Idx* off = static_cast<const Idx*>(tag_offset);
       const B* b = static_cast<const B*>(bias);
-      const Idx* sd = static_cast<const Idx*>(seeds);
       hipLaunchKernelGGL((biased_count_kernel<Idx, B>), dim3(grid1(n + 1, kBiasedCountBlock)), dim3(kBiasedCountBlock), 0, s,
-                         g.indptr, off, b, sd, n, g.num_rows, g.nnz, T, fanout, replace, picks, flags);
-      if (msd::exclusive_scan<int64_t, Idx>(picks, static_cast<Idx*>(out_indptr), n + 1, scratch.p + L.scan, s)) return -1;
+                         g.indptr, off, b, o.seeds, n, g.num_rows, g.nnz, T, fanout, replace, picks, flags);
+      if (msd::exclusive_scan<int64_t, Idx>(picks, o.indptr, n + 1, scratch.p + L.head.scan, s)) return -1;
       if (fanout < 0) {  // the sizes depend on the graph: the flag words come back before the pick launch
         int fl[kFwWords];
         if (read_back(fl, flags, sizeof(fl), s)) return -1;
-        if (fl[kFwBadSeed]) return biased_bad_seed(who, g.num_rows);
+        if (fl[kFwBadSeed]) return bad_seed(who, g.num_rows);
       }
-      if (!out_nbr || fanout == 0) return 0;
-      Idx *on = static_cast<Idx*>(out_nbr), *oe = static_cast<Idx*>(out_eids);
-      const Idx* oi = static_cast<const Idx*>(out_indptr);
+      if (!o.nbr || fanout == 0) return 0;
       if (biased_width(T) == 16)
         hipLaunchKernelGGL((biased_pick_kernel<Idx, B, 16, 16>), dim3(grid1(n, 4)), dim3(64), 0, s, g.indptr, g.indices, g.data, off,
-                           b, sd, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, oi, on, oe);
+                           b, o.seeds, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, o.indptr, o.nbr, o.eids);
       else if (T <= kBiasedCapSmall)
         hipLaunchKernelGGL((biased_pick_kernel<Idx, B, 64, kBiasedCapSmall>), dim3(grid1(n, 1)), dim3(64), 0, s, g.indptr, g.indices,
-                           g.data, off, b, sd, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, oi, on, oe);
+                           g.data, off, b, o.seeds, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, o.indptr, o.nbr, o.eids);
       else
         hipLaunchKernelGGL((biased_pick_kernel<Idx, B, 64, kBiasedMaxTags>), dim3(grid1(n, 1)), dim3(64), 0, s, g.indptr, g.indices,
-                           g.data, off, b, sd, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, oi, on, oe);
+                           g.data, off, b, o.seeds, n, g.num_rows, g.nnz, T, fanout, replace, rng_seed, o.indptr, o.nbr, o.eids);
       return 0;
     });
   });
@@ -722,9 +708,8 @@ int dgla_sample_neighbors_biased_host(const dgla_csr* csr, const void* tag_offse
     return with_float(bias_dtype, [&](auto bt) -> int {
       using B = decltype(bt);
       return sample_biased_host<Idx, B>(who, TypedCsr<Idx>(csr), static_cast<const Idx*>(tag_offset), num_tags,
-                                        static_cast<const B*>(bias), static_cast<const Idx*>(seeds), num_seeds, fanout, replace != 0,
-                                        rng_seed, static_cast<Idx*>(out_indptr), static_cast<Idx*>(out_nbr),
-                                        static_cast<Idx*>(out_eids));
+                                        static_cast<const B*>(bias), SeedCsrOut<Idx>(seeds, out_indptr, out_nbr, out_eids),
+                                        num_seeds, fanout, replace != 0, rng_seed);
     });
   });
 }

@@ -254,14 +254,14 @@ __global__ __launch_bounds__(kEtypeBlock) void etype_kernel(const Idx* __restric
 
 // ---- host side --------------------------------------------------------------------------------------
 struct EtypeLayout {  // offsets into the workspace of dgla_sample_etype_neighbors
-  size_t picks, scan, bytes;
+  SeedScan head;
+  size_t bytes;
 };
 
 EtypeLayout etype_layout(int64_t n) {
   EtypeLayout L{};
   Carver c;
-  L.picks = c.take(sizeof(int64_t) * static_cast<size_t>(n + 1));
-  L.scan = c.take(msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
+  L.head = take_seed_scan(c, n, msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
   L.bytes = c.bytes();
   return L;
 }
@@ -278,10 +278,7 @@ int check_etype(const char* who, const dgla_csr* csr, const int64_t* etype_offse
   if (!fanout) return fail(who, "fanout is null");
   if (prob && prob_dtype != kF32 && prob_dtype != kF64 && prob_dtype != kEtypeU8)
     return fail(who, "unsupported prob dtype " + std::to_string(prob_dtype) + " (fp32, fp64 and uint8 are accepted)");
-  if (num_seeds < 0) return fail(who, "negative number of seeds");
-  if (num_seeds > 0 && !seeds) return fail(who, "seeds is null");
-  if (!out_indptr) return fail(who, "out_indptr is null");
-  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
+  if (check_seeds(who, seeds, num_seeds) || check_seed_outputs(who, out_indptr, out_nbr, out_eids)) return -1;
   if (out_nbr && out_capacity < 0) return fail(who, "negative out_capacity");
   return 0;
 }
@@ -297,8 +294,7 @@ int with_prob(const void* prob, int dtype, F&& f) {
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx, typename P>
 int sample_etype_host(const char* who, const TypedCsr<Idx>& g, const int64_t* off, const int64_t* fan, int64_t T,
-                      const P* const* prob, const Idx* seeds, int64_t n, bool rep, uint64_t rng_seed, Idx* out_indptr, Idx* out_nbr,
-                      Idx* out_eids, int64_t cap) {
+                      const P* const* prob, const SeedCsrOut<Idx>& o, int64_t n, bool rep, uint64_t rng_seed, int64_t cap) {
   const int W = etype_width(T);
   std::vector<double> w(W), x(W);
   std::vector<int64_t> chosen;
@@ -306,14 +302,14 @@ int sample_etype_host(const char* who, const TypedCsr<Idx>& g, const int64_t* of
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
-    topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
-    out_indptr[i] = static_cast<Idx>(at);
+    topk_row(g.indptr, o.seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
+    o.indptr[i] = static_cast<Idx>(at);
     if (bad) continue;
-    const int64_t u = static_cast<int64_t>(seeds[i]), deg = hi - lo;
+    const int64_t u = static_cast<int64_t>(o.seeds[i]), deg = hi - lo;
     auto emit = [&](int64_t slot, int64_t pos) {
       if (slot >= cap || pos >= deg) return;
-      out_nbr[slot] = g.indices[lo + pos];
-      out_eids[slot] = static_cast<Idx>(topk_eid(g.data, lo + pos));
+      o.nbr[slot] = g.indices[lo + pos];
+      o.eids[slot] = static_cast<Idx>(topk_eid(g.data, lo + pos));
     };
     for (int64_t t = 0; t < T; ++t) {
       const int64_t b0 = off[t], b1 = off[t + 1], f = fan[t];
@@ -331,7 +327,7 @@ int sample_etype_host(const char* who, const TypedCsr<Idx>& g, const int64_t* of
       }
       const int64_t cnt = etype_picks(pos, f, rep), slot = at;
       at += cnt;
-      if (!out_nbr || cnt == 0) continue;
+      if (!o.nbr || cnt == 0) continue;
       const uint64_t key = etype_key(rng_seed, u, t);
       if (f < 0 || (!rep && pos <= f)) {
         int64_t done = 0;
@@ -393,22 +389,22 @@ int sample_etype_host(const char* who, const TypedCsr<Idx>& g, const int64_t* of
       }
     }
   }
-  out_indptr[n] = static_cast<Idx>(at);
+  o.indptr[n] = static_cast<Idx>(at);
   return 0;
 }
 
 template <typename Idx, typename P, int W>
-void launch_etype(const TypedCsr<Idx>& g, const int64_t* off, const int64_t* fan, int64_t T, const P* const* prob, const Idx* seeds,
-                  int64_t n, int replace, uint64_t rng_seed, int64_t* picks, const Idx* out_indptr, Idx* out_nbr, Idx* out_eids,
-                  int64_t cap, bool pick, hipStream_t s) {
+void launch_etype(const TypedCsr<Idx>& g, const int64_t* off, const int64_t* fan, int64_t T, const P* const* prob,
+                  const SeedCsrOut<Idx>& o, int64_t n, int replace, uint64_t rng_seed, int64_t* picks, int64_t cap, bool pick,
+                  hipStream_t s) {
   const size_t lds = sizeof(int64_t) * static_cast<size_t>(2 * T + 1);
   const dim3 grid(grid1(pick ? n : n + 1, kEtypeBlock / W)), block(kEtypeBlock);
   if (pick)
-    hipLaunchKernelGGL((etype_kernel<Idx, P, W, true>), grid, block, lds, s, g.indptr, g.indices, g.data, off, fan, prob, seeds, n,
-                       g.num_rows, g.nnz, T, replace, rng_seed, picks, out_indptr, out_nbr, out_eids, cap);
+    hipLaunchKernelGGL((etype_kernel<Idx, P, W, true>), grid, block, lds, s, g.indptr, g.indices, g.data, off, fan, prob, o.seeds, n,
+                       g.num_rows, g.nnz, T, replace, rng_seed, picks, o.indptr, o.nbr, o.eids, cap);
   else
-    hipLaunchKernelGGL((etype_kernel<Idx, P, W, false>), grid, block, lds, s, g.indptr, g.indices, g.data, off, fan, prob, seeds, n,
-                       g.num_rows, g.nnz, T, replace, rng_seed, picks, out_indptr, out_nbr, out_eids, cap);
+    hipLaunchKernelGGL((etype_kernel<Idx, P, W, false>), grid, block, lds, s, g.indptr, g.indices, g.data, off, fan, prob, o.seeds, n,
+                       g.num_rows, g.nnz, T, replace, rng_seed, picks, o.indptr, o.nbr, o.eids, cap);
 }
 
 }  // namespace
@@ -443,24 +439,23 @@ int dgla_sample_etype_neighbors(const dgla_csr* csr, const int64_t* etype_offset
   if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
-  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.picks);
+  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.head.picks);
   const int rc = with_idx(csr->idtype_bits, [&](auto id) -> int {
     using Idx = decltype(id);
     return with_prob(prob, prob_dtype, [&](auto pt) -> int {
       using P = decltype(pt);
       const TypedCsr<Idx> g(csr);
       const P* const* pp = reinterpret_cast<const P* const*>(prob);
-      const Idx* sd = static_cast<const Idx*>(seeds);
-      Idx *oi = static_cast<Idx*>(out_indptr), *on = static_cast<Idx*>(out_nbr), *oe = static_cast<Idx*>(out_eids);
+      const SeedCsrOut<Idx> o(seeds, out_indptr, out_nbr, out_eids);
       auto pass = [&](bool pick) {
         if (etype_width(T) == 16)
-          launch_etype<Idx, P, 16>(g, etype_offset, fanout, T, pp, sd, n, replace, rng_seed, picks, oi, on, oe, out_capacity, pick, s);
+          launch_etype<Idx, P, 16>(g, etype_offset, fanout, T, pp, o, n, replace, rng_seed, picks, out_capacity, pick, s);
         else
-          launch_etype<Idx, P, 64>(g, etype_offset, fanout, T, pp, sd, n, replace, rng_seed, picks, oi, on, oe, out_capacity, pick, s);
+          launch_etype<Idx, P, 64>(g, etype_offset, fanout, T, pp, o, n, replace, rng_seed, picks, out_capacity, pick, s);
       };
       pass(false);
-      if (msd::exclusive_scan<int64_t, Idx>(picks, oi, n + 1, scratch.p + L.scan, s)) return -1;
-      if (on && out_capacity > 0) pass(true);
+      if (msd::exclusive_scan<int64_t, Idx>(picks, o.indptr, n + 1, scratch.p + L.head.scan, s)) return -1;
+      if (o.nbr && out_capacity > 0) pass(true);
       return 0;
     });
   });
@@ -483,9 +478,9 @@ int dgla_sample_etype_neighbors_host(const dgla_csr* csr, const int64_t* etype_o
     return with_prob(prob, prob_dtype, [&](auto pt) -> int {
       using P = decltype(pt);
       return sample_etype_host<Idx, P>(who, TypedCsr<Idx>(csr), etype_offset, fanout, num_etypes,
-                                       reinterpret_cast<const P* const*>(prob), static_cast<const Idx*>(seeds), num_seeds, replace != 0,
-                                       rng_seed, static_cast<Idx*>(out_indptr), static_cast<Idx*>(out_nbr),
-                                       static_cast<Idx*>(out_eids), out_capacity);
+                                       reinterpret_cast<const P* const*>(prob),
+                                       SeedCsrOut<Idx>(seeds, out_indptr, out_nbr, out_eids), num_seeds, replace != 0, rng_seed,
+                                       out_capacity);
     });
   });
 }

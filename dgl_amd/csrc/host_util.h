@@ -1,8 +1,9 @@
-// Host-side scaffold of the sampler and sparse units (sampling, random_walk, node2vec, negative_sampling, pinsage,
-// csr_mm, coo2csr, labor, knn, matching, subgraph, exclude, traversal, topk): launch geometry, the structural CSR check
-// and the typed CSR view, the workspace carver and its two bindings, the read-back, and the id-width and float-type
-// dispatches.  fail(msg), align256() and gptr<T> live in common.h, which every unit includes.  Nothing here is device
-// code.
+// Host-side scaffold of the sixteen sampler and sparse units (sampling, random_walk, node2vec, negative_sampling,
+// pinsage, csr_mm, coo2csr, labor, knn, matching, subgraph, exclude, traversal, topk, biased, etype): launch geometry, the
+// structural CSR check and the typed CSR view, the workspace carver and its two bindings, the read-back, the id-width
+// and float-type dispatches, and what the seed-row samplers (topk, biased, etype) share: the refusals of their seeds and
+// outputs, the head of their workspace and the typed view of their arrays.  fail(msg), align256() and gptr<T> live in
+// common.h, which every unit includes.  Nothing here is device code.
 #pragma once
 #include <stdint.h>
 
@@ -65,6 +66,50 @@ struct Carver {
     return o;
   }
   size_t bytes() const { return at; }
+};
+
+// ---- seed-row samplers: a CSR over the seeds comes out (out_indptr[n + 1], out_nbr, out_eids) ----------------------
+// The two refusals of the seeds.  A unit calls this, then checks its own arguments (k, fanout), then
+// check_seed_outputs: the order decides which message a doubly wrong call gets.
+inline int check_seeds(const char* who, const void* seeds, int64_t num_seeds) {
+  if (num_seeds < 0) return fail(who, "negative number of seeds");
+  if (num_seeds > 0 && !seeds) return fail(who, "seeds is null");
+  return 0;
+}
+
+// The two refusals of the outputs: a null out_nbr asks for the sizes only, and then out_eids is not read either.
+inline int check_seed_outputs(const char* who, const void* out_indptr, const void* out_nbr, const void* out_eids) {
+  if (!out_indptr) return fail(who, "out_indptr is null");
+  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
+  return 0;
+}
+
+// What a call answers when the arrays show a seed that is no row of the CSR.
+inline int bad_seed(const char* who, int64_t num_rows) {
+  return fail(who, "a seed lies outside [0, " + std::to_string(num_rows) + ")");
+}
+
+// The head of a seed-row sampler's workspace: the pick counts, int64[n + 1], and the temporary of their device scan,
+// `scan_bytes` = msd::scan_temp_bytes(n + 1, sizeof(int64_t)) of sort.hip.h, which this header does not include.  A
+// unit's layout function takes it first and appends its own pieces (its flag words) after it.
+struct SeedScan {
+  size_t picks, scan;
+};
+inline SeedScan take_seed_scan(Carver& c, int64_t n, size_t scan_bytes) {
+  SeedScan h{};
+  h.picks = c.take(sizeof(int64_t) * static_cast<size_t>(n + 1));
+  h.scan = c.take(scan_bytes);
+  return h;
+}
+
+// The seeds and the three outputs of a call in its id type, built once per with_idx body (as TypedCsr is).
+template <typename Idx>
+struct SeedCsrOut {
+  const Idx* seeds;
+  Idx *indptr, *nbr, *eids;
+  SeedCsrOut(const void* sd, void* out_indptr, void* out_nbr, void* out_eids)
+      : seeds(static_cast<const Idx*>(sd)), indptr(static_cast<Idx*>(out_indptr)), nbr(static_cast<Idx*>(out_nbr)),
+        eids(static_cast<Idx*>(out_eids)) {}
 };
 
 // The one wording of a workspace refusal.

@@ -239,14 +239,14 @@ __global__ __launch_bounds__(NT) void topk_select_kernel(const Idx* __restrict__
 
 // ---- host side --------------------------------------------------------------------------------------
 struct TopkLayout {  // offsets into the workspace of dgla_select_topk
-  size_t picks, scan, flags, bytes;
+  SeedScan head;
+  size_t flags, bytes;
 };
 
 TopkLayout topk_layout(int64_t n) {
   TopkLayout L{};
   Carver c;
-  L.picks = c.take(sizeof(int64_t) * static_cast<size_t>(n + 1));
-  L.scan = c.take(msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
+  L.head = take_seed_scan(c, n, msd::scan_temp_bytes(n + 1, sizeof(int64_t)));
   L.flags = c.take(sizeof(int64_t) * kFlWords);
   L.bytes = c.bytes();
   return L;
@@ -256,26 +256,20 @@ bool topk_dtype_ok(int dt) { return dt >= kTopkF32 && dt <= kTopkI64; }
 
 // everything dgla_select_topk and dgla_select_topk_host refuse before they read an array
 int check_topk(const char* who, const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds,
-               int64_t num_seeds, int64_t k, const void* out_indptr) {
+               int64_t num_seeds, int64_t k, const void* out_indptr, const void* out_nbr, const void* out_eids) {
   if (check_csr(who, csr)) return -1;
   if (!weight && csr->nnz > 0) return fail(who, "weight is null");
   if (!topk_dtype_ok(weight_dtype))
     return fail(who, "unsupported weight dtype " + std::to_string(weight_dtype) +
                          " (fp32, fp64, fp16, bf16, int32 and int64 are accepted)");
-  if (num_seeds < 0) return fail(who, "negative number of seeds");
-  if (num_seeds > 0 && !seeds) return fail(who, "seeds is null");
+  if (check_seeds(who, seeds, num_seeds)) return -1;
   if (k < -1) return fail(who, "k must be -1 (all), 0 or positive, got " + std::to_string(k));
-  if (!out_indptr) return fail(who, "out_indptr is null");
-  return 0;
+  return check_seed_outputs(who, out_indptr, out_nbr, out_eids);
 }
 
 int topk_over(const char* who, int64_t picks) {
   return fail(who, "a row yields " + std::to_string(picks) + " picks, which exceeds the limit of " +
                        std::to_string(kTopkMaxPicks) + " picks per row (select_topk_max_picks)");
-}
-
-int topk_bad_seed(const char* who, int64_t num_rows) {
-  return fail(who, "a seed lies outside [0, " + std::to_string(num_rows) + ")");
 }
 
 // f(std::integral_constant<int, DT>{}) for the weight type of a call, checked by the caller
@@ -293,8 +287,8 @@ int with_topk_dtype(int dt, F&& f) {
 
 // ---- the rule run by the CPU ------------------------------------------------------------------------
 template <typename Idx, int DT>
-int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight, const Idx* seeds, int64_t n, int64_t k,
-                     bool asc, Idx* out_indptr, Idx* out_nbr, Idx* out_eids) {
+int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight, const SeedCsrOut<Idx>& o, int64_t n, int64_t k,
+                     bool asc) {
   using K = typename TopkTypes<DT>::key;
   using Word = typename TopkTypes<DT>::word;
   using U = typename std::make_unsigned<Idx>::type;
@@ -303,8 +297,8 @@ int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
-    topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
-    if (bad) return topk_bad_seed(who, g.num_rows);
+    topk_row(g.indptr, o.seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
+    if (bad) return bad_seed(who, g.num_rows);
     const int64_t p = topk_picks(hi - lo, k);
     if (p > kTopkMaxPicks) return topk_over(who, p);
   }
@@ -318,10 +312,10 @@ int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight
   for (int64_t i = 0; i < n; ++i) {
     int64_t lo, hi;
     bool bad;
-    topk_row(g.indptr, seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
+    topk_row(g.indptr, o.seeds, g.num_rows, g.nnz, i, &lo, &hi, &bad);
     const int64_t p = topk_picks(hi - lo, k);
-    out_indptr[i] = static_cast<Idx>(at);
-    if (p == 0 || !out_nbr) {
+    o.indptr[i] = static_cast<Idx>(at);
+    if (p == 0 || !o.nbr) {
       at += p;
       continue;
     }
@@ -334,22 +328,20 @@ int select_topk_host(const char* who, const TypedCsr<Idx>& g, const void* weight
       return topk_before(a.key, a.eid, a.pos, b.key, b.eid, b.pos);
     });
     for (int64_t r = 0; r < p; ++r) {
-      out_eids[at + r] = static_cast<Idx>(row[r].eid);
-      out_nbr[at + r] = g.indices[lo + row[r].pos];
+      o.eids[at + r] = static_cast<Idx>(row[r].eid);
+      o.nbr[at + r] = g.indices[lo + row[r].pos];
     }
     at += p;
   }
-  out_indptr[n] = static_cast<Idx>(at);
+  o.indptr[n] = static_cast<Idx>(at);
   return 0;
 }
 
 template <typename Idx, int DT, int NT, int G, int CAP>
-void launch_select(const dgla_csr* csr, const void* weight, const void* seeds, int64_t n, int64_t k, int asc, void* out_indptr,
-                   void* out_nbr, void* out_eids, hipStream_t s) {
-  const TypedCsr<Idx> g(csr);
+void launch_select(const TypedCsr<Idx>& g, const void* weight, const SeedCsrOut<Idx>& o, int64_t n, int64_t k, int asc,
+                   hipStream_t s) {
   hipLaunchKernelGGL((topk_select_kernel<Idx, DT, NT, G, CAP>), dim3(grid1(n, NT / G)), dim3(NT), 0, s, g.indptr, g.indices,
-                     g.data, weight, static_cast<const Idx*>(seeds), n, g.num_rows, g.nnz, k, asc,
-                     static_cast<const Idx*>(out_indptr), static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eids));
+                     g.data, weight, o.seeds, n, g.num_rows, g.nnz, k, asc, o.indptr, o.nbr, o.eids);
 }
 
 }  // namespace
@@ -370,8 +362,7 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
                      int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids, void* workspace,
                      size_t workspace_bytes, void* hip_stream) {
   const char* who = "select_topk";
-  if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr)) return -1;
-  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
+  if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr, out_nbr, out_eids)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out_indptr);
   const int64_t n = num_seeds;
@@ -384,14 +375,15 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
   if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
-  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.picks);
+  int64_t* picks = reinterpret_cast<int64_t*>(scratch.p + L.head.picks);
   int64_t* flags = reinterpret_cast<int64_t*>(scratch.p + L.flags);
   DGLA_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int64_t) * kFlWords, s));
   const int rc = with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
+    const SeedCsrOut<Idx> o(seeds, out_indptr, out_nbr, out_eids);
     hipLaunchKernelGGL(topk_count_kernel<Idx>, dim3(grid1(n + 1, kTopkCountBlock)), dim3(kTopkCountBlock), 0, s,
-                       TypedCsr<Idx>(csr).indptr, static_cast<const Idx*>(seeds), n, csr->num_rows, csr->nnz, k, picks, flags);
-    return msd::exclusive_scan<int64_t, Idx>(picks, static_cast<Idx*>(out_indptr), n + 1, scratch.p + L.scan, s);
+                       TypedCsr<Idx>(csr).indptr, o.seeds, n, csr->num_rows, csr->nnz, k, picks, flags);
+    return msd::exclusive_scan<int64_t, Idx>(picks, o.indptr, n + 1, scratch.p + L.head.scan, s);
   });
   if (rc) return -1;
   // The largest pick count decides the size class.  0 <= k <= 1024 bounds it without a read-back (and a seed outside
@@ -400,7 +392,7 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
   if (k < 0 || k > kTopkMaxPicks) {
     int64_t fl[kFlWords];
     if (read_back(fl, flags, sizeof(fl), s)) return -1;
-    if (fl[kFlBadSeed]) return topk_bad_seed(who, csr->num_rows);
+    if (fl[kFlBadSeed]) return bad_seed(who, csr->num_rows);
     if (fl[kFlOver]) return topk_over(who, fl[kFlOverPicks]);
     bound = fl[kFlAboveB] ? kTopkCapC : (fl[kFlAboveA] ? kTopkCapB : kTopkCapA);
   }
@@ -412,14 +404,16 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
   const bool short_rows = csr->nnz / rows <= kTopkShortMean;
   with_idx(csr->idtype_bits, [&](auto tag) {
     using Idx = decltype(tag);
+    const TypedCsr<Idx> g(csr);
+    const SeedCsrOut<Idx> o(seeds, out_indptr, out_nbr, out_eids);
     return with_topk_dtype(weight_dtype, [&](auto dt) -> int {
       constexpr int DT = decltype(dt)::value;
       if (bound <= kTopkCapA && short_rows)
-        launch_select<Idx, DT, 64, 16, kTopkCapA>(csr, weight, seeds, n, k, ascending, out_indptr, out_nbr, out_eids, s);
+        launch_select<Idx, DT, 64, 16, kTopkCapA>(g, weight, o, n, k, ascending, s);
       else if (bound <= kTopkCapB)
-        launch_select<Idx, DT, 64, 64, kTopkCapB>(csr, weight, seeds, n, k, ascending, out_indptr, out_nbr, out_eids, s);
+        launch_select<Idx, DT, 64, 64, kTopkCapB>(g, weight, o, n, k, ascending, s);
       else
-        launch_select<Idx, DT, 256, 256, kTopkCapC>(csr, weight, seeds, n, k, ascending, out_indptr, out_nbr, out_eids, s);
+        launch_select<Idx, DT, 256, 256, kTopkCapC>(g, weight, o, n, k, ascending, s);
       return 0;
     });
   });
@@ -430,14 +424,13 @@ int dgla_select_topk(const dgla_csr* csr, const void* weight, int weight_dtype, 
 int dgla_select_topk_host(const dgla_csr* csr, const void* weight, int weight_dtype, const void* seeds, int64_t num_seeds,
                           int64_t k, int ascending, void* out_indptr, void* out_nbr, void* out_eids) {
   const char* who = "select_topk_host";
-  if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr)) return -1;
-  if (out_nbr && !out_eids) return fail(who, "out_eids is null");
+  if (check_topk(who, csr, weight, weight_dtype, seeds, num_seeds, k, out_indptr, out_nbr, out_eids)) return -1;
   return with_idx(csr->idtype_bits, [&](auto tag) -> int {
     using Idx = decltype(tag);
+    const SeedCsrOut<Idx> o(seeds, out_indptr, out_nbr, out_eids);
     return with_topk_dtype(weight_dtype, [&](auto dt) -> int {
       constexpr int DT = decltype(dt)::value;
-      return select_topk_host<Idx, DT>(who, TypedCsr<Idx>(csr), weight, static_cast<const Idx*>(seeds), num_seeds, k, ascending != 0,
-                                       static_cast<Idx*>(out_indptr), static_cast<Idx*>(out_nbr), static_cast<Idx*>(out_eids));
+      return select_topk_host<Idx, DT>(who, TypedCsr<Idx>(csr), weight, o, num_seeds, k, ascending != 0);
     });
   });
 }

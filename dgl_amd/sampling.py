@@ -43,6 +43,66 @@ def _node_ids(nodes, device, idtype):
     return torch.as_tensor(nodes).reshape(-1).to(device=device, dtype=idtype).contiguous()
 
 
+def _nodes_by_type(g, nodes):
+    """``nodes`` (ids, or a dict per node type) as a dict per node type of ``g``."""
+    if not isinstance(nodes, dict):
+        if len(g.ntypes) != 1:
+            raise _DGLError("Must specify node type when the graph is not homogeneous.")
+        nodes = {g.ntypes[0]: nodes}
+    for n in nodes:
+        if n not in g.ntypes:
+            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    return nodes
+
+
+def _direction_view(rel, edge_dir, gpu, indices_data=None):
+    """The ``dgla_csr`` of relation ``rel`` whose rows are the seed side: the CSC for ``"in"``, the CSR for ``"out"``.  A GPU
+    graph goes through ``make_csr``, a CPU graph through ``host_csr`` on contiguous arrays; either keeps the arrays it
+    borrows alive.  ``indices_data`` replaces the two arrays behind the indptr (the same rows in another order)."""
+    indptr, indices, data = rel.csc() if edge_dir == "in" else rel.csr()
+    if indices_data is not None:
+        indices, data = indices_data
+    cols = rel.num_src if edge_dir == "in" else rel.num_dst
+    if gpu:
+        return _capi.make_csr(indptr, indices, data, cols)
+    return _capi.host_csr(indptr.contiguous(), indices.contiguous(), None if data is None else data.contiguous(), cols)
+
+
+def _seed_rows(seeds, indptr, nbr, eids):
+    """``(own, nbr, eids)`` of a CSR over ``seeds``: the seed of every entry, and the two outputs cut to the
+    ``indptr[-1]`` entries that are the result (a device call allocates them at capacity)."""
+    n_e = int(indptr[-1])
+    own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
+    return own, nbr[:n_e], eids[:n_e]
+
+
+def _frontier(g, edges_per_relation, copy_ndata, copy_edata, edge_dir, output_device=None):
+    """The graph a seed-row sampler returns: every node type and node count of ``g`` and, per relation, the edges
+    ``(own, nbr, eids)`` of ``edges_per_relation`` (``own`` the seed side under ``edge_dir``; ``None``: no edge).
+    ``edata[EID]`` holds ``eids``; ``copy_ndata`` shares the node features of ``g`` (the same tensors, as
+    utils.extract_node_subframes(g, None) does) and ``copy_edata`` gathers its edge features at ``eids``."""
+    gi = g._graph
+    rels, picked = [], []
+    for rel, edges in zip(gi.relations, edges_per_relation):
+        own, nbr, eids = edges or (torch.empty(0, dtype=rel.idtype, device=rel.device),) * 3
+        src, dst = (nbr.contiguous(), own) if edge_dir == "in" else (own, nbr.contiguous())
+        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=rel.idtype, device=rel.device))
+        picked.append(eids)
+    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
+                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
+    if copy_ndata:
+        for i, fr in enumerate(g._node_frames):
+            for key, val in fr.items():
+                out._node_frames[i][key] = val
+    for etid, eids in enumerate(picked):
+        if copy_edata:
+            for key, val in g._edge_frames[etid].items():
+                if key != EID:
+                    out._edge_frames[etid][key] = val[eids.long()]
+        out._edge_frames[etid][EID] = eids
+    return out if output_device is None else out.to(output_device)
+
+
 def _relation_slot(rel, name, keyed_tensors, build):
     """What ``build()`` returns, kept in ONE slot ``name`` on relation ``rel``: keyed by the address, ``_version``, shape,
     dtype and device of ``keyed_tensors`` and checked at every use (as ``static_features`` checks its promise), so an
@@ -153,29 +213,18 @@ def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed, ex
     """sample_neighbors on a graph with several relations (python/dgl/sampling/neighbor.py:300-395): relation by
     relation through the same kernels; a relation whose seed side has no nodes in ``nodes``, or whose fanout is 0, comes
     out empty.  The result keeps every node type and node count of ``g``."""
-    if not isinstance(nodes, dict):
-        if len(g.ntypes) != 1:
-            raise _DGLError("Must specify node type when the graph is not homogeneous.")
-        nodes = {g.ntypes[0]: nodes}
-    for n in nodes:
-        if n not in g.ntypes:
-            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    nodes = _nodes_by_type(g, nodes)
     fanouts = _per_etype(g, fanout, "fanout")
-    rels = []
-    picked = []
+    edges = []
     for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
         rel = g._graph.relations[etid]
-        dev, idt = rel.device, rel.idtype
         seeds = nodes.get(d_t if edge_dir == "in" else s_t)
         f = int(fanouts[etid])
         if seeds is None or f == 0 or rel.num_edges == 0 or torch.as_tensor(seeds).numel() == 0:
-            empty = torch.empty(0, dtype=idt, device=dev)
-            rels.append(Relation(rel.num_src, rel.num_dst, empty, empty, idtype=idt, device=dev))
-            picked.append(empty)
+            edges.append(None)
             continue
-        seeds = _node_ids(seeds, dev, idt)
-        fmt = rel.csc() if edge_dir == "in" else rel.csr()
-        csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_src if edge_dir == "in" else rel.num_dst)
+        seeds = _node_ids(seeds, rel.device, rel.idtype)
+        csr = _direction_view(rel, edge_dir, True)
         p = _prob_of(prob, g._edge_frames[etid], rel, "sample_neighbors")
         rng = int(seed) * 131 + etid
         if p is None:
@@ -186,21 +235,12 @@ def _sample_neighbors_hetero(g, nodes, fanout, edge_dir, prob, replace, seed, ex
             indptr, nbr, eids = _capi.sample_neighbors_weighted(csr, p, seeds, f, replace, rng)
         if excluded is not None and excluded[etid] is not None:     # sample first, then drop (sampling/utils.py EidExcluder)
             indptr, nbr, eids = _capi.frontier_exclude(indptr, nbr, eids, excluded[etid])
-        n_e = int(indptr[-1])
-        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
-        nbr, eids = nbr[:n_e], eids[:n_e]
+        own, nbr, eids = _seed_rows(seeds, indptr, nbr, eids)
         if p is not None and f < 0:
             keep_e = p[eids.long()] > 0
             own, nbr, eids = own[keep_e], nbr[keep_e], eids[keep_e]
-        src, dst = (nbr.contiguous(), own) if edge_dir == "in" else (own, nbr.contiguous())
-        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev))
-        picked.append(eids)
-    gi = g._graph
-    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
-                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
-    for etid, e in enumerate(picked):
-        out._edge_frames[etid][EID] = e
-    return out
+        edges.append((own, nbr, eids))
+    return _frontier(g, edges, False, False, edge_dir)
 
 
 def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, seed=None, exclude_edges=None):
@@ -644,16 +684,10 @@ def sample_labors(g, nodes, fanout, edge_dir="in", prob=None, importance_samplin
     if g.device.type != "cuda":
         raise _DGLError("sample_labors runs on a ROCm GPU; the graph is on %s (no CPU fallback)" % g.device)
     seed = _labor_seed(random_seed)
-    if not isinstance(nodes, dict):
-        if len(g.ntypes) != 1:
-            raise _DGLError("Must specify node type when the graph is not homogeneous.")
-        nodes = {g.ntypes[0]: nodes}
-    for n in nodes:
-        if n not in g.ntypes:
-            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    nodes = _nodes_by_type(g, nodes)
     fanouts = _per_etype(g, fanout, "fanout")
     excluded = _per_etype_ids(g, exclude_edges)
-    rels, picked, importances = [], [], []
+    edges, importances = [], []
     for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
         rel = g._graph.relations[etid]
         dev, idt = rel.device, rel.idtype
@@ -663,41 +697,26 @@ def sample_labors(g, nodes, fanout, edge_dir="in", prob=None, importance_samplin
         seeds = nodes.get(d_t if edge_dir == "in" else s_t)
         f = int(fanouts[etid])
         if seeds is None or f == 0 or rel.num_edges == 0 or torch.as_tensor(seeds).numel() == 0:
-            own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
-            imp = torch.empty(0, dtype=torch.float32 if p is None else p.dtype, device=dev)
-        else:
-            seeds = _node_ids(seeds, dev, idt)
-            fmt = rel.csc() if edge_dir == "in" else rel.csr()
-            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], rel.num_src if edge_dir == "in" else rel.num_dst)
-            # the SAME seed for every relation: a node's variate is shared across edge types (labor.py:101-112)
-            indptr, nbr, eids, imp = _capi.labor_sample(csr, seeds, f, seed, prob=p)
-            own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=int(eids.shape[0]))
-            if imp is None:
-                imp = torch.empty(0, dtype=torch.float32, device=dev)
-            if excluded[etid] is not None:
-                keep_e = ~torch.isin(eids, _node_ids(excluded[etid], dev, idt))
-                own, nbr, eids = own[keep_e], nbr[keep_e], eids[keep_e]
-                if p is not None:
-                    imp = imp[keep_e]
-        src, dst = (nbr.contiguous(), own) if edge_dir == "in" else (own, nbr.contiguous())
-        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev))
-        picked.append(eids)
+            edges.append(None)
+            importances.append(torch.empty(0, dtype=torch.float32 if p is None else p.dtype, device=dev))
+            continue
+        seeds = _node_ids(seeds, dev, idt)
+        csr = _direction_view(rel, edge_dir, True)
+        # the SAME seed for every relation: a node's variate is shared across edge types (labor.py:101-112)
+        indptr, nbr, eids, imp = _capi.labor_sample(csr, seeds, f, seed, prob=p)
+        # (not _seed_rows: labor_sample read the total back and cut nbr and eids to it)
+        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=int(eids.shape[0]))
+        if imp is None:
+            imp = torch.empty(0, dtype=torch.float32, device=dev)
+        if excluded[etid] is not None:
+            keep_e = ~torch.isin(eids, _node_ids(excluded[etid], dev, idt))
+            own, nbr, eids = own[keep_e], nbr[keep_e], eids[keep_e]
+            if p is not None:
+                imp = imp[keep_e]
+        edges.append((own, nbr, eids))
         importances.append(imp)
-    gi = g._graph
-    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
-                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
-    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
-        for i, fr in enumerate(g._node_frames):
-            for key, val in fr.items():
-                out._node_frames[i][key] = val
-    for etid, e in enumerate(picked):
-        if copy_edata:
-            for key, val in g._edge_frames[etid].items():
-                if key != EID:
-                    out._edge_frames[etid][key] = val[e.long()]
-        out._edge_frames[etid][EID] = e
+    out = _frontier(g, edges, copy_ndata, copy_edata, edge_dir, output_device)
     if output_device is not None:
-        out = out.to(output_device)
         importances = [w.to(output_device) for w in importances]
     return out, importances
 
@@ -730,13 +749,7 @@ def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False, copy_n
         raise _DGLError("%s: weight is the name of an edge feature, got %r" % (who, type(weight).__name__))
     if nodes is None:
         nodes = {n: torch.arange(g._graph.num_nodes(i)) for i, n in enumerate(g.ntypes)}
-    elif not isinstance(nodes, dict):
-        if len(g.ntypes) != 1:
-            raise _DGLError("Must specify node type when the graph is not homogeneous.")
-        nodes = {g.ntypes[0]: nodes}
-    for n in nodes:
-        if n not in g.ntypes:
-            raise _DGLError('Node type "{}" does not exist.'.format(n))
+    nodes = _nodes_by_type(g, nodes)
     if isinstance(k, dict) and len(k) != len(g.canonical_etypes):
         raise _DGLError("K value must be specified for each edge type if a dict is provided.")
     ks = _per_etype(g, k, "k")
@@ -746,10 +759,10 @@ def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False, copy_n
         if weight not in frame:
             raise _DGLError('Edge weights "{}" do not exist for relation graph "{}".'.format(weight, c))
         weights.append(frame[weight])
-    rels, picked = [], []
+    edges = []
     for etid, (s_t, _, d_t) in enumerate(g.canonical_etypes):
         rel = g._graph.relations[etid]
-        dev, idt = rel.device, rel.idtype
+        dev, gpu = rel.device, rel.device.type == "cuda"
         w = weights[etid]
         if w.dim() == 0 or w.shape[0] != rel.num_edges or w.numel() != rel.num_edges:
             raise _DGLError('%s: edge weights "%s" of relation graph "%s" must have one element per edge (%d), got shape %s'
@@ -757,39 +770,13 @@ def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False, copy_n
         seeds = nodes.get(d_t if edge_dir == "in" else s_t)
         kk = int(ks[etid])
         if seeds is None or kk == 0 or rel.num_edges == 0 or torch.as_tensor(seeds).numel() == 0:
-            own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
-        else:
-            seeds = _node_ids(seeds, dev, idt)
-            w = w.to(dev).reshape(-1).contiguous()
-            fmt = rel.csc() if edge_dir == "in" else rel.csr()
-            cols = rel.num_src if edge_dir == "in" else rel.num_dst
-            if dev.type == "cuda":
-                csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
-                indptr, nbr, eids = _capi.select_topk(csr, w, seeds, kk, ascending)
-            else:
-                csr = _capi.host_csr(fmt[0].contiguous(), fmt[1].contiguous(), None if fmt[2] is None else fmt[2].contiguous(),
-                                     cols)
-                indptr, nbr, eids = _capi.select_topk_host(csr, w, seeds, kk, ascending)
-            n_e = int(indptr[-1])
-            own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
-            nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
-        src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
-        rels.append(Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev))
-        picked.append(eids)
-    gi = g._graph
-    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges), rels),
-                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
-    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
-        for i, fr in enumerate(g._node_frames):
-            for key, val in fr.items():
-                out._node_frames[i][key] = val
-    for etid, e in enumerate(picked):
-        if copy_edata:
-            for key, val in g._edge_frames[etid].items():
-                if key != EID:
-                    out._edge_frames[etid][key] = val[e.long()]
-        out._edge_frames[etid][EID] = e
-    return out if output_device is None else out.to(output_device)
+            edges.append(None)
+            continue
+        seeds = _node_ids(seeds, dev, rel.idtype)
+        topk = _capi.select_topk if gpu else _capi.select_topk_host
+        rows = topk(_direction_view(rel, edge_dir, gpu), w.to(dev).reshape(-1).contiguous(), seeds, kk, ascending)
+        edges.append(_seed_rows(seeds, *rows))
+    return _frontier(g, edges, copy_ndata, copy_edata, edge_dir, output_device)
 
 
 DGLGraph.select_topk = select_topk
@@ -828,55 +815,31 @@ def sample_neighbors_biased(g, nodes, fanout, bias, edge_dir="in", tag_offset_na
         bias = bias.float()
     bias = bias.to(dev).reshape(-1).contiguous()
     seeds = _node_ids(nodes, dev, idt)
-    rng_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-    fmt = rel.csc() if edge_dir == "in" else rel.csr()
-    cols = rel.num_src if edge_dir == "in" else rel.num_dst
-    if seeds.numel() == 0 or int(fanout) == 0 or rel.num_edges == 0:
-        own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
-    else:
-        if dev.type == "cuda":
-            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
-            indptr, nbr, eids = _capi.sample_neighbors_biased(csr, offsets, bias, seeds, int(fanout), replace, rng_seed)
-        else:
-            csr = _capi.host_csr(fmt[0].contiguous(), fmt[1].contiguous(), None if fmt[2] is None else fmt[2].contiguous(), cols)
-            indptr, nbr, eids = _capi.sample_neighbors_biased_host(csr, offsets, bias, seeds, int(fanout), replace, rng_seed)
-        n_e = int(indptr[-1])
-        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
-        nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
-    src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
-    gi = g._graph
-    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges),
-                              [Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev)]),
-                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
-    if copy_ndata:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
-        for i, fr in enumerate(g._node_frames):
-            for key, val in fr.items():
-                out._node_frames[i][key] = val
-    if copy_edata:
-        for key, val in g._edge_frames[0].items():
-            if key != EID:
-                out._edge_frames[0][key] = val[eids.long()]
-    out._edge_frames[0][EID] = eids
-    return out if output_device is None else out.to(output_device)
+    rng_seed = _call_seed(seed)
+    gpu = dev.type == "cuda"
+    edges = None
+    if seeds.numel() != 0 and int(fanout) != 0 and rel.num_edges != 0:
+        biased = _capi.sample_neighbors_biased if gpu else _capi.sample_neighbors_biased_host
+        rows = biased(_direction_view(rel, edge_dir, gpu), offsets, bias, seeds, int(fanout), replace, rng_seed)
+        edges = _seed_rows(seeds, *rows)
+    return _frontier(g, [edges], copy_ndata, copy_edata, edge_dir, output_device)
 
 
 DGLGraph.sample_neighbors_biased = sample_neighbors_biased
 
 
-def _etype_sorted_rows(rel, fmt, cols, table, edge_dir):
-    """``(indices, data)`` of ``fmt`` with every row ordered by edge type: the per-edge type is computed once, the rows go
-    through the stable tag sort, and the result stays in ONE slot on the relation, keyed by direction and offsets.  The
+def _etype_sorted_rows(rel, edge_dir, gpu, table):
+    """``(indices, data)`` of the seed side's CSR with every row ordered by edge type: the per-edge type is computed once, the
+    rows go through the stable tag sort, and the result stays in ONE slot on the relation, keyed by direction and offsets.  The
     ``(N, T + 1)`` offset table of the sort is dropped: the sampler finds its ranges by bisection."""
     key = (edge_dir, tuple(table.host.tolist()))
     slot = getattr(rel, "_etype_sorted", None)
     if slot is None or slot[0] != key:
-        dev = fmt[0].device
+        dev = rel.device
         tag = torch.bucketize(torch.arange(rel.num_edges, device=dev), table.host[1:].to(dev), right=True)
         num_tags = table.num_etypes + (1 if int(table.host[-1]) < rel.num_edges else 0)   # (ids past the last type sort last)
-        if dev.type == "cuda":
-            indices, data, _ = _capi.sort_csr_by_tag(_capi.make_csr(fmt[0], fmt[1], fmt[2], cols), tag, num_tags)
-        else:
-            indices, data, _ = _capi.sort_csr_by_tag_host(_capi.host_csr(*fmt, cols), tag, num_tags)
+        sort = _capi.sort_csr_by_tag if gpu else _capi.sort_csr_by_tag_host
+        indices, data, _ = sort(_direction_view(rel, edge_dir, gpu), tag, num_tags)
         slot = (key, (indices, data))
         rel._etype_sorted = slot
     return slot[1]
@@ -929,40 +892,17 @@ def sample_etype_neighbors(g, nodes, etype_offset, fanout, edge_dir="in", prob=N
         prob = table.probs(views)
     seeds = _node_ids(nodes, dev, idt)
     rng_seed = _call_seed(seed)
-    fmt = rel.csc() if edge_dir == "in" else rel.csr()
-    fmt = tuple(None if t is None else t.contiguous() for t in fmt)
-    cols = rel.num_src if edge_dir == "in" else rel.num_dst
-    if seeds.numel() == 0 or rel.num_edges == 0:
-        own = nbr = eids = torch.empty(0, dtype=idt, device=dev)
-    else:
-        if not etype_sorted:
-            fmt = (fmt[0],) + _etype_sorted_rows(rel, fmt, cols, table, edge_dir)
+    edges = None
+    if seeds.numel() != 0 and rel.num_edges != 0:
+        csr = _direction_view(rel, edge_dir, gpu, None if etype_sorted else _etype_sorted_rows(rel, edge_dir, gpu, table))
         if gpu:
-            csr = _capi.make_csr(fmt[0], fmt[1], fmt[2], cols)
             f = fan.cpu()
             cap = None if bool((f < 0).any()) else int(f.sum()) * seeds.numel()
-            indptr, nbr, eids = _capi.sample_etype_neighbors(csr, table, fan, seeds, replace, rng_seed, prob=prob, capacity=cap)
+            rows = _capi.sample_etype_neighbors(csr, table, fan, seeds, replace, rng_seed, prob=prob, capacity=cap)
         else:
-            indptr, nbr, eids = _capi.sample_etype_neighbors_host(_capi.host_csr(*fmt, cols), table, fan, seeds, replace, rng_seed,
-                                                                  prob=prob)
-        n_e = int(indptr[-1])
-        own = torch.repeat_interleave(seeds, (indptr[1:] - indptr[:-1]).long(), output_size=n_e)
-        nbr, eids = nbr[:n_e].contiguous(), eids[:n_e].contiguous()
-    src, dst = (nbr, own) if edge_dir == "in" else (own, nbr)
-    gi = g._graph
-    out = DGLGraph(GraphIndex([gi.num_nodes(i) for i in range(len(g._ntypes))], list(gi.metagraph.edges),
-                              [Relation(rel.num_src, rel.num_dst, src, dst, idtype=idt, device=dev)]),
-                   g._ntypes, g.canonical_etypes, src_ntypes=g._src_ntype_ids, dst_ntypes=g._dst_ntype_ids)
-    if copy_ndata and not _dist_training:      # the same tensors, as utils.extract_node_subframes(g, None) shares them
-        for i, fr in enumerate(g._node_frames):
-            for key, val in fr.items():
-                out._node_frames[i][key] = val
-    if copy_edata and not _dist_training:
-        for key, val in g._edge_frames[0].items():
-            if key != EID:
-                out._edge_frames[0][key] = val[eids.long()]
-    out._edge_frames[0][EID] = eids
-    return out if output_device is None else out.to(output_device)
+            rows = _capi.sample_etype_neighbors_host(csr, table, fan, seeds, replace, rng_seed, prob=prob)
+        edges = _seed_rows(seeds, *rows)
+    return _frontier(g, [edges], copy_ndata and not _dist_training, copy_edata and not _dist_training, edge_dir, output_device)
 
 
 DGLGraph.sample_etype_neighbors = sample_etype_neighbors

@@ -30,6 +30,10 @@ ONES = np.ones(N, np.float64)
 ZERO_PTR = np.zeros(1, _I)
 OUT = [np.zeros(64, _I) for _ in range(4)]            # outputs of the host twins (at most 2 * NNZ + N entries)
 I32 = np.zeros(64, np.int32)
+TAG = np.zeros(NNZ, _I)                               # one tag: every edge has tag 0
+TAG_OFFSET = np.array([[0, 2]] * N, _I)               # [N, 2]: the one tag's range is the whole row
+ETYPE_OFFSET = np.array([0, NNZ], _I)                 # one edge type
+FANOUT = np.ones(1, _I)
 SCRATCH = np.zeros(1 << 16, np.uint8)                 # stands in for a workspace that is too small
 BFS_NODES = 0
 
@@ -92,6 +96,35 @@ def _other(c):  # a second operand that fits `c`
     return empty() if c is not None and c.num_rows == 0 else base()
 
 
+# The seed-row samplers (select_topk, sample_neighbors_biased, sample_etype_neighbors): `head` = the arguments in front
+# of the seeds, `tail` = those behind the outputs; the keywords are what the doubly wrong calls below damage.
+def _seed_rows(fn, c, head, tail, seeds=SEEDS, n=None, mid=(), indptr=OUT[0], nbr=OUT[1], eids=OUT[2]):
+    opt = lambda a: None if a is None else ptr(a)
+    return fn(ref(c), *head, opt(seeds), seeds_of(c) if n is None else n, *mid, opt(indptr), opt(nbr), opt(eids), *tail)
+
+
+def _topk(fn, tail, c, k=1, **kw):
+    return _seed_rows(fn, c, (ptr(W32), 0), tail, mid=(k, 0), **kw)
+
+
+def _biased(fn, tail, c, fanout=1, **kw):
+    return _seed_rows(fn, c, (ptr(TAG_OFFSET), 1, ptr(W32), 0), tail, mid=(fanout, 0, 7), **kw)
+
+
+def _etype(fn, tail, c, capacity=NNZ, **kw):
+    return _seed_rows(fn, c, (ptr(ETYPE_OFFSET), ptr(FANOUT), 1, None, 0), (capacity,) + tail, mid=(0, 7), **kw)
+
+
+DEVICE_TAIL = (None, 0, None)       # no workspace, the null stream
+SEED_ROW_CALLS = {
+    "select_topk": lambda c, **kw: _topk(LIB.dgla_select_topk, DEVICE_TAIL, c, **kw),
+    "select_topk_host": lambda c, **kw: _topk(LIB.dgla_select_topk_host, (), c, **kw),
+    "sample_neighbors_biased": lambda c, **kw: _biased(LIB.dgla_sample_neighbors_biased, DEVICE_TAIL, c, **kw),
+    "sample_neighbors_biased_host": lambda c, **kw: _biased(LIB.dgla_sample_neighbors_biased_host, (), c, **kw),
+    "sample_etype_neighbors": lambda c, **kw: _etype(LIB.dgla_sample_etype_neighbors, DEVICE_TAIL, c, **kw),
+    "sample_etype_neighbors_host": lambda c, **kw: _etype(LIB.dgla_sample_etype_neighbors_host, (), c, **kw),
+}
+
 # entry -> (who, call(csr or None)); the `_host` entries run on the CPU, the others refuse before they touch the GPU
 ENTRIES = {
     "csr_sorted_columns": ("csr_sorted_columns", lambda c: LIB.dgla_csr_sorted_columns(ref(c), ptr(OUT[0]), None, 0, None)),
@@ -126,6 +159,14 @@ ENTRIES = {
         ref(c), ptr(W32), 0, ptr(SEEDS), seeds_of(c), 1, 0, ptr(OUT[0]), ptr(OUT[1]), ptr(OUT[2]), None, 0, None)),
     "select_topk_host": ("select_topk_host", lambda c: LIB.dgla_select_topk_host(
         ref(c), ptr(W32), 0, ptr(SEEDS), seeds_of(c), 1, 0, ptr(OUT[0]), ptr(OUT[1]), ptr(OUT[2]))),
+    "sort_csr_by_tag": ("sort_csr_by_tag", lambda c: LIB.dgla_sort_csr_by_tag(
+        ref(c), ptr(TAG), 64, 1, ptr(OUT[0]), ptr(OUT[1]), ptr(OUT[2]), None)),
+    "sort_csr_by_tag_host": ("sort_csr_by_tag_host", lambda c: LIB.dgla_sort_csr_by_tag_host(
+        ref(c), ptr(TAG), 64, 1, ptr(OUT[0]), ptr(OUT[1]), ptr(OUT[2]))),
+    "sample_neighbors_biased": ("sample_neighbors_biased", SEED_ROW_CALLS["sample_neighbors_biased"]),
+    "sample_neighbors_biased_host": ("sample_neighbors_biased_host", SEED_ROW_CALLS["sample_neighbors_biased_host"]),
+    "sample_etype_neighbors": ("sample_etype_neighbors", SEED_ROW_CALLS["sample_etype_neighbors"]),
+    "sample_etype_neighbors_host": ("sample_etype_neighbors_host", SEED_ROW_CALLS["sample_etype_neighbors_host"]),
     "labor_scale": ("labor_scale", lambda c: LIB.dgla_labor_scale(
         ref(c), ptr(W32), 0, ptr(SEEDS), seeds_of(c), 1, ptr(ONES), None)),
     "labor_scale_host": ("labor_scale_host", lambda c: LIB.dgla_labor_scale_host(
@@ -178,6 +219,12 @@ REFUSED = {
     "traverse_host": ALL,
     "select_topk": ALL,
     "select_topk_host": ALL,
+    "sort_csr_by_tag": ALL,
+    "sort_csr_by_tag_host": ALL,
+    "sample_neighbors_biased": ALL,
+    "sample_neighbors_biased_host": ALL,
+    "sample_etype_neighbors": ALL,
+    "sample_etype_neighbors_host": ALL,
     "labor_scale": BUT_EMPTY,
     "labor_scale_host": BUT_EMPTY,
     "labor_count": BUT_EMPTY,
@@ -213,11 +260,11 @@ def observe(entry, defect):
 
 
 def test_tables_cover_every_entry_and_defect():
-    assert sorted(ENTRIES) == sorted(REFUSED) and len(ENTRIES) == 32 and len(DEFECTS) == 7
+    assert sorted(ENTRIES) == sorted(REFUSED) and len(ENTRIES) == 38 and len(DEFECTS) == 7
     assert all(set(r) <= set(DEFECTS) for r in REFUSED.values())
     # a device entry and its host twin refuse the same csr
     twins = [e for e in ENTRIES if e.endswith("_host") and e[:-5] in ENTRIES]
-    assert len(twins) == 8 and all(REFUSED[t] == REFUSED[t[:-5]] for t in twins)
+    assert len(twins) == 11 and all(REFUSED[t] == REFUSED[t[:-5]] for t in twins)
 
 
 HOST = sorted(e for e in ENTRIES if e.endswith("_host"))
@@ -241,6 +288,32 @@ def test_csr_defects_match_the_recorded_table(entry):
         elif entry.endswith("_host"):
             rc, msg = observe(entry, defect)
             assert rc == 0, (entry, defect, msg)
+
+
+# ---- calls that are wrong in two ways: the order of the checks decides the message ----------------------------------
+# (unit, damage) -> the message behind "<who>: "; recorded from the library as it stood before the units moved to
+# check_seeds / check_seed_outputs of csrc/host_util.h.  Asked of the device entry and of its host twin.
+DOUBLY_WRONG = [
+    ("select_topk", dict(n=-1, indptr=None), "negative number of seeds"),
+    ("select_topk", dict(k=-2, seeds=None), "seeds is null"),
+    ("select_topk", dict(k=-2, indptr=None), "k must be -1 (all), 0 or positive, got -2"),
+    ("select_topk", dict(indptr=None, eids=None), "out_indptr is null"),
+    ("sample_neighbors_biased", dict(n=-1, indptr=None), "negative number of seeds"),
+    ("sample_neighbors_biased", dict(fanout=-2, seeds=None), "seeds is null"),
+    ("sample_neighbors_biased", dict(fanout=-2, indptr=None), "fanout must be -1 (all), 0 or positive, got -2"),
+    ("sample_neighbors_biased", dict(indptr=None, eids=None), "out_indptr is null"),
+    ("sample_etype_neighbors", dict(n=-1, indptr=None), "negative number of seeds"),
+    ("sample_etype_neighbors", dict(seeds=None, indptr=None), "seeds is null"),
+    ("sample_etype_neighbors", dict(indptr=None, eids=None), "out_indptr is null"),
+    ("sample_etype_neighbors", dict(eids=None, capacity=-1), "out_eids is null"),
+]
+
+
+@pytest.mark.parametrize("twin", ["", "_host"], ids=["device", "host"])
+@pytest.mark.parametrize("unit,damage,message", DOUBLY_WRONG, ids=["%s-%s" % (u, "+".join(sorted(d))) for u, d, _ in DOUBLY_WRONG])
+def test_a_doubly_wrong_call_gets_the_first_check_s_message(unit, damage, message, twin):
+    assert SEED_ROW_CALLS[unit + twin](base(), **damage) == -1
+    assert last_error() == "%s%s: %s" % (unit, twin, message)
 
 
 # ---- workspaces ---------------------------------------------------------------------------------------------------
@@ -316,6 +389,10 @@ WORKSPACES = {
     "select_topk": ("select_topk", lambda: LIB.dgla_select_topk_workspace_bytes(64, N),
                     lambda ws, b: LIB.dgla_select_topk(ref(base()), ptr(W32), 0, ptr(SEEDS), N, 1, 0, ptr(OUT[0]), ptr(OUT[1]),
                                                        ptr(OUT[2]), ws, b, None), False),
+    "sample_neighbors_biased": ("sample_neighbors_biased", lambda: LIB.dgla_sample_neighbors_biased_workspace_bytes(64, N),
+                                lambda ws, b: _biased(LIB.dgla_sample_neighbors_biased, (ws, b, None), base()), False),
+    "sample_etype_neighbors": ("sample_etype_neighbors", lambda: LIB.dgla_sample_etype_neighbors_workspace_bytes(64, N),
+                               lambda ws, b: _etype(LIB.dgla_sample_etype_neighbors, (ws, b, None), base()), False),
 }
 
 
