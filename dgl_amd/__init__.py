@@ -18,7 +18,7 @@ from . import nn  # noqa: E402,F401
 from . import sampling  # noqa: E402,F401
 from .transforms import (adj_product_graph, adj_sum_graph, add_reverse_edges, add_self_loop, batch, bipartite_from_scipy, compact_graphs, edge_subgraph,  # noqa: E402,F401
                          from_scipy, in_subgraph, khop_in_subgraph, khop_out_subgraph, knn, knn_graph, node_subgraph, out_subgraph, remove_edges, remove_self_loop, reorder_graph,
-                         segmented_knn_graph, sort_csc_by_tag, sort_csr_by_tag, to_bidirected, to_simple, unbatch)
+                         segmented_knn_graph, shortest_dist, sort_csc_by_tag, sort_csr_by_tag, to_bidirected, to_simple, unbatch)
 from . import geometry  # noqa: E402,F401
 from . import traversal  # noqa: E402,F401
 from . import propagate  # noqa: E402,F401

@@ -1317,6 +1317,54 @@ def traverse_host(mode, csr, opposite=None, sources=None):
     return ids[:num_ids.value], list(sections[:num_sections.value])
 
 
+def shortest_dist_workspace_bytes(idtype, num_nodes, num_sources):
+    """The bytes of the workspace of :func:`shortest_dist` (dgla_shortest_dist_workspace_bytes; host query)."""
+    return int(LIB.dgla_shortest_dist_workspace_bytes(_id_bits(idtype), int(num_nodes), int(num_sources)))
+
+
+def _shortest_dist(who, gpu, csr, sources, return_paths, ws, max_lds_nodes):
+    """The two calls of dgla_shortest_dist / dgla_shortest_dist_host: dist and L first, then paths at (S, n, L)."""
+    indptr = csr._keep[0]
+    _all_on(gpu, who, indptr, sources, ws)
+    if sources is not None:
+        _id_tensor_ok(who, "sources", sources, indptr)
+    n = csr.num_rows
+    ns = n if sources is None else sources.shape[0]
+    dist = torch.empty((ns, n), dtype=torch.int64, device=indptr.device)
+    longest = ctypes.c_int64(0)
+    if gpu:
+        if return_paths and ws is None:    # the table of the first call outlives it
+            ws = _workspace(shortest_dist_workspace_bytes(indptr.dtype, n, ns), indptr.device)
+        tail = (*_ws(ws), int(max_lds_nodes or 0), _stream(indptr))
+        call = LIB.dgla_shortest_dist
+    else:
+        tail, call = (), LIB.dgla_shortest_dist_host
+    head = (ctypes.byref(csr), _ptr(sources), ns, _ptr(dist))
+    check_call(call(*head, None, ctypes.byref(longest) if return_paths else None, *tail))
+    if not return_paths:
+        return dist
+    paths = torch.empty((ns, n, longest.value), dtype=torch.int64, device=indptr.device)
+    if paths.numel():
+        check_call(call(*head, _ptr(paths), ctypes.byref(longest), *tail))
+    return dist, paths
+
+
+def shortest_dist(csr, sources, return_paths, ws=None, max_lds_nodes=None):
+    """The hop distance from every source to every node of the square IN-EDGE CSR `csr`, and one shortest path per pair
+    (dgla_shortest_dist; the rule: include/dgl_amd.h "Shortest distances and paths").  `sources` is an id tensor of the
+    csr's type on its device, or None for every node in order.  Returns `dist`, int64 (S, n) with -1 for an unreachable
+    node, or ``(dist, paths)`` with `paths` int64 (S, n, L): the edge ids of the path front to back, padded with -1, L
+    the largest distance, the only value read back (8 bytes).  `ws` (uint8, :func:`shortest_dist_workspace_bytes`) is
+    the optional workspace; `max_lds_nodes` can only lower the node count up to which the search keeps its masks in LDS."""
+    return _shortest_dist("shortest_dist", True, csr, sources, return_paths, ws, max_lds_nodes)
+
+
+def shortest_dist_host(csr, sources, return_paths):
+    """:func:`shortest_dist` run by the CPU on CPU tensors (dgla_shortest_dist_host; CSRs built with :func:`host_csr`):
+    a queue BFS per source, then the predecessor test and the walk-back the kernels compile too.  Needs no GPU."""
+    return _shortest_dist("shortest_dist_host", False, csr, sources, return_paths, None, None)
+
+
 def _seed_csr(call, args, seeds, capacity=None, tail=(), into=None, pass_capacity=False):
     """``(indptr, nbr, eids)``, a CSR over `seeds`, from an entry point of the form ``call(*args, out_indptr, out_nbr,
     out_eids, *tail)``.  With a `capacity` the outputs are allocated at it and the entry is called once; ``None`` asks

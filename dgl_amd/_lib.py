@@ -354,6 +354,14 @@ LIB.dgla_traverse.restype = c_int
 LIB.dgla_traverse.argtypes = _TRAVERSE + [c_void_p, c_size_t, c_void_p]
 LIB.dgla_traverse_host.restype = c_int
 LIB.dgla_traverse_host.argtypes = _TRAVERSE
+# the shortest-distance unit: csr, sources, num_sources, dist, paths, max_len
+_SHORTEST = [P(CSR), c_void_p, c_int64, c_void_p, c_void_p, P(c_int64)]
+LIB.dgla_shortest_dist_workspace_bytes.restype = c_size_t
+LIB.dgla_shortest_dist_workspace_bytes.argtypes = [c_int, c_int64, c_int64]
+LIB.dgla_shortest_dist.restype = c_int
+LIB.dgla_shortest_dist.argtypes = _SHORTEST + [c_void_p, c_size_t, c_int64, c_void_p]
+LIB.dgla_shortest_dist_host.restype = c_int
+LIB.dgla_shortest_dist_host.argtypes = _SHORTEST
 # the top-k selection unit: csr, weight, weight dtype, seeds, num_seeds, k, ascending, out_indptr, out_nbr, out_eids
 _TOPK = [P(CSR), c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]
 LIB.dgla_select_topk_max_picks.restype = c_int

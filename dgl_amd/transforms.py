@@ -922,6 +922,41 @@ def sort_csc_by_tag(g, tag, tag_offset_name="_TAG_OFFSET", tag_type="node"):
     return _sort_by_tag(g, tag, tag_offset_name, tag_type, False)
 
 
+def shortest_dist(g, root=None, return_paths=False):
+    """``dgl.shortest_dist`` (python/dgl/transforms/functional.py): the number of edges on a shortest directed path
+    between nodes, -1 where there is none, and optionally one such path per pair.  With a ``root`` the result is `dist`
+    of shape (N,) and `paths` of shape (N, L) from the root to every node; without, (N, N) and (N, N, L) for every pair.
+    Both are int64 on the graph's device.  A path lists its edge ids front to back, padded with -1; L is the largest
+    distance, and the path of a node to itself is all -1.
+
+    A GPU graph runs the kernels of csrc/shortest_dist.hip and never leaves the GPU (the reference copies the graph to
+    the host for scipy and rebuilds the paths in Python); a CPU graph runs the same rule compiled for the host.  Where a
+    pair has several shortest paths, the edge into every node is the one with the smallest edge id among those that leave
+    a node one step nearer to the source (include/dgl_amd.h "Shortest distances and paths").  The reference keeps whichever
+    predecessor scipy's queue found and whichever parallel edge ``edge_ids`` returns, so its paths have the same lengths
+    but may differ from these on such pairs."""
+    from . import _capi
+
+    who = "shortest_dist"
+    if len(g.canonical_etypes) != 1 or len(g.ntypes) != 1 or getattr(g, "is_block", False):
+        raise DGLAMDError("%s: takes a homogeneous graph (one node type, one edge type, no block)" % who)
+    rel = g._graph.relations[0]
+    n, dev = rel.num_dst, g.device
+    if root is not None and not 0 <= int(root) < n:
+        raise DGLAMDError("%s: the root %d lies outside [0, %d)" % (who, int(root), n))
+    if n == 0:
+        dist = torch.empty((0, 0), dtype=torch.int64, device=dev)
+        return (dist, torch.empty((0, 0, 0), dtype=torch.int64, device=dev)) if return_paths else dist
+    gpu = dev.type == "cuda"
+    indptr, indices, eids = (t if t is None else t.contiguous() for t in rel.csc())
+    csr = (_capi.make_csr if gpu else _capi.host_csr)(indptr, indices, eids, n)
+    sources = None if root is None else torch.tensor([int(root)], dtype=indptr.dtype, device=indptr.device)
+    out = _capi.shortest_dist(csr, sources, return_paths) if gpu else _capi.shortest_dist_host(csr, sources, return_paths)
+    if root is None:
+        return out
+    return (out[0][0], out[1][0]) if return_paths else out[0]
+
+
 __all__ = ["adj_product_graph", "adj_sum_graph", "add_self_loop", "remove_self_loop", "remove_edges", "reorder_graph", "add_reverse_edges", "to_simple", "to_bidirected",
            "node_subgraph", "edge_subgraph", "in_subgraph", "out_subgraph", "khop_in_subgraph", "khop_out_subgraph", "batch", "unbatch", "from_scipy", "bipartite_from_scipy",
-           "adj_external", "knn", "knn_graph", "segmented_knn_graph", "sort_csr_by_tag", "sort_csc_by_tag", "DGLWarning"]
+           "adj_external", "knn", "knn_graph", "segmented_knn_graph", "sort_csr_by_tag", "sort_csc_by_tag", "shortest_dist", "DGLWarning"]

@@ -1188,6 +1188,65 @@ int dgla_traverse(int mode, const dgla_csr* csr, const dgla_csr* opposite, const
 int dgla_traverse_host(int mode, const dgla_csr* csr, const dgla_csr* opposite, const void* sources, int64_t num_sources,
                        void* ids, int64_t* sections, int64_t* num_ids, int64_t* num_sections);
 
+/* ---- Shortest distances and paths (csrc/shortest_dist.hip) ------------------------------------------------
+ * dgl.shortest_dist: the hop distance from every source to every node and one shortest path per pair, what the
+ * SpatialEncoder / PathEncoder of a graph transformer consume.  The reference has no GPU form:
+ * python/dgl/transforms/functional.py copies the graph to the host, runs scipy's shortest_path / dijkstra, rebuilds every
+ * path in a Python double loop over the pairs and asks edge_ids for the edges.  The rule (the pieces device and host
+ * share: csrc/shortest_dist_step.h):
+ *
+ * Input.  The in-edge CSR of a homogeneous graph with n nodes (indptr[n + 1], indices[nnz] = the source of every
+ * in-edge, data[nnz] = the edge-id map or NULL; int32 or int64 ids) and a list of S source ids.
+ *
+ * dist.  dist[s][v] is the number of edges on a shortest directed path from sources[s] to v: 0 for the source itself,
+ * -1 when v cannot be reached.  int64 whatever the id type, as in the reference.
+ *
+ * Predecessor edge.  For every reachable v != sources[s], among the in-edges (u -> v) with dist[s][u] == dist[s][v] - 1
+ * the one with the smallest edge id.  A self-loop never qualifies; among parallel edges the smallest id wins.  The
+ * minimum is a commutative reduction: it depends neither on thread order nor on the order of the CSR's entries.
+ *
+ * path.  paths[s][v][0 .. d) holds the predecessor edges walked back from v, stored front to back, so that
+ * paths[s][v][d - 1] enters v; paths[s][v][d .. L) is -1.  L is the largest entry of dist, 0 without a reachable pair
+ * (paths then has no element).  int64.
+ *
+ * Difference from the reference: it takes whichever predecessor scipy's queue found and whichever parallel edge
+ * edge_ids returns.  Its paths are shortest too and have the same lengths; where a pair has several shortest paths the
+ * two may pick different ones.
+ *
+ * An entry of `indices` outside [0, n) is ignored and nothing is read or written through it.  Integers only: device,
+ * host twin and any model compare exactly.
+ *
+ * Kernels (three, each launched once): a bit-parallel multi-source BFS (64 sources share one 64-bit word per node, one
+ * workgroup of 256 threads owns a word and runs its whole search, so there is no grid-wide synchronisation and no host
+ * round trip per level; the frontier / next / seen masks live in LDS up to 6400 nodes, 153 600 bytes, and in the
+ * workspace above), the predecessor table (one lane per pair), and the paths (walked back into an LDS tile and written as
+ * one coalesced stream).  ONE source means one word and therefore one workgroup: a root search over a graph of millions
+ * of nodes is out of scope, dgla_traverse (bfs_nodes_generator) remains the scalable single-source tool.
+ *
+ * dgla_shortest_dist_workspace_bytes: with W = ceil(S / 64) words and b = idtype_bits / 8, every piece rounded up to 256
+ *   bytes: W * 3 * 8 n (the masks of the searches) + 2 b * S * n (the predecessor table) + 8 (the longest distance).  0
+ *   for another id width, num_nodes <= 0 or num_sources <= 0.
+ * dgla_shortest_dist: the CSR's arrays, sources, dist, paths and the workspace are device memory, *max_len is HOST
+ *   memory.  sources == NULL stands for every node in order (num_sources must be n).  L is only known after the search,
+ *   so paths take a second call, the idiom of the seed-row samplers:
+ *     paths == NULL: writes dist[S][n].  With max_len != NULL it also builds the predecessor table in the caller's
+ *       workspace and reports L in *max_len, the one read-back of 8 bytes.
+ *     paths != NULL: writes paths[S][n][*max_len] from dist and the workspace of that earlier call, which is required
+ *       here; *max_len is what that call reported.
+ *   max_lds_nodes > 0 lowers the node count up to which the masks live in LDS (it cannot raise it); results do not
+ *   depend on it.  workspace == NULL: stream-ordered scratch serves the call; one that is given but too small is refused
+ *   with the bytes required.  Runs on the caller's stream.
+ * dgla_shortest_dist_host: the same rule run by the CPU on HOST pointers (a queue BFS per source, then the shared
+ *   pieces), no workspace and no stream; with paths != NULL it computes everything again and *max_len must be L.
+ * Both fail with -1 and a message that names the entry point, before any launch, for a NULL csr, an invalid csr
+ *   (negative sizes, not square, NULL indptr / indices), an id width other than 32 / 64, a NULL dist, paths without
+ *   max_len, and a source outside [0, n) (the device form reads the list back to check it). */
+size_t dgla_shortest_dist_workspace_bytes(int idtype_bits, int64_t num_nodes, int64_t num_sources);
+int dgla_shortest_dist(const dgla_csr* csr, const void* sources, int64_t num_sources, int64_t* dist, int64_t* paths,
+                       int64_t* max_len, void* workspace, size_t workspace_bytes, int64_t max_lds_nodes, void* hip_stream);
+int dgla_shortest_dist_host(const dgla_csr* csr, const void* sources, int64_t num_sources, int64_t* dist, int64_t* paths,
+                            int64_t* max_len);
+
 /* ---- Top-k neighbour selection (csrc/topk.hip) ------------------------------------------------------------
  * dgl.sampling.select_topk: for every seed the k in- or out-edges with the largest (or smallest) weight.  The reference
  * has no GPU form: python/dgl/sampling/neighbor.py asserts a CPU graph and sorts every row with std::sort
