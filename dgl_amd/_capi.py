@@ -1365,6 +1365,54 @@ def shortest_dist_host(csr, sources, return_paths):
     return _shortest_dist("shortest_dist_host", False, csr, sources, return_paths, None, None)
 
 
+def graphormer_bias_workspace_bytes(num_pairs, path_len, max_len, num_edges, num_heads, spatial_rows):
+    """The bytes of the workspace of :func:`graphormer_bias_backward` (dgla_graphormer_bias_workspace_bytes; host query);
+    `spatial_rows` is 0 for a call without a spatial table."""
+    return int(LIB.dgla_graphormer_bias_workspace_bytes(int(num_pairs), int(path_len), int(max_len), int(num_edges),
+                                                        int(num_heads), int(spatial_rows)))
+
+
+def _gbias_head(dist, paths):
+    """The arguments the two Graphormer bias calls start with: `dist` (P,) and `paths` (P, Lp) of one id width."""
+    if _idbits(dist) != _idbits(paths):
+        raise _lib.DGLAMDError("graphormer_bias: dist and paths must share one id width, got %s and %s" % (dist.dtype, paths.dtype))
+    if dist.dim() != 1 or paths.dim() != 2 or paths.shape[0] != dist.shape[0]:
+        raise _lib.DGLAMDError("graphormer_bias: paths must be (pairs, path length) with one row per entry of dist")
+    return _idbits(dist), dist.shape[0], paths.shape[1]
+
+
+def graphormer_bias_forward(dist, paths, table, spatial, max_len, num_heads):
+    """``out`` (P, H) of the rule "Graphormer attention bias" of include/dgl_amd.h (dgla_graphormer_bias_forward): one
+    launch, nothing read back.  `table` is the projected table (E, max_len * H), `spatial` (max_dist + 2, H) or None; all
+    tensors contiguous on one GPU."""
+    bits, P, Lp = _gbias_head(dist, paths)
+    _all_on(True, "graphormer_bias", dist, paths, table, spatial)
+    out = torch.empty((P, int(num_heads)), dtype=table.dtype, device=table.device)
+    check_call(LIB.dgla_graphormer_bias_forward(
+        bits, _DTYPES.get(table.dtype, -1), _ptr(dist), _ptr(paths), P, Lp, _ptr(table), table.shape[0], int(max_len),
+        int(num_heads), _ptr(spatial), 0 if spatial is None else spatial.shape[0], _ptr(out), _stream(table)))
+    return out
+
+
+def graphormer_bias_backward(dist, paths, grad_out, num_edges, max_len, spatial_rows, want_table=True, want_spatial=True,
+                             padding_idx=None, ws=None):
+    """``(grad_table, grad_spatial)`` of :func:`graphormer_bias_forward` (dgla_graphormer_bias_backward), each None when
+    not wanted: deterministic sums over the inverted path index and the distance bins.  An id >= `num_edges` in `paths`
+    raises, the one read-back (4 bytes).  `ws` (uint8, :func:`graphormer_bias_workspace_bytes`) is the optional
+    workspace."""
+    bits, P, Lp = _gbias_head(dist, paths)
+    _all_on(True, "graphormer_bias", dist, paths, grad_out, ws)
+    H = grad_out.shape[1]
+    new = lambda rows, cols: torch.empty((rows, cols), dtype=grad_out.dtype, device=grad_out.device)
+    gt = new(int(num_edges), int(max_len) * H) if want_table else None
+    gs = new(int(spatial_rows), H) if want_spatial else None
+    check_call(LIB.dgla_graphormer_bias_backward(
+        bits, _DTYPES.get(grad_out.dtype, -1), _ptr(dist), _ptr(paths), P, Lp, int(num_edges), int(max_len), H,
+        int(spatial_rows) if want_spatial else 0, _ptr(grad_out), _ptr(gt), _ptr(gs),
+        -1 if padding_idx is None else int(padding_idx), *_ws(ws), _stream(grad_out)))
+    return gt, gs
+
+
 def _seed_csr(call, args, seeds, capacity=None, tail=(), into=None, pass_capacity=False):
     """``(indptr, nbr, eids)``, a CSR over `seeds`, from an entry point of the form ``call(*args, out_indptr, out_nbr,
     out_eids, *tail)``.  With a `capacity` the outputs are allocated at it and the entry is called once; ``None`` asks

@@ -362,6 +362,15 @@ LIB.dgla_shortest_dist.restype = c_int
 LIB.dgla_shortest_dist.argtypes = _SHORTEST + [c_void_p, c_size_t, c_int64, c_void_p]
 LIB.dgla_shortest_dist_host.restype = c_int
 LIB.dgla_shortest_dist_host.argtypes = _SHORTEST
+# the Graphormer bias unit: idtype bits, dtype, dist, paths, num_pairs, path_len
+_GBIAS = [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64]
+LIB.dgla_graphormer_bias_workspace_bytes.restype = c_size_t
+LIB.dgla_graphormer_bias_workspace_bytes.argtypes = [c_int64] * 6
+LIB.dgla_graphormer_bias_forward.restype = c_int
+LIB.dgla_graphormer_bias_forward.argtypes = _GBIAS + [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+LIB.dgla_graphormer_bias_backward.restype = c_int
+LIB.dgla_graphormer_bias_backward.argtypes = _GBIAS + [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                       c_void_p, c_size_t, c_void_p]
 # the top-k selection unit: csr, weight, weight dtype, seeds, num_seeds, k, ascending, out_indptr, out_nbr, out_eids
 _TOPK = [P(CSR), c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]
 LIB.dgla_select_topk_max_picks.restype = c_int

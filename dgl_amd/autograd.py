@@ -406,6 +406,32 @@ class GATAttentionTrain(torch.autograd.Function):
         return None, d_ft, d_el, d_er, None, None, None, None
 
 
+class GraphormerBiasGather(torch.autograd.Function):
+    """The gather half of the Graphormer bias (csrc/graphormer_bias.hip): ``out`` (P, H) from `dist` (P,), `paths`
+    (P, Lp), the projected table (E, max_len * H) and the optional spatial table.  The backward inverts the path index
+    once and sums without atomics; `dist` and `paths` are all it keeps."""
+
+    @staticmethod
+    def forward(ctx, dist, paths, table, spatial, max_len, heads, padding_idx):
+        from . import _capi
+
+        ctx.save_for_backward(dist, paths)
+        ctx.shape = table.shape[0], max_len, None if spatial is None else spatial.shape[0], padding_idx
+        return _capi.graphormer_bias_forward(dist, paths, table.contiguous(), None if spatial is None else spatial.contiguous(),
+                                             max_len, heads)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _capi
+
+        dist, paths = ctx.saved_tensors
+        num_edges, max_len, spatial_rows, padding_idx = ctx.shape
+        d_table, d_spatial = _capi.graphormer_bias_backward(
+            dist, paths, dout.contiguous(), num_edges, max_len, spatial_rows or 0, ctx.needs_input_grad[2],
+            spatial_rows is not None and ctx.needs_input_grad[3], padding_idx)
+        return None, None, d_table, d_spatial, None, None, None
+
+
 def _nd(t):
     from . import _ffi
     return None if t is None else _ffi.NDArray(t)

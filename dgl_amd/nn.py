@@ -15,7 +15,7 @@ from . import edge_order as _eo
 from . import function as fn
 from .ops import edge_softmax
 
-__all__ = ["functional", "gat_attention", "GATAttention"]
+__all__ = ["functional", "gat_attention", "GATAttention", "GraphormerBias"]
 
 
 class functional:  # noqa: N801  (a namespace: python/dgl/nn/functional/__init__.py exports exactly this)
@@ -78,3 +78,41 @@ class GATAttention(torch.nn.Module):
 
     def extra_repr(self):
         return "negative_slope=%g, attn_drop=%g" % (self.negative_slope, self.attn_drop)
+
+
+class _EmbeddingTable(torch.nn.Module):
+    """One ``embedding_table``, the only parameter of the reference's SpatialEncoder and of its PathEncoder: a state dict
+    of either loads into it unchanged."""
+
+    def __init__(self, rows, cols, padding_idx=None):
+        super().__init__()
+        self.embedding_table = torch.nn.Embedding(rows, cols, padding_idx=padding_idx)
+
+
+class GraphormerBias(torch.nn.Module):
+    """The attention bias of a Graphormer layer: ``SpatialEncoder(max_dist, num_heads)`` plus
+    ``PathEncoder(max_len, feat_dim, num_heads)`` (python/dgl/nn/pytorch/gt) as ONE operator,
+    :func:`dgl_amd.ops.graphormer_bias`.  The tables sit under the reference's names and shapes,
+    ``spatial_encoder.embedding_table.weight`` (max_dist + 2, num_heads; row 0 is the padding row) and
+    ``path_encoder.embedding_table.weight`` (max_len * num_heads, feat_dim), so
+    ``m.spatial_encoder.load_state_dict(spatial.state_dict())`` and ``m.path_encoder.load_state_dict(path.state_dict())``
+    carry trained encoders over.
+
+    ``forward(dist, paths, edge_feat)``: `dist` of any shape and `paths` of that shape plus the path axis, as
+    ``shortest_dist(g, return_paths=True)`` returns them (callers slice per-graph blocks out of the batched result with
+    torch indexing), `edge_feat` (E, feat_dim) indexed by the ids in `paths`.  Returns ``(*dist.shape, num_heads)``."""
+
+    def __init__(self, max_dist, max_len, feat_dim, num_heads=1):
+        super().__init__()
+        self.max_dist, self.max_len, self.feat_dim, self.num_heads = int(max_dist), int(max_len), int(feat_dim), int(num_heads)
+        self.spatial_encoder = _EmbeddingTable(self.max_dist + 2, self.num_heads, padding_idx=0)
+        self.path_encoder = _EmbeddingTable(self.max_len * self.num_heads, self.feat_dim)
+
+    def forward(self, dist, paths, edge_feat, fused=None):
+        from . import ops
+
+        return ops.graphormer_bias(dist, paths, edge_feat, self.path_encoder.embedding_table.weight,
+                                   self.spatial_encoder.embedding_table.weight, max_len=self.max_len, padding_idx=0, fused=fused)
+
+    def extra_repr(self):
+        return "max_dist=%d, max_len=%d, feat_dim=%d, num_heads=%d" % (self.max_dist, self.max_len, self.feat_dim, self.num_heads)

@@ -13,7 +13,8 @@ from . import autograd as _F
 from . import _capi
 from ._lib import DGLAMDError
 
-__all__ = ["gspmm", "gsddmm", "edge_softmax", "copy_u", "copy_v", "copy_e", "gat_attention", "gat_attention_applies"]
+__all__ = ["gspmm", "gsddmm", "edge_softmax", "copy_u", "copy_v", "copy_e", "gat_attention", "gat_attention_applies",
+           "graphormer_bias", "graphormer_bias_gather"]
 
 
 def _reshape_for_broadcast(op, lhs, rhs):
@@ -226,6 +227,117 @@ def gat_attention(graph, ft, el, er, negative_slope=0.2, attn_drop=0.0, training
     if not 0 <= seed < 2 ** 63:
         raise DGLAMDError("gat_attention: seed must be an integer in [0, 2**63)")
     return _F.gat_attention(graph._graph, ft, el, er, float(negative_slope), p, seed, bool(get_attention))
+
+
+# ---- Graphormer attention bias: spatial + path encoding as one operator ------------------------------
+_GBIAS_MAX_HEADS, _GBIAS_MAX_LEN = 256, 32
+
+
+def _gbias_check(dist, paths, floats, heads, max_len, spatial_weight):
+    """The refusals of the Graphormer bias, by name, before anything is launched."""
+    who = "graphormer_bias: "
+    ints = (torch.int32, torch.int64)
+    if dist.dtype not in ints or paths.dtype not in ints or dist.dtype != paths.dtype:
+        raise DGLAMDError(who + "dist and paths must share one id width (both int64 or both int32), got %s and %s"
+                          % (dist.dtype, paths.dtype))
+    if paths.dim() != dist.dim() + 1 or paths.shape[:-1] != dist.shape:
+        raise DGLAMDError(who + "paths must have the shape of dist plus one axis, got %s for dist %s"
+                          % (tuple(paths.shape), tuple(dist.shape)))
+    if len({t.dtype for t in floats}) != 1:
+        raise DGLAMDError(who + "operand dtypes differ: %s" % ", ".join(str(t.dtype) for t in floats))
+    if not 1 <= heads <= _GBIAS_MAX_HEADS:
+        raise DGLAMDError(who + "%d heads: the kernels take 1 to %d" % (heads, _GBIAS_MAX_HEADS))
+    if not 1 <= max_len <= _GBIAS_MAX_LEN:
+        raise DGLAMDError(who + "max_len %d: the kernels take 1 to %d" % (max_len, _GBIAS_MAX_LEN))
+    if spatial_weight is not None and (spatial_weight.dim() != 2 or spatial_weight.shape[0] < 2):
+        raise DGLAMDError(who + "spatial_weight must be (max_dist + 2, H)")
+
+
+def _gbias_route(fused, tensors):
+    """True: the kernels.  CPU tensors take the torch composition unless the kernels were asked for by name."""
+    on_gpu = all(t.is_cuda for t in tensors)
+    if fused and not on_gpu:
+        raise DGLAMDError("graphormer_bias: dgl_amd kernels run on a ROCm GPU (no CPU fallback); fused=True needs GPU tensors")
+    return on_gpu if fused is None else bool(fused)
+
+
+def _gbias_finish(path_sum, dist, spatial_weight, max_len, padding_idx, dtype):
+    """The tail both compositions share: divide by the clamped distance, add the spatial row, round once."""
+    out = path_sum / dist.clamp(1, max_len).unsqueeze(-1).to(torch.float32)
+    if spatial_weight is not None:
+        bins = dist.clamp(-1, spatial_weight.shape[0] - 2).long() + 1
+        out = out + torch.nn.functional.embedding(bins, spatial_weight, padding_idx=padding_idx).to(torch.float32)
+    return out.to(dtype)
+
+
+def graphormer_bias_gather(dist, paths, T, spatial_weight=None, *, max_len, padding_idx=None, fused=None):
+    """The gather half of :func:`graphormer_bias`: `T` is the projected table ``edge_feat @ path_weight.T``, shape
+    (E, max_len * H).  Differentiable in `T` and `spatial_weight`; the gradients are deterministic sums (no atomics).
+    An edge id >= E in `paths` is the caller's error in the forward (the pair misses the term) and raises in the
+    backward."""
+    max_len = int(max_len)
+    if T.dim() != 2 or max_len < 1 or T.shape[1] % max_len:
+        raise DGLAMDError("graphormer_bias: T must be (E, max_len * H)")
+    heads = T.shape[1] // max_len
+    floats = (T,) if spatial_weight is None else (T, spatial_weight)
+    _gbias_check(dist, paths, floats, heads, max_len, spatial_weight)
+    if spatial_weight is not None and spatial_weight.shape[1] != heads:
+        raise DGLAMDError("graphormer_bias: spatial_weight has %d heads, T has %d" % (spatial_weight.shape[1], heads))
+    if _gbias_route(fused, (dist, paths) + floats):
+        out = _F.GraphormerBiasGather.apply(dist.reshape(-1).contiguous(), paths.reshape(-1, paths.shape[-1]).contiguous(),
+                                            T, spatial_weight, max_len, heads, padding_idx)
+        return out.reshape(tuple(dist.shape) + (heads,))
+    lc, num_edges = min(paths.shape[-1], max_len), T.shape[0]
+    rows = torch.cat([T.reshape(num_edges, max_len, heads), T.new_zeros(1, max_len, heads)])      # row E: the zero row
+    ids = paths[..., :lc].long()
+    ids = torch.where(ids < 0, torch.full_like(ids, num_edges), ids)
+    acc = torch.zeros(tuple(dist.shape) + (heads,), dtype=torch.float32, device=T.device)
+    for l in range(lc):                                                                           # the fixed order of l
+        acc = acc + rows[ids[..., l], l].to(torch.float32)
+    return _gbias_finish(acc, dist, spatial_weight, max_len, padding_idx, T.dtype)
+
+
+def graphormer_bias(dist, paths, edge_feat, path_weight, spatial_weight=None, *, max_len=None, padding_idx=None, fused=None):
+    """The attention bias of a Graphormer layer, SpatialEncoder + PathEncoder (python/dgl/nn/pytorch/gt) as one operator::
+
+        out[p, h] = S[clamp(dist[p], -1, max_dist) + 1, h]
+                  + (sum_{l < Lc, paths[p, l] >= 0} T[paths[p, l], l * H + h]) / clamp(dist[p], 1, max_len)
+        T = edge_feat @ path_weight.T,  Lc = min(paths.shape[-1], max_len)
+
+    `dist` (any shape) and `paths` (that shape + (Lp,)) are what ``shortest_dist(g, return_paths=True)`` returns, both
+    int64 or both int32; ids index the rows of `edge_feat` (E, d).  `path_weight` is ``PathEncoder.embedding_table.weight``
+    (max_len * H, d), `spatial_weight` ``SpatialEncoder.embedding_table.weight`` (max_dist + 2, H) or None.  `max_len`
+    defaults to ``path_weight.shape[0] // H`` when a spatial table fixes H and is required otherwise.  ``padding_idx=0``
+    zeroes the gradient of that spatial row, as ``nn.Embedding(padding_idx=0)`` does.  Returns ``(*dist.shape, H)``.
+
+    On a GPU (``fused=None`` or True) the projection runs on :func:`segment_mm` with one segment and the gather, its
+    backward to T and the backward to S on the kernels of csrc/graphormer_bias.hip: the (pairs, L, d) tensor of the
+    reference is never built.  ``fused=False``, and CPU tensors, take the reference's torch composition."""
+    if path_weight.dim() != 2 or edge_feat.dim() != 2 or edge_feat.shape[1] != path_weight.shape[1]:
+        raise DGLAMDError("graphormer_bias: edge_feat must be (E, d) and path_weight (max_len * H, d)")
+    if max_len is None:
+        if spatial_weight is None:
+            raise DGLAMDError("graphormer_bias: max_len is required when no spatial table fixes the head count")
+        max_len = path_weight.shape[0] // max(int(spatial_weight.shape[-1]), 1)
+    max_len = int(max_len)
+    if max_len < 1 or path_weight.shape[0] % max_len:
+        raise DGLAMDError("graphormer_bias: path_weight has %d rows, no multiple of max_len %d" % (path_weight.shape[0], max_len))
+    heads = path_weight.shape[0] // max_len
+    floats = (edge_feat, path_weight) + (() if spatial_weight is None else (spatial_weight,))
+    _gbias_check(dist, paths, floats, heads, max_len, spatial_weight)
+    if spatial_weight is not None and spatial_weight.shape[1] != heads:
+        raise DGLAMDError("graphormer_bias: spatial_weight has %d heads, path_weight has %d" % (spatial_weight.shape[1], heads))
+    if _gbias_route(fused, (dist, paths) + floats):
+        seg = torch.tensor([edge_feat.shape[0]], dtype=torch.int64)
+        table = segment_mm(edge_feat, path_weight.t().unsqueeze(0), seg)
+        return graphormer_bias_gather(dist, paths, table, spatial_weight, max_len=max_len, padding_idx=padding_idx, fused=True)
+    lc, num_edges = min(paths.shape[-1], max_len), edge_feat.shape[0]
+    ids = paths[..., :lc].long()
+    ids = torch.where(ids < 0, torch.full_like(ids, num_edges), ids)
+    path_data = torch.cat([edge_feat, edge_feat.new_zeros(1, edge_feat.shape[1])])[ids]           # (..., Lc, d)
+    weight = path_weight.reshape(max_len, heads, -1)[:lc]
+    acc = torch.einsum("...ld,lhd->...h", path_data, weight).to(torch.float32)
+    return _gbias_finish(acc, dist, spatial_weight, max_len, padding_idx, edge_feat.dtype)
 
 
 # ---- generated aliases -----------------------------------------------------------------

@@ -1247,6 +1247,50 @@ int dgla_shortest_dist(const dgla_csr* csr, const void* sources, int64_t num_sou
 int dgla_shortest_dist_host(const dgla_csr* csr, const void* sources, int64_t num_sources, int64_t* dist, int64_t* paths,
                             int64_t* max_len);
 
+/* ---- Graphormer attention bias (csrc/graphormer_bias.hip) -------------------------------------------------
+ * The SpatialEncoder and the PathEncoder of a graph transformer (python/dgl/nn/pytorch/gt/spatial_encoder.py,
+ * path_encoder.py) as one gather over what dgla_shortest_dist emits.  The reference composes torch operators and
+ * writes a (pairs, L, d) tensor to make a (pairs, H) bias.  The rule, for P pairs (the flattened leading shape of dist):
+ *
+ *   out[p][h] = S[clamp(dist[p], -1, max_dist) + 1][h]                              (left out when S is NULL)
+ *             + ( sum over l < Lc with paths[p][l] >= 0 of T[paths[p][l]][l * H + h] ) / clamp(dist[p], 1, max_len)
+ *
+ * T is the projected table, (E, max_len * H): edge_feat (E, d) times the transposed path table (max_len * H, d), which
+ * the caller computes with dgla_segment_mm.  S is the spatial table, (max_dist + 2, H); Lc = min(path_len, max_len).  A
+ * -1 id is the zero row, ids at positions >= max_len are cut off, the divisor is the clamped distance and not the
+ * number of terms, an unreachable pair gives S[0].  The sum runs in the order l = 0, 1, ..., Lc - 1 in fp32 for every
+ * operand type (float32, float16, bfloat16; dtype codes as dgla_tensor) and is rounded once at the store.
+ *
+ * Backward.  dT[e][l * H + h] = the sum over the pairs p with paths[p][l] == e of g[p][h] / clamp(dist[p], 1, max_len),
+ * in ascending p; dS[r][h] = the sum of g[p][h] over the pairs whose clamped distance + 1 is r, row padding_idx zeroed
+ * (padding_idx < 0: none).  fp32 sums of a fixed shape, no floating-point atomics: the same bits on every run.
+ *
+ * dgla_graphormer_bias_workspace_bytes: the workspace of the backward, every piece rounded up to 256 bytes; with
+ *   n = P * Lc path entries, R = E * Lc + 1 index rows and b = 4 when n and R fit int32, else 8: 4 (the flag) + 4 b n (the
+ *   keys, the pairs, and the sort's two outputs) + b (R + 1) (indptr) + the workspace of the library's COO -> CSR sort for
+ *   n entries + 4 * W * spatial_rows * H (W <= 1024 partial tables of the backward to S).  0 for a shape that is refused.
+ * dgla_graphormer_bias_forward: one launch, no workspace, nothing read back or cleared, so the call can be captured.
+ *   dist[P] and paths[P][path_len] share one id width.  An id >= E is the CALLER'S ERROR here: nothing is read through it
+ *   and the pair misses that term, but no error is raised, because that would cost a read-back.
+ * dgla_graphormer_bias_backward: grad_table (E, max_len * H) and grad_spatial (spatial_rows, H) may each be NULL; every
+ *   element of a gradient that is asked for is written, so neither needs a fill.  The path index is inverted once per
+ *   call into the workspace.  An id >= E is refused here: a flag set on the device, the one read-back of 4 bytes.
+ *   workspace == NULL: stream-ordered scratch serves the call; one that is given but too small is refused with the bytes
+ *   required.
+ * All pointers but the workspace sizes are device memory; both calls run on the caller's stream.  They fail with -1 and a
+ *   message prefixed "graphormer_bias:", before any launch, for an id width other than 32 / 64, an operand type other
+ *   than the three, negative sizes, more than 256 heads, max_len outside [1, 32], a spatial table that does not fit the
+ *   workgroup's LDS (forward), and NULL arrays.  P == 0 writes nothing (forward) or zeros (backward) without a launch. */
+size_t dgla_graphormer_bias_workspace_bytes(int64_t num_pairs, int64_t path_len, int64_t max_len, int64_t num_edges,
+                                            int64_t num_heads, int64_t spatial_rows);
+int dgla_graphormer_bias_forward(int idtype_bits, int dtype, const void* dist, const void* paths, int64_t num_pairs,
+                                 int64_t path_len, const void* table, int64_t num_edges, int64_t max_len, int64_t num_heads,
+                                 const void* spatial, int64_t spatial_rows, void* out, void* hip_stream);
+int dgla_graphormer_bias_backward(int idtype_bits, int dtype, const void* dist, const void* paths, int64_t num_pairs,
+                                  int64_t path_len, int64_t num_edges, int64_t max_len, int64_t num_heads,
+                                  int64_t spatial_rows, const void* grad_out, void* grad_table, void* grad_spatial,
+                                  int64_t padding_idx, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- Top-k neighbour selection (csrc/topk.hip) ------------------------------------------------------------
  * dgl.sampling.select_topk: for every seed the k in- or out-edges with the largest (or smallest) weight.  The reference
  * has no GPU form: python/dgl/sampling/neighbor.py asserts a CPU graph and sorts every row with std::sort
