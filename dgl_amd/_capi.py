@@ -1413,6 +1413,58 @@ def graphormer_bias_backward(dist, paths, grad_out, num_edges, max_len, spatial_
     return gt, gs
 
 
+def biased_attention_workspace_bytes(B, N, H):
+    """The bytes of the workspace of :func:`biased_attention_backward` (dgla_biased_attention_workspace_bytes)."""
+    return int(LIB.dgla_biased_attention_workspace_bytes(int(B), int(N), int(H)))
+
+
+def _battn_head(q, k, v, bias, mask):
+    """The arguments both biased attention calls start with; q, k, v (B, N, H, D), bias (B, N, N, H) or None, mask
+    (B, N, N) uint8 / bool or None, all contiguous on one GPU (checked by ops.biased_attention)."""
+    _all_on(True, "biased_attention", q, k, v, bias, mask)
+    for t in (q, k, v, bias, mask):
+        if t is not None and not t.is_contiguous():
+            raise _lib.DGLAMDError("biased_attention: operands must be contiguous")
+    return [_DTYPES.get(q.dtype, -1), _ptr(q), _ptr(k), _ptr(v), _ptr(bias), _ptr(mask)]
+
+
+def biased_attention_forward(q, k, v, bias, mask, scale, drop, seed, into=None):
+    """``(out, lse)`` of the rule "Biased attention" of include/dgl_amd.h (dgla_biased_attention_forward): one launch,
+    nothing read back.  `into` = (out, lse) gives the two preallocated: out (B, N, H, D) and lse (2, B, H, N) fp32 (the
+    row log-sum-exp and its low-order part)."""
+    head = _battn_head(q, k, v, bias, mask)
+    B, N, H, D = q.shape
+    out, lse = into or (torch.empty_like(q), torch.empty((2, B, H, N), dtype=torch.float32, device=q.device))
+    check_call(LIB.dgla_biased_attention_forward(*head, B, N, H, D, float(scale), float(drop), _u64(seed), _ptr(out), _ptr(lse),
+                                                 _stream(q)))
+    return out, lse
+
+
+def biased_attention_backward(q, k, v, bias, mask, fwd_out, lse, dout, scale, drop, seed, want_bias=True, dbias=None, ws=None):
+    """``(dq, dk, dv, dbias)`` of :func:`biased_attention_forward` for the same (drop, seed)
+    (dgla_biased_attention_backward): deterministic, no atomics; ``dbias`` is None unless a bias was given and
+    `want_bias`.  `dbias` (B, N, N, H) and `ws` (uint8, :func:`biased_attention_workspace_bytes`) may be given."""
+    head = _battn_head(q, k, v, bias, mask)
+    _all_on(True, "biased_attention", fwd_out, lse, dout, dbias, ws)
+    B, N, H, D = q.shape
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    if bias is None or not want_bias:
+        dbias = None
+    elif dbias is None:
+        dbias = torch.empty_like(bias)
+    check_call(LIB.dgla_biased_attention_backward(*head, _ptr(fwd_out), _ptr(lse), _ptr(dout), B, N, H, D, float(scale), float(drop),
+                                                  _u64(seed), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dbias), *_ws(ws), _stream(q)))
+    return dq, dk, dv, dbias
+
+
+def biased_attention_dropout_mask_host(seed, drop, B, H, N):
+    """The keep bits of :func:`biased_attention_forward`'s dropout as a (B, H, N, N) uint8 CPU tensor, from the same
+    definition the kernels evaluate (dgla_biased_attention_dropout_mask_host; needs no GPU)."""
+    keep = torch.empty((int(B), int(H), int(N), int(N)), dtype=torch.uint8)
+    check_call(LIB.dgla_biased_attention_dropout_mask_host(_u64(seed), float(drop), int(B), int(H), int(N), keep.data_ptr()))
+    return keep
+
+
 def _seed_csr(call, args, seeds, capacity=None, tail=(), into=None, pass_capacity=False):
     """``(indptr, nbr, eids)``, a CSR over `seeds`, from an entry point of the form ``call(*args, out_indptr, out_nbr,
     out_eids, *tail)``.  With a `capacity` the outputs are allocated at it and the entry is called once; ``None`` asks

@@ -371,6 +371,17 @@ LIB.dgla_graphormer_bias_forward.argtypes = _GBIAS + [c_void_p, c_int64, c_int64
 LIB.dgla_graphormer_bias_backward.restype = c_int
 LIB.dgla_graphormer_bias_backward.argtypes = _GBIAS + [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                                        c_void_p, c_size_t, c_void_p]
+# the biased attention unit: dtype, q, k, v, bias, mask
+_BATTN = [c_int] + [c_void_p] * 5
+LIB.dgla_biased_attention_workspace_bytes.restype = c_size_t
+LIB.dgla_biased_attention_workspace_bytes.argtypes = [c_int64] * 3
+LIB.dgla_biased_attention_forward.restype = c_int
+LIB.dgla_biased_attention_forward.argtypes = _BATTN + [c_int64] * 4 + [ctypes.c_float, ctypes.c_float, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]
+LIB.dgla_biased_attention_backward.restype = c_int
+LIB.dgla_biased_attention_backward.argtypes = (_BATTN + [c_void_p] * 3 + [c_int64] * 4 + [ctypes.c_float, ctypes.c_float, ctypes.c_uint64] +
+                                               [c_void_p] * 5 + [c_size_t, c_void_p])
+LIB.dgla_biased_attention_dropout_mask_host.restype = c_int
+LIB.dgla_biased_attention_dropout_mask_host.argtypes = [ctypes.c_uint64, ctypes.c_float, c_int64, c_int64, c_int64, c_void_p]
 # the top-k selection unit: csr, weight, weight dtype, seeds, num_seeds, k, ascending, out_indptr, out_nbr, out_eids
 _TOPK = [P(CSR), c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]
 LIB.dgla_select_topk_max_picks.restype = c_int

@@ -432,6 +432,32 @@ class GraphormerBiasGather(torch.autograd.Function):
         return None, None, d_table, d_spatial, None, None, None
 
 
+class BiasedAttention(torch.autograd.Function):
+    """Biased multi-head attention (csrc/biased_attention.hip): ``out`` (B, N, H, D) from q, k, v, the bias
+    (B, N, N, H) and the mask (B, N, N).  The forward keeps the row log-sum-exp; the backward recomputes the attention
+    weights from it (and the dropout mask from the seed), so no (B, H, N, N) tensor is ever stored."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, mask, scale, drop, seed):
+        from . import _capi
+
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        out, lse = _capi.biased_attention_forward(q, k, v, bias, mask, scale, drop, seed)
+        ctx.save_for_backward(q, k, v, bias, mask, out, lse)
+        ctx.meta = scale, drop, seed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _capi
+
+        q, k, v, bias, mask, out, lse = ctx.saved_tensors
+        dq, dk, dv, dbias = _capi.biased_attention_backward(q, k, v, bias, mask, out, lse, dout.contiguous(), *ctx.meta,
+                                                            want_bias=bias is not None and ctx.needs_input_grad[3])
+        return dq, dk, dv, dbias, None, None, None, None
+
+
 def _nd(t):
     from . import _ffi
     return None if t is None else _ffi.NDArray(t)

@@ -15,7 +15,7 @@ from . import edge_order as _eo
 from . import function as fn
 from .ops import edge_softmax
 
-__all__ = ["functional", "gat_attention", "GATAttention", "GraphormerBias"]
+__all__ = ["functional", "gat_attention", "GATAttention", "GraphormerBias", "BiasedMHA"]
 
 
 class functional:  # noqa: N801  (a namespace: python/dgl/nn/functional/__init__.py exports exactly this)
@@ -116,3 +116,61 @@ class GraphormerBias(torch.nn.Module):
 
     def extra_repr(self):
         return "max_dist=%d, max_len=%d, feat_dim=%d, num_heads=%d" % (self.max_dist, self.max_len, self.feat_dim, self.num_heads)
+
+
+class BiasedMHA(torch.nn.Module):
+    """Dense multi-head attention with a graph attention bias, the reference's ``BiasedMHA(feat_size, num_heads,
+    bias=True, attn_bias_type="add", attn_drop=0.1)`` (python/dgl/nn/pytorch/gt/biased_mha.py) with its attention on
+    :func:`dgl_amd.ops.biased_attention`.  ``q_proj``, ``k_proj``, ``v_proj`` and ``out_proj`` carry the reference's
+    names, shapes and initialisation, so its state dict loads unchanged; they stay ``nn.Linear`` and the operator takes
+    the (B, N, H, D) views of their outputs without a copy.
+
+    ``forward(ndata, attn_bias=None, attn_mask=None, fused=None, seed=None)``: `ndata` (B, N, feat_size), `attn_bias`
+    (B, N, N, num_heads), `attn_mask` (B, N, N) with True = masked.  Returns (B, N, feat_size).  On the fused route a
+    fully masked row yields the output bias of ``out_proj`` (a zero attention row) where the reference yields NaN.
+    ``attn_bias_type="mul"`` is the torch composition only (absent from the kernels)."""
+
+    def __init__(self, feat_size, num_heads, bias=True, attn_bias_type="add", attn_drop=0.1):
+        super().__init__()
+        self.feat_size, self.num_heads = int(feat_size), int(num_heads)
+        self.head_dim = self.feat_size // self.num_heads
+        if self.head_dim * self.num_heads != self.feat_size:
+            raise ValueError("feat_size must be divisible by num_heads")
+        if attn_bias_type not in ("add", "mul"):
+            raise ValueError("attn_bias_type must be 'add' or 'mul'")
+        self.scaling = self.head_dim ** -0.5
+        self.attn_bias_type, self.attn_drop = attn_bias_type, float(attn_drop)
+        self.q_proj = torch.nn.Linear(feat_size, feat_size, bias=bias)
+        self.k_proj = torch.nn.Linear(feat_size, feat_size, bias=bias)
+        self.v_proj = torch.nn.Linear(feat_size, feat_size, bias=bias)
+        self.out_proj = torch.nn.Linear(feat_size, feat_size, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for proj in (self.q_proj, self.k_proj, self.v_proj):
+            torch.nn.init.xavier_uniform_(proj.weight, gain=2 ** -0.5)
+        torch.nn.init.xavier_uniform_(self.out_proj.weight)
+        if self.out_proj.bias is not None:
+            torch.nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, ndata, attn_bias=None, attn_mask=None, fused=None, seed=None):
+        from . import ops
+
+        B, N, _ = ndata.shape
+        q, k, v = (proj(ndata).view(B, N, self.num_heads, self.head_dim) for proj in (self.q_proj, self.k_proj, self.v_proj))
+        if self.attn_bias_type == "mul" and attn_bias is not None:
+            if fused:
+                raise ops.DGLAMDError("biased_attention: the multiplicative bias has no kernel (attn_bias_type='mul')")
+            w = torch.einsum("bihd,bjhd->bijh", q * self.scaling, k) * attn_bias
+            if attn_mask is not None:
+                w = w.masked_fill(attn_mask.to(torch.bool).unsqueeze(-1), float("-inf"))
+            w = torch.nn.functional.dropout(torch.softmax(w, dim=2), p=self.attn_drop, training=self.training)
+            attn = torch.einsum("bijh,bjhd->bihd", w, v)
+        else:
+            attn = ops.biased_attention(q, k, v, attn_bias, attn_mask, scale=self.scaling, attn_drop=self.attn_drop,
+                                        training=self.training, seed=seed, fused=fused)
+        return self.out_proj(attn.reshape(B, N, self.feat_size))
+
+    def extra_repr(self):
+        return "feat_size=%d, num_heads=%d, attn_bias_type=%s, attn_drop=%g" % (self.feat_size, self.num_heads,
+                                                                               self.attn_bias_type, self.attn_drop)

@@ -14,7 +14,7 @@ from . import _capi
 from ._lib import DGLAMDError
 
 __all__ = ["gspmm", "gsddmm", "edge_softmax", "copy_u", "copy_v", "copy_e", "gat_attention", "gat_attention_applies",
-           "graphormer_bias", "graphormer_bias_gather"]
+           "graphormer_bias", "graphormer_bias_gather", "biased_attention", "biased_attention_applies"]
 
 
 def _reshape_for_broadcast(op, lhs, rhs):
@@ -338,6 +338,102 @@ def graphormer_bias(dist, paths, edge_feat, path_weight, spatial_weight=None, *,
     weight = path_weight.reshape(max_len, heads, -1)[:lc]
     acc = torch.einsum("...ld,lhd->...h", path_data, weight).to(torch.float32)
     return _gbias_finish(acc, dist, spatial_weight, max_len, padding_idx, edge_feat.dtype)
+
+
+# ---- biased multi-head attention: the consumer of the Graphormer bias -------------------------------
+_BATTN_MAX_DIM = 128
+_BATTN_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _battn_check(q, k, v, attn_bias, attn_mask, attn_drop):
+    """The refusals of biased attention, by name, before anything is launched."""
+    who = "biased_attention: "
+    if q.dim() != 4 or k.shape != q.shape or v.shape != q.shape:
+        raise DGLAMDError(who + "q, k, v must share one shape (B, N, H, D), got %s, %s, %s"
+                          % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    B, N, H, D = q.shape
+    floats = (q, k, v) + (() if attn_bias is None else (attn_bias,))
+    if len({t.dtype for t in floats}) != 1:
+        raise DGLAMDError(who + "operand dtypes differ: %s" % ", ".join(str(t.dtype) for t in floats))
+    if attn_bias is not None and tuple(attn_bias.shape) != (B, N, N, H):
+        raise DGLAMDError(who + "attn_bias must be (B, N, N, H) = %s, got %s" % ((B, N, N, H), tuple(attn_bias.shape)))
+    if attn_mask is not None and (tuple(attn_mask.shape) != (B, N, N) or attn_mask.dtype not in (torch.bool, torch.uint8)):
+        raise DGLAMDError(who + "attn_mask must be a bool or uint8 (B, N, N) = %s, got %s %s"
+                          % ((B, N, N), attn_mask.dtype, tuple(attn_mask.shape)))
+    if not 0.0 <= float(attn_drop) < 1.0:
+        raise DGLAMDError(who + "attn_drop must lie in [0, 1), got %r" % (attn_drop,))
+    tensors = floats + (() if attn_mask is None else (attn_mask,))
+    if len({t.device for t in tensors}) != 1:
+        raise DGLAMDError(who + "operands lie on different devices: %s" % ", ".join(str(t.device) for t in tensors))
+
+
+def biased_attention_applies(q, k, v, attn_bias=None, attn_mask=None):
+    """Whether the kernels of csrc/biased_attention.hip take this call: fp32 / fp16 / bf16 operands of one dtype on one
+    GPU, q, k, v (B, N, H, D) with 1 <= D <= 128 and N, H >= 1, the bias (B, N, N, H), the mask a bool / uint8 (B, N, N)."""
+    try:
+        _battn_check(q, k, v, attn_bias, attn_mask, 0.0)
+    except DGLAMDError:
+        return False
+    return (q.is_cuda and q.dtype in _BATTN_DTYPES and 1 <= q.shape[3] <= _BATTN_MAX_DIM and q.shape[1] >= 1 and q.shape[2] >= 1
+            and all(type(t) is torch.Tensor for t in (q, k, v)))
+
+
+def biased_attention(q, k, v, attn_bias=None, attn_mask=None, *, scale=None, attn_drop=0.0, training=True, seed=None, fused=None):
+    """Dense multi-head attention with a graph attention bias, what BiasedMHA (python/dgl/nn/pytorch/gt/biased_mha.py)
+    computes between its projections::
+
+        s[b, i, j, h] = scale * <q[b, i, h], k[b, j, h]> + attn_bias[b, i, j, h];   -inf where attn_mask[b, i, j]
+        out[b, i, h]  = sum_j dropout(softmax_j(s))[b, i, j, h] * v[b, j, h]
+
+    `q`, `k`, `v` are (B, N, H, D), views of the (B, N, H * D) projections; `attn_bias` is (B, N, N, H), as
+    :func:`graphormer_bias` lays it out; `attn_mask` (B, N, N), bool or uint8, True = masked, shared by the heads; `scale`
+    defaults to ``D ** -0.5``.  Returns (B, N, H, D).  Differentiable in q, k, v and attn_bias.
+
+    ``fused=None`` takes the kernels except for fp32 operands with N > 128 (slower than the composition at N = 512).
+    On a GPU (``fused=None`` or True) this is ONE kernel forward and three backward (csrc/biased_attention.hip): the
+    scores live in registers, the bias is read once in its own layout and its gradient written once in the same, and the
+    backward recomputes the weights from the row log-sum-exp, deterministically.  ``fused=False``, and CPU tensors, take
+    the reference's sequence in plain torch (bmm, add, masked fill, softmax, dropout, bmm).
+
+    A row whose scores are all -inf (a fully masked row, -inf in the bias) gives a ZERO output row and zero gradients on
+    the fused route; the composed route keeps the reference's NaN.  The two routes draw different dropout streams: the
+    fused keep bit is a function of (seed, b, h, i, j) (see :func:`dgl_amd._capi.biased_attention_dropout_mask_host`),
+    ``seed=None`` draws one from torch's default CPU generator, and under stream capture ``attn_drop > 0`` needs an
+    explicit seed."""
+    _battn_check(q, k, v, attn_bias, attn_mask, attn_drop)
+    p = float(attn_drop) if training else 0.0
+    scale = float(q.shape[3]) ** -0.5 if scale is None else float(scale)
+    applies = biased_attention_applies(q, k, v, attn_bias, attn_mask)
+    if fused and not applies:
+        if not q.is_cuda:
+            raise DGLAMDError("biased_attention: dgl_amd kernels run on a ROCm GPU (no CPU fallback); fused=True needs GPU tensors")
+        if q.shape[3] > _BATTN_MAX_DIM:
+            raise DGLAMDError("biased_attention: head width %d: the kernels take 1 to %d" % (q.shape[3], _BATTN_MAX_DIM))
+        raise DGLAMDError("biased_attention: the fused kernels take float32, float16 or bfloat16 operands, got %s" % q.dtype)
+    # fused=None: the kernels wherever they were measured not slower (profiles/r25): fp32 beyond N = 128 lost at the
+    # one larger size measured (N = 512, 0.6-0.9x) and is left to the composition
+    auto = applies and not (q.dtype == torch.float32 and q.shape[1] > 128)
+    if auto if fused is None else bool(fused):
+        if p == 0.0:
+            seed = 0
+        elif seed is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise DGLAMDError("biased_attention: attn_drop > 0 under stream capture needs an explicit seed")
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        if not 0 <= int(seed) < 2 ** 63:
+            raise DGLAMDError("biased_attention: seed must be an integer in [0, 2**63)")
+        mask = None if attn_mask is None else attn_mask.contiguous().view(torch.uint8)
+        return _F.BiasedAttention.apply(q, k, v, attn_bias, mask, scale, p, int(seed))
+    B, N, H, D = q.shape
+    qh = q.permute(0, 2, 1, 3).reshape(B * H, N, D) * scale
+    w = torch.bmm(qh, k.permute(0, 2, 3, 1).reshape(B * H, D, N)).reshape(B, H, N, N).permute(0, 2, 3, 1)
+    if attn_bias is not None:
+        w = w + attn_bias
+    if attn_mask is not None:
+        w = w.masked_fill(attn_mask.to(torch.bool).unsqueeze(-1), float("-inf"))
+    w = torch.softmax(w.permute(0, 3, 1, 2).reshape(B * H, N, N), dim=2)
+    w = torch.nn.functional.dropout(w, p=p, training=p > 0.0)
+    return torch.bmm(w, v.permute(0, 2, 1, 3).reshape(B * H, N, D)).reshape(B, H, N, D).permute(0, 2, 1, 3)
 
 
 # ---- generated aliases -----------------------------------------------------------------

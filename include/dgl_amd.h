@@ -1291,6 +1291,51 @@ int dgla_graphormer_bias_backward(int idtype_bits, int dtype, const void* dist, 
                                   int64_t spatial_rows, const void* grad_out, void* grad_table, void* grad_spatial,
                                   int64_t padding_idx, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- Biased attention (csrc/biased_attention.hip) ---------------------------------------------------------
+ * The attention of a Graphormer layer (python/dgl/nn/pytorch/gt/biased_mha.py between its projections), which the
+ * reference composes from bmm, transposes, an in-place add, a masked fill, softmax, dropout and a second bmm.  The rule,
+ * for batch b, head h, query i, key j; q, k, v, out are (B, N, H, D), bias (B, N, N, H), mask (B, N, N) uint8 / bool:
+ *
+ *   s[b][i][j][h] = scale * sum_d q[b][i][h][d] k[b][j][h][d] + bias[b][i][j][h]        (no bias term when bias is NULL)
+ *   s[b][i][j][h] = -inf where mask[b][i][j] != 0                                        (mask may be NULL)
+ *   p             = softmax over j of s, with the row maximum
+ *   out[b][i][h][:] = sum_j keep[b][h][i][j] p[b][i][j][h] / (1 - drop) v[b][j][h][:]
+ *
+ * q, k, v, bias and out share one type (float32, float16, bfloat16; dtype codes as dgla_tensor).  Every sum is fp32; out
+ * and the gradients are rounded once, at the store.  p is rounded to the operand type before the second product for
+ * the 16-bit types and stays fp32 for float32.  1 <= D <= 128; any N, H >= 1.
+ *
+ * Rows with no finite score.  A row whose scores are all -inf (a fully masked row, or -inf written into the bias) gives
+ * a ZERO output row, lse = -inf, and zero gradients through it.  The reference gives NaN there and tells its users to
+ * keep one key open; the torch composition of this library keeps that NaN.
+ *
+ * Dropout: the keep rule of csrc/gat_dropout.h, unchanged: w = Philox4x32-10(key = seed, counter = (row low, row high,
+ * j / 4, 0))[j % 4] with row = (b H + h) N + i, keep = (w >> 8) >= (uint32_t)(drop * 2^24).  A threshold of 0 skips the
+ * generator.  dgla_biased_attention_dropout_mask_host writes keep as (B, H, N, N) uint8 from the same definition.
+ *
+ * dgla_biased_attention_forward: one launch, no workspace, nothing read back or cleared: the call can be captured.
+ *   Writes out and lse (2, B, H, N) fp32: lse[0] is the row log-sum-exp of s (before dropout), -inf for a zero row, and
+ *   lse[1] its low-order part (the exact value minus lse[0], 0 for a zero row).  The backward computes
+ *   p = exp((s - lse[0]) - lse[1]): a log-sum-exp rounded once to fp32 would be the largest error of the fp32 gradients.
+ * dgla_biased_attention_backward: dq, dk, dv (B, N, H, D) and, when dbias is not NULL, dbias (B, N, N, H) in the
+ *   operands' type; every element is written, so none needs a fill.  dbias = p (keep / (1 - drop) (dout . v) - delta),
+ *   zero at masked positions; delta = sum_d dout out.  p is recomputed from q, k, bias, mask and lse.  Three launches, no
+ *   floating-point atomics: the same bits on every run.  The workspace holds delta: workspace == NULL takes
+ *   stream-ordered scratch, one that is given but too small is refused with the bytes required.
+ * dgla_biased_attention_workspace_bytes: 4 B N H rounded up to 256; 0 for sizes that are refused.
+ * All pointers but keep are device memory; the calls run on the caller's stream.  They fail with -1 and a message
+ * prefixed "biased_attention:", before any launch, for an operand type other than the three, D outside [1, 128],
+ * N < 1 or H < 1, drop outside [0, 1), and NULL arrays.  B == 0 launches nothing. */
+size_t dgla_biased_attention_workspace_bytes(int64_t B, int64_t N, int64_t H);
+int dgla_biased_attention_forward(int dtype, const void* q, const void* k, const void* v, const void* bias, const void* mask,
+                                  int64_t B, int64_t N, int64_t H, int64_t D, float scale, float drop, uint64_t seed, void* out,
+                                  float* lse, void* hip_stream);
+int dgla_biased_attention_backward(int dtype, const void* q, const void* k, const void* v, const void* bias, const void* mask,
+                                   const void* out, const float* lse, const void* dout, int64_t B, int64_t N, int64_t H, int64_t D,
+                                   float scale, float drop, uint64_t seed, void* dq, void* dk, void* dv, void* dbias,
+                                   void* workspace, size_t workspace_bytes, void* hip_stream);
+int dgla_biased_attention_dropout_mask_host(uint64_t seed, float drop, int64_t B, int64_t H, int64_t N, uint8_t* keep);
+
 /* ---- Top-k neighbour selection (csrc/topk.hip) ------------------------------------------------------------
  * dgl.sampling.select_topk: for every seed the k in- or out-edges with the largest (or smallest) weight.  The reference
  * has no GPU form: python/dgl/sampling/neighbor.py asserts a CPU graph and sorts every row with std::sort
