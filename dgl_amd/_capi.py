@@ -1465,6 +1465,49 @@ def biased_attention_dropout_mask_host(seed, drop, B, H, N):
     return keep
 
 
+def spatial_encoder3d_workspace_bytes(B, N, K, H):
+    """The bytes of the workspace of :func:`spatial_encoder3d_backward` (dgla_spatial_encoder3d_workspace_bytes)."""
+    return int(LIB.dgla_spatial_encoder3d_workspace_bytes(int(B), int(N), int(K), int(H)))
+
+
+def _se3d_head(coord, pair, means, stds, w1, b1, w2, b2):
+    """The arguments both 3D spatial encoding calls start with: coord (B, N, 3), the four (B, N) pair vectors `pair` =
+    (gamma_src, gamma_tgt, beta_src, beta_tgt), means and stds (K), all float32; w1 (K, K), b1 (K), w2 (H, K), b2 (H) of
+    one dtype; all contiguous on one GPU (checked by ops.spatial_encoder_3d)."""
+    small, weights = (coord,) + tuple(pair) + (means, stds), (w1, b1, w2, b2)
+    _all_on(True, "spatial_encoder_3d", *small, *weights)
+    if any(t.dtype != torch.float32 for t in small) or any(t.dtype != w1.dtype for t in weights):
+        raise _lib.DGLAMDError("spatial_encoder_3d: coord, the pair vectors, means and stds must be float32 and the weights of one dtype")
+    if not all(t.is_contiguous() for t in small + weights):
+        raise _lib.DGLAMDError("spatial_encoder_3d: operands must be contiguous")
+    return [_DTYPES.get(w1.dtype, -1)] + [_ptr(t) for t in small + weights]
+
+
+def spatial_encoder3d_forward(coord, pair, means, stds, w1, b1, w2, b2, into=None):
+    """``out`` (B, N, N, H) of the rule "3D spatial encoding" of include/dgl_amd.h (dgla_spatial_encoder3d_forward):
+    one launch, nothing read back.  `into` gives `out` preallocated."""
+    head = _se3d_head(coord, pair, means, stds, w1, b1, w2, b2)
+    (B, N), K, H = coord.shape[:2], w1.shape[0], w2.shape[0]
+    out = torch.empty((B, N, N, H), dtype=w1.dtype, device=w1.device) if into is None else into
+    check_call(LIB.dgla_spatial_encoder3d_forward(*head, B, N, K, H, _ptr(out), _stream(w1)))
+    return out
+
+
+def spatial_encoder3d_backward(coord, pair, means, stds, w1, b1, w2, b2, dout, into=None, ws=None):
+    """``(dw1, db1, dw2, db2, dmeans, dstds, dgamma_src, dgamma_tgt, dbeta_src, dbeta_tgt)`` of
+    :func:`spatial_encoder3d_forward` (dgla_spatial_encoder3d_backward): deterministic, no atomics.  `into` gives the ten
+    preallocated in that order; `ws` (uint8, :func:`spatial_encoder3d_workspace_bytes`) may be given."""
+    head = _se3d_head(coord, pair, means, stds, w1, b1, w2, b2)
+    (B, N), K, H = coord.shape[:2], w1.shape[0], w2.shape[0]
+    if into is None:
+        into = tuple(torch.empty_like(t) for t in (w1, b1, w2, b2, means, stds) + tuple(pair))
+    _all_on(True, "spatial_encoder_3d", dout, ws, *into)
+    if dout.dtype != w1.dtype or not dout.is_contiguous():
+        raise _lib.DGLAMDError("spatial_encoder_3d: the cotangent must be contiguous and of the weights' dtype")
+    check_call(LIB.dgla_spatial_encoder3d_backward(*head, _ptr(dout), B, N, K, H, *[_ptr(t) for t in into], *_ws(ws), _stream(w1)))
+    return tuple(into)
+
+
 def _seed_csr(call, args, seeds, capacity=None, tail=(), into=None, pass_capacity=False):
     """``(indptr, nbr, eids)``, a CSR over `seeds`, from an entry point of the form ``call(*args, out_indptr, out_nbr,
     out_eids, *tail)``.  With a `capacity` the outputs are allocated at it and the entry is called once; ``None`` asks

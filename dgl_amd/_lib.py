@@ -382,6 +382,14 @@ LIB.dgla_biased_attention_backward.argtypes = (_BATTN + [c_void_p] * 3 + [c_int6
                                                [c_void_p] * 5 + [c_size_t, c_void_p])
 LIB.dgla_biased_attention_dropout_mask_host.restype = c_int
 LIB.dgla_biased_attention_dropout_mask_host.argtypes = [ctypes.c_uint64, ctypes.c_float, c_int64, c_int64, c_int64, c_void_p]
+# the 3D spatial encoding unit: dtype, coord, the four pair vectors, means, stds, w1, b1, w2, b2
+_SE3D = [c_int] + [c_void_p] * 11
+LIB.dgla_spatial_encoder3d_workspace_bytes.restype = c_size_t
+LIB.dgla_spatial_encoder3d_workspace_bytes.argtypes = [c_int64] * 4
+LIB.dgla_spatial_encoder3d_forward.restype = c_int
+LIB.dgla_spatial_encoder3d_forward.argtypes = _SE3D + [c_int64] * 4 + [c_void_p, c_void_p]
+LIB.dgla_spatial_encoder3d_backward.restype = c_int
+LIB.dgla_spatial_encoder3d_backward.argtypes = _SE3D + [c_void_p] + [c_int64] * 4 + [c_void_p] * 11 + [c_size_t, c_void_p]
 # the top-k selection unit: csr, weight, weight dtype, seeds, num_seeds, k, ascending, out_indptr, out_nbr, out_eids
 _TOPK = [P(CSR), c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]
 LIB.dgla_select_topk_max_picks.restype = c_int

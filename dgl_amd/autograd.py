@@ -458,6 +458,28 @@ class BiasedAttention(torch.autograd.Function):
         return dq, dk, dv, dbias, None, None, None, None
 
 
+class SpatialEncoder3d(torch.autograd.Function):
+    """The 3D spatial encoding (csrc/spatial_encoder3d.hip): ``out`` (B, N, N, H) from coord, the four (B, N) pair
+    vectors, means, stds (all fp32) and the two linears.  Only the inputs are saved; the backward recomputes the features
+    and the hidden layer per tile, so no (B N N, K) tensor is ever stored.  No gradient with respect to coord."""
+
+    @staticmethod
+    def forward(ctx, coord, gs, gt, bs, bt, means, stds, w1, b1, w2, b2):
+        from . import _capi
+
+        saved = tuple(t.contiguous() for t in (coord, gs, gt, bs, bt, means, stds, w1, b1, w2, b2))
+        ctx.save_for_backward(*saved)
+        return _capi.spatial_encoder3d_forward(saved[0], saved[1:5], *saved[5:])
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import _capi
+
+        s = ctx.saved_tensors
+        dw1, db1, dw2, db2, dmeans, dstds, dgs, dgt, dbs, dbt = _capi.spatial_encoder3d_backward(s[0], s[1:5], *s[5:], dout.contiguous())
+        return None, dgs, dgt, dbs, dbt, dmeans, dstds, dw1, db1, dw2, db2
+
+
 def _nd(t):
     from . import _ffi
     return None if t is None else _ffi.NDArray(t)

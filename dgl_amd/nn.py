@@ -15,7 +15,7 @@ from . import edge_order as _eo
 from . import function as fn
 from .ops import edge_softmax
 
-__all__ = ["functional", "gat_attention", "GATAttention", "GraphormerBias", "BiasedMHA"]
+__all__ = ["functional", "gat_attention", "GATAttention", "GraphormerBias", "BiasedMHA", "SpatialEncoder3d"]
 
 
 class functional:  # noqa: N801  (a namespace: python/dgl/nn/functional/__init__.py exports exactly this)
@@ -174,3 +174,45 @@ class BiasedMHA(torch.nn.Module):
     def extra_repr(self):
         return "feat_size=%d, num_heads=%d, attn_bias_type=%s, attn_drop=%g" % (self.feat_size, self.num_heads,
                                                                                self.attn_bias_type, self.attn_drop)
+
+
+class SpatialEncoder3d(torch.nn.Module):
+    """The attention bias of the 3D (molecular) Graphormer, the reference's ``SpatialEncoder3d(num_kernels, num_heads=1,
+    max_node_type=100)`` (python/dgl/nn/pytorch/gt/spatial_encoder.py) on :func:`dgl_amd.ops.spatial_encoder_3d`.
+    ``means``, ``stds``, ``linear_layer_1``, ``linear_layer_2``, ``gamma`` and ``beta`` carry the reference's names,
+    shapes and initialisation, so its state dict loads unchanged.
+
+    ``forward(coord, node_type=None, fused=None)``: `coord` (B, N, 3), `node_type` (B, N) integer ids in
+    [-1, max_node_type) (-1 = a padded node).  Returns (B, N, N, num_heads).  The module gathers the (B, N) scalars of
+    the source rows ``node_type + 2`` and the target rows ``node_type + max_node_type + 3`` of ``gamma`` and ``beta``
+    with torch's embedding (row 0, the padding row, for all four when `node_type` is None): the id range check, the
+    padding row's zero gradient and the scatter of the gradients into the tables stay torch's, and the kernels never
+    index a table by a caller's id."""
+
+    def __init__(self, num_kernels, num_heads=1, max_node_type=100):
+        super().__init__()
+        self.num_kernels, self.num_heads, self.max_node_type = int(num_kernels), int(num_heads), int(max_node_type)
+        self.means = torch.nn.Parameter(torch.empty(self.num_kernels))
+        self.stds = torch.nn.Parameter(torch.empty(self.num_kernels))
+        self.linear_layer_1 = torch.nn.Linear(self.num_kernels, self.num_kernels)
+        self.linear_layer_2 = torch.nn.Linear(self.num_kernels, self.num_heads)
+        self.gamma = torch.nn.Embedding(2 * self.max_node_type + 3, 1, padding_idx=0)
+        self.beta = torch.nn.Embedding(2 * self.max_node_type + 3, 1, padding_idx=0)
+        torch.nn.init.uniform_(self.means, 0, 3)
+        torch.nn.init.uniform_(self.stds, 0, 3)
+        torch.nn.init.constant_(self.gamma.weight, 1)
+        torch.nn.init.constant_(self.beta.weight, 0)
+
+    def forward(self, coord, node_type=None, fused=None):
+        from . import ops
+
+        if node_type is None:
+            src = tgt = torch.zeros(coord.shape[:2], dtype=torch.long, device=coord.device)
+        else:
+            src, tgt = node_type.long() + 2, node_type.long() + self.max_node_type + 3
+        pair = [table(ids).squeeze(-1) for table in (self.gamma, self.beta) for ids in (src, tgt)]
+        return ops.spatial_encoder_3d(coord, self.means, self.stds, self.linear_layer_1.weight, self.linear_layer_1.bias,
+                                      self.linear_layer_2.weight, self.linear_layer_2.bias, *pair, fused=fused)
+
+    def extra_repr(self):
+        return "num_kernels=%d, num_heads=%d, max_node_type=%d" % (self.num_kernels, self.num_heads, self.max_node_type)

@@ -14,7 +14,8 @@ from . import _capi
 from ._lib import DGLAMDError
 
 __all__ = ["gspmm", "gsddmm", "edge_softmax", "copy_u", "copy_v", "copy_e", "gat_attention", "gat_attention_applies",
-           "graphormer_bias", "graphormer_bias_gather", "biased_attention", "biased_attention_applies"]
+           "graphormer_bias", "graphormer_bias_gather", "biased_attention", "biased_attention_applies",
+           "spatial_encoder_3d", "spatial_encoder_3d_applies"]
 
 
 def _reshape_for_broadcast(op, lhs, rhs):
@@ -434,6 +435,95 @@ def biased_attention(q, k, v, attn_bias=None, attn_mask=None, *, scale=None, att
     w = torch.softmax(w.permute(0, 3, 1, 2).reshape(B * H, N, N), dim=2)
     w = torch.nn.functional.dropout(w, p=p, training=p > 0.0)
     return torch.bmm(w, v.permute(0, 2, 1, 3).reshape(B * H, N, D)).reshape(B, H, N, D).permute(0, 2, 1, 3)
+
+
+# ---- 3D spatial encoding: the attention bias of the 3D Graphormer -----------------------------------
+_SE3D_MAX_K, _SE3D_MAX_H = 128, 64
+
+
+def _se3d_check(coord, means, stds, w1, b1, w2, b2, pair):
+    """The refusals of the 3D spatial encoding, by name, before anything is launched; returns (B, N, K, H)."""
+    who = "spatial_encoder_3d: "
+    if coord.dim() != 3 or coord.shape[2] != 3:
+        raise DGLAMDError(who + "coord must be (B, N, 3), got %s" % (tuple(coord.shape),))
+    B, N = coord.shape[:2]
+    K, H = means.shape[0], w2.shape[0]
+    shapes = ((means, (K,)), (stds, (K,)), (w1, (K, K)), (b1, (K,)), (w2, (H, K)), (b2, (H,)))
+    if means.dim() != 1 or w2.dim() != 2 or any(tuple(t.shape) != s for t, s in shapes):
+        raise DGLAMDError(who + "means, stds, b1 must be (K,), w1 (K, K), w2 (H, K), b2 (H,), got %s"
+                          % ", ".join(str(tuple(t.shape)) for t, _ in shapes))
+    if len({t.dtype for t in (w1, b1, w2, b2)}) != 1:
+        raise DGLAMDError(who + "operand dtypes differ: %s" % ", ".join(str(t.dtype) for t in (w1, b1, w2, b2)))
+    given = [t for t in pair if t is not None]
+    if any(tuple(t.shape) != (B, N) for t in given):
+        raise DGLAMDError(who + "gamma_src, gamma_tgt, beta_src, beta_tgt must be (B, N) = %s" % ((B, N),))
+    tensors = [coord, means, stds, w1, b1, w2, b2] + given
+    if len({t.device for t in tensors}) != 1:
+        raise DGLAMDError(who + "operands lie on different devices: %s" % ", ".join(str(t.device) for t in tensors))
+    return B, N, K, H
+
+
+def spatial_encoder_3d_applies(coord, means, stds, w1, b1, w2, b2, gamma_src=None, gamma_tgt=None, beta_src=None, beta_tgt=None):
+    """Whether the kernels of csrc/spatial_encoder3d.hip take this call: everything on one GPU, fp32 / fp16 / bf16
+    weights of one dtype, 1 <= K <= 128, 1 <= H <= 64, and no gradient asked of `coord`."""
+    pair = (gamma_src, gamma_tgt, beta_src, beta_tgt)
+    try:
+        _, _, K, H = _se3d_check(coord, means, stds, w1, b1, w2, b2, pair)
+    except DGLAMDError:
+        return False
+    return (w1.is_cuda and w1.dtype in _BATTN_DTYPES and 1 <= K <= _SE3D_MAX_K and 1 <= H <= _SE3D_MAX_H
+            and not (coord.requires_grad and torch.is_grad_enabled())
+            and all(type(t) in (torch.Tensor, torch.nn.Parameter) for t in (coord, means, stds, w1, b1, w2, b2)))
+
+
+def spatial_encoder_3d(coord, means, stds, w1, b1, w2, b2, gamma_src=None, gamma_tgt=None, beta_src=None, beta_tgt=None, *,
+                       fused=None):
+    """The 3D spatial encoding of SpatialEncoder3d (python/dgl/nn/pytorch/gt/spatial_encoder.py:136-209), the rule
+    "3D spatial encoding" of include/dgl_amd.h::
+
+        d = |coord[b, i] - coord[b, j]|;   x = (gamma_src[b, i] + gamma_tgt[b, j]) * d + (beta_src[b, i] + beta_tgt[b, j])
+        g_k = exp(-0.5 * ((x - means[k]) / sd_k) ** 2) / (sqrt(2 * 3.14159) * sd_k),   sd_k = |stds[k]| + 1e-2
+        out[b, i, j] = gelu(g @ w1.T + b1) @ w2.T + b2
+
+    `coord` (B, N, 3); `means`, `stds` (K,); `w1` (K, K), `b1` (K,), `w2` (H, K), `b2` (H,) of one dtype, which is the
+    result's; the four pair vectors (B, N) are what the reference's gamma / beta embeddings give per source and per
+    target node (None: gamma 1 and 0, beta 0 and 0, i.e. x = d).  Returns (B, N, N, H), the layout
+    :func:`biased_attention` takes as its bias.  Differentiable in everything but `coord` on the fused route.
+
+    On a GPU (``fused=None`` or True) this is ONE kernel forward and three backward (csrc/spatial_encoder3d.hip): both
+    weight matrices stay in registers, the features live in LDS only, and the backward recomputes them; coord, the pair
+    vectors, means and stds cross as fp32.  ``fused=False``, CPU tensors, an empty batch and a `coord` that requires
+    grad take the reference's sequence in plain torch (cdist without the matmul shortcut, Gaussian, linear, GELU, linear)."""
+    pair = (gamma_src, gamma_tgt, beta_src, beta_tgt)
+    B, N, K, H = _se3d_check(coord, means, stds, w1, b1, w2, b2, pair)
+    applies = spatial_encoder_3d_applies(coord, means, stds, w1, b1, w2, b2, *pair)
+    if fused and not applies:
+        who = "spatial_encoder_3d: "
+        if not 1 <= K <= _SE3D_MAX_K:
+            raise DGLAMDError(who + "num_kernels %d: the kernels take 1 to %d" % (K, _SE3D_MAX_K))
+        if not 1 <= H <= _SE3D_MAX_H:
+            raise DGLAMDError(who + "num_heads %d: the kernels take 1 to %d" % (H, _SE3D_MAX_H))
+        if not w1.is_cuda:
+            raise DGLAMDError(who + "dgl_amd kernels run on a ROCm GPU (no CPU fallback); fused=True needs GPU tensors")
+        if coord.requires_grad:
+            raise DGLAMDError(who + "the gradient with respect to coord has no kernel (coord.requires_grad)")
+        raise DGLAMDError(who + "the fused kernels take float32, float16 or bfloat16 weights, got %s" % w1.dtype)
+    feat = torch.float64 if w1.dtype == torch.float64 else torch.float32
+    if pair == (None, None, None, None):
+        one, zero = coord.new_ones((B, N), dtype=feat), coord.new_zeros((B, N), dtype=feat)
+        pair = (one, zero, zero, zero)
+    elif None in pair:
+        raise DGLAMDError("spatial_encoder_3d: give all four of gamma_src, gamma_tgt, beta_src, beta_tgt or none")
+    coord, means, stds = coord.to(feat), means.to(feat), stds.to(feat)
+    gs, gt, bs, bt = (t.to(feat) for t in pair)
+    if (applies if fused is None else bool(fused)) and B * N > 0:
+        return _F.SpatialEncoder3d.apply(coord, gs, gt, bs, bt, means, stds, w1, b1, w2, b2)
+    d = torch.cdist(coord, coord, p=2.0, compute_mode="donot_use_mm_for_euclid_dist")
+    x = (gs.unsqueeze(2) + gt.unsqueeze(1)) * d + (bs.unsqueeze(2) + bt.unsqueeze(1))
+    sd = stds.abs() + 1e-2
+    g = torch.exp(-0.5 * ((x.unsqueeze(-1) - means) / sd) ** 2) / ((2 * 3.14159) ** 0.5 * sd)
+    h = torch.nn.functional.gelu(torch.nn.functional.linear(g.to(w1.dtype), w1, b1))
+    return torch.nn.functional.linear(h, w2, b2)
 
 
 # ---- generated aliases -----------------------------------------------------------------

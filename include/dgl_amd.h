@@ -1336,6 +1336,51 @@ int dgla_biased_attention_backward(int dtype, const void* q, const void* k, cons
                                    void* workspace, size_t workspace_bytes, void* hip_stream);
 int dgla_biased_attention_dropout_mask_host(uint64_t seed, float drop, int64_t B, int64_t H, int64_t N, uint8_t* keep);
 
+/* ---- 3D spatial encoding (csrc/spatial_encoder3d.hip) -----------------------------------------------------
+ * The attention bias of the 3D (molecular) Graphormer, SpatialEncoder3d (python/dgl/nn/pytorch/gt/spatial_encoder.py:
+ * 136-209), which the reference composes from cdist, two embedding gathers over (B, N, N, 2) ids, a Gaussian, two
+ * linears and a GELU, keeping three (B N N, K) tensors.  The rule, for the pair p = (b, i, j); coord is (B, N, 3), the
+ * four pair vectors gamma_src, gamma_tgt, beta_src, beta_tgt (gs, gt, bs, bt) are (B, N), means and stds (K), W1 (K, K),
+ * b1 (K), W2 (H, K), b2 (H), out (B, N, N, H):
+ *
+ *   d     = sqrt(sum_c (coord[b][i][c] - coord[b][j][c])^2)                         (exact differences, fp32)
+ *   x     = (gs[b][i] + gt[b][j]) * d + (bs[b][i] + bt[b][j])                       (fp32)
+ *   sd_k  = |stds[k]| + 1e-2
+ *   g_k   = exp(-0.5 * ((x - means[k]) / sd_k)^2) / (sqrt(2 * 3.14159) * sd_k)      (the reference's constant, not pi)
+ *   z1    = g W1^T + b1;   h = gelu(z1)                                              (the erf form)
+ *   out[b][i][j][:] = h W2^T + b2
+ *
+ * coord, the pair vectors, means and stds and their gradients are float32 always.  W1, b1, W2, b2, out and dout share
+ * one type (float32, float16, bfloat16; dtype codes as dgla_tensor).  d, x and g are fp32; g and h are rounded to the
+ * weights' type as they enter the matrix products (no rounding for float32); every sum is fp32 and out and the
+ * gradients are rounded once, at the store.  1 <= K <= 128, 1 <= H <= 64, any value; the pair index is 64-bit.
+ * The kernels never see a node type: the pair vectors are what the caller gathered from its gamma / beta tables.
+ * The gradient with respect to coord is absent.
+ *
+ * dgla_spatial_encoder3d_forward: one launch, no workspace, nothing read back or cleared: the call can be captured.
+ *   No array of pairs x K elements is written anywhere.
+ * dgla_spatial_encoder3d_backward: dw1, db1, dw2, db2 in the weights' type, dmeans, dstds (K) and the four (B, N)
+ *   gradients of the pair vectors in float32; every element is written.  g, z1 and h are recomputed.  Three launches, no
+ *   floating-point atomics: the same bits on every run.  The workspace holds dL/dx, one float per pair, and one partial
+ *   of the parameter sums per workgroup (at most 256), which the second launch adds in workgroup order; the third forms
+ *   dgs[b][i] = sum_j dx d, dbs[b][i] = sum_j dx, dgt[b][j] = sum_i dx d, dbt[b][j] = sum_i dx with d recomputed.
+ *   workspace == NULL takes stream-ordered scratch, one that is given but too small is refused with the bytes required.
+ * dgla_spatial_encoder3d_workspace_bytes: the bytes of that workspace; 0 for sizes that are refused and for no pairs.
+ * All pointers are device memory; the calls run on the caller's stream.  They fail with -1 and a message prefixed
+ * "spatial_encoder_3d:", before any launch, for a weight type other than the three, K outside [1, 128], H outside
+ * [1, 64], negative B or N and NULL arrays.  B == 0 or N == 0 launches nothing and writes nothing. */
+size_t dgla_spatial_encoder3d_workspace_bytes(int64_t B, int64_t N, int64_t K, int64_t H);
+int dgla_spatial_encoder3d_forward(int dtype, const float* coord, const float* gamma_src, const float* gamma_tgt,
+                                   const float* beta_src, const float* beta_tgt, const float* means, const float* stds,
+                                   const void* w1, const void* b1, const void* w2, const void* b2, int64_t B, int64_t N, int64_t K,
+                                   int64_t H, void* out, void* hip_stream);
+int dgla_spatial_encoder3d_backward(int dtype, const float* coord, const float* gamma_src, const float* gamma_tgt,
+                                    const float* beta_src, const float* beta_tgt, const float* means, const float* stds,
+                                    const void* w1, const void* b1, const void* w2, const void* b2, const void* dout, int64_t B,
+                                    int64_t N, int64_t K, int64_t H, void* dw1, void* db1, void* dw2, void* db2, float* dmeans,
+                                    float* dstds, float* dgamma_src, float* dgamma_tgt, float* dbeta_src, float* dbeta_tgt,
+                                    void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- Top-k neighbour selection (csrc/topk.hip) ------------------------------------------------------------
  * dgl.sampling.select_topk: for every seed the k in- or out-edges with the largest (or smallest) weight.  The reference
  * has no GPU form: python/dgl/sampling/neighbor.py asserts a CPU graph and sorts every row with std::sort
