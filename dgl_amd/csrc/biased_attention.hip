@@ -40,6 +40,7 @@
 
 #include "gat_dropout.h"
 #include "host_util.h"
+#include "mfma_tile.h"
 
 namespace dgla {
 namespace {
@@ -48,43 +49,6 @@ constexpr int kBaTile = 32;        // rows of a tile: the M and N of the 32 x 32
 constexpr int kBaMaxWaves = 4;     // heads per workgroup
 constexpr int kBaMaxDim = 128;
 constexpr int kBaLdsBytes = 65536;  // what a workgroup may take without asking the runtime for more
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
-
-// One MFMA per operand type.  Raw is what a lane hands the instruction for A or B: FE consecutive k elements.
-template <typename T>
-struct BaMma;
-template <>
-struct BaMma<float> {
-  static constexpr int KSTEP = 2, FE = 1;
-  using Raw = float;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ void put(Raw& f, int e, float x) { f = x; }
-  static __device__ __forceinline__ void put_raw(Raw& f, int e, float x) { f = x; }
-};
-template <>
-struct BaMma<f16_t> {
-  static constexpr int KSTEP = 16, FE = 8;
-  using Raw = u16x8;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void put(Raw& f, int e, float x) { f[e] = __builtin_bit_cast(uint16_t, static_cast<f16_t>(x)); }
-  static __device__ __forceinline__ void put_raw(Raw& f, int e, f16_t x) { f[e] = __builtin_bit_cast(uint16_t, x); }
-};
-template <>
-struct BaMma<bf16_t> {
-  static constexpr int KSTEP = 16, FE = 8;
-  using Raw = u16x8;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b16x8, a), __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void put(Raw& f, int e, float x) { f[e] = from_acc<bf16_t>(x).bits; }
-  static __device__ __forceinline__ void put_raw(Raw& f, int e, bf16_t x) { f[e] = x.bits; }
-};
 
 // The weight exp(s - m) of a score s = hi + lo against a reference m = m_hi + m_lo.  The 16-bit types, whose results
 // carry 8 or 11 bits, take the hardware exponential of the rounded difference.  fp32 operands carry the score in two
@@ -113,8 +77,8 @@ struct BaGeo {
   static constexpr int DP = 32 * NB;
   static constexpr int RS = DP + VEC;
   static constexpr int BS = kBaTile + VEC;
-  static constexpr int KK = DP / BaMma<T>::KSTEP;      // steps of a product over d
-  static constexpr int STEPS = kBaTile / BaMma<T>::KSTEP;  // steps of a product over the 32 streamed rows
+  static constexpr int KK = DP / Mma32<T>::KSTEP;      // steps of a product over d
+  static constexpr int STEPS = kBaTile / Mma32<T>::KSTEP;  // steps of a product over the 32 streamed rows
   static constexpr int kTileElems = kBaTile * RS;
   static constexpr int kBiasElems = kBaTile * BS;
   static constexpr size_t kWaveBytes = sizeof(T) * (2 * kTileElems + kBiasElems);
@@ -133,9 +97,6 @@ struct BaArgs {
   int hg, tiles, groups;  // heads per workgroup, tiles of 32 rows, head groups
   int vec_ok, bias_vec_ok, out_vec_ok;
 };
-
-// the streamed row a register of the C tile holds
-__device__ __forceinline__ int ba_krow(int r, int g) { return 8 * (r >> 2) + 4 * g + (r & 3); }
 
 // A 32 x DP tile of a (B, N, H, D) operand into the wave's LDS, zero past `rows` and past D.  `src` is the tile's first
 // row at the wave's head; consecutive rows lie `row_stride` elements apart.
@@ -161,9 +122,9 @@ __device__ __forceinline__ void ba_load_tile(T* lds, const T* __restrict__ src, 
 
 // The stationary operand out of an LDS tile: the B fragments of row lane % 32 for every step over d.
 template <typename T, int NB>
-__device__ __forceinline__ void ba_read_frags(const T* lds, typename BaMma<T>::Raw (&f)[BaGeo<T, NB>::KK], int lane) {
+__device__ __forceinline__ void ba_read_frags(const T* lds, typename Mma32<T>::Raw (&f)[BaGeo<T, NB>::KK], int lane) {
   using G = BaGeo<T, NB>;
-  using M = BaMma<T>;
+  using M = Mma32<T>;
   const T* row = lds + (lane & 31) * G::RS + (lane >> 5) * M::FE;
 #pragma unroll
   for (int kk = 0; kk < G::KK; ++kk) f[kk] = *reinterpret_cast<const typename M::Raw*>(row + kk * M::KSTEP);
@@ -171,10 +132,10 @@ __device__ __forceinline__ void ba_read_frags(const T* lds, typename BaMma<T>::R
 
 // C[streamed row][stationary row] = sum_d X[streamed][d] S[stationary][d]: X in LDS, S in fragments.
 template <typename T, int NB>
-__device__ __forceinline__ f32x16 ba_score(const T* xs, const typename BaMma<T>::Raw (&st)[BaGeo<T, NB>::KK], int D, int lane) {
+__device__ __forceinline__ f32x16 ba_score(const T* xs, const typename Mma32<T>::Raw (&st)[BaGeo<T, NB>::KK], int D, int lane) {
   using G = BaGeo<T, NB>;
-  using M = BaMma<T>;
-  f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  using M = Mma32<T>;
+  f32x16 c = mfma_zero();
   const T* row = xs + (lane & 31) * G::RS + (lane >> 5) * M::FE;
 #pragma unroll
   for (int kk = 0; kk < G::KK; ++kk)
@@ -188,18 +149,18 @@ __device__ __forceinline__ f32x16 ba_score(const T* xs, const typename BaMma<T>:
 template <typename T, int NB>
 __device__ __forceinline__ void ba_accumulate(f32x16 (&acc)[NB], const T* ws, const f32x16& c, int lane) {
   using G = BaGeo<T, NB>;
-  using M = BaMma<T>;
+  using M = Mma32<T>;
   const int n = lane & 31, g = lane >> 5;
 #pragma unroll
   for (int st = 0; st < G::STEPS; ++st) {
     typename M::Raw b;
 #pragma unroll
-    for (int e = 0; e < M::FE; ++e) M::put(b, e, c[st * M::FE + e]);
+    for (int e = 0; e < M::FE; ++e) M::put(b, e, from_acc<T>(c[st * M::FE + e]));
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       typename M::Raw a;
 #pragma unroll
-      for (int e = 0; e < M::FE; ++e) M::put_raw(a, e, ws[ba_krow(st * M::FE + e, g) * G::RS + nb * 32 + n]);
+      for (int e = 0; e < M::FE; ++e) M::put(a, e, ws[mfma_c_row(st * M::FE + e, g) * G::RS + nb * 32 + n]);
       acc[nb] = M::mma(a, b, acc[nb]);
     }
   }
@@ -333,7 +294,7 @@ __device__ __forceinline__ BaBlock ba_block(const BaArgs& a) {
 template <typename T, int NB, bool BWD>
 __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_query_kernel(const BaArgs a) {
   using G = BaGeo<T, NB>;
-  using M = BaMma<T>;
+  using M = Mma32<T>;
   extern __shared__ __attribute__((aligned(16))) unsigned char ba_lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, g = lane >> 5;
   const int N = static_cast<int>(a.N), H = static_cast<int>(a.H), D = static_cast<int>(a.D);
@@ -366,9 +327,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_query_kernel(const BaArgs
   if (BWD) lse = a.lse[stat_row], lse_lo = a.lse[plane + stat_row], delta = a.delta[stat_row];
   f32x16 acc[NB];
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+  for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma_zero();
 
   for (int j0 = 0; j0 < N; j0 += kBaTile) {
     const int krows = N - j0 < kBaTile ? N - j0 : kBaTile;
@@ -383,7 +342,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_query_kernel(const BaArgs
     ba_add_bias<T, NB>(s, s_lo, sbw, staged, a.scale, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (ba_krow(r, g) >= krows) s[r] = ninf;
+      if (mfma_c_row(r, g) >= krows) s[r] = ninf;
 
     float keep[16];
 #pragma unroll
@@ -458,7 +417,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_query_kernel(const BaArgs
 template <typename T, int NB>
 __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_key_kernel(const BaArgs a) {
   using G = BaGeo<T, NB>;
-  using M = BaMma<T>;
+  using M = Mma32<T>;
   extern __shared__ __attribute__((aligned(16))) unsigned char ba_lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, g = lane >> 5;
   const int N = static_cast<int>(a.N), H = static_cast<int>(a.H), D = static_cast<int>(a.D);
@@ -487,9 +446,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_key_kernel(const BaArgs a
 
   f32x16 dk[NB], dv[NB];
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dk[nb][r] = 0.f, dv[nb][r] = 0.f;
+  for (int nb = 0; nb < NB; ++nb) dk[nb] = mfma_zero(), dv[nb] = mfma_zero();
   const int64_t head_rows = (blk.b * H + hc) * N;  // the head's rows of lse and delta
 
   for (int i0 = 0; i0 < N; i0 += kBaTile) {
@@ -511,7 +468,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_key_kernel(const BaArgs a
     f32x16 pd;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int qi = ba_krow(r, g);
+      const int qi = mfma_c_row(r, g);
       const float lse = __shfl(lse_n, qi), lse_lo = __shfl(lo_n, qi), delta = __shfl(delta_n, qi);
       const float p = lse == ninf || !key_ok ? 0.f : ba_weight<T>(s[r], s_lo[r], lse, lse_lo);
       float keep = 1.f;
@@ -529,7 +486,7 @@ __global__ __launch_bounds__(64 * kBaMaxWaves) void ba_key_kernel(const BaArgs a
     ba_accumulate<T, NB>(dk, xs, s, lane);   // dK^T += Q^T dS
     if (a.dbias) {  // (uniform: every wave reaches the barrier; a wave's own tile is read before it is overwritten)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sbw[n * G::BS + ba_krow(r, g)] = from_acc<T>(s[r]);
+      for (int r = 0; r < 16; ++r) sbw[n * G::BS + mfma_c_row(r, g)] = from_acc<T>(s[r]);
       __syncthreads();
       ba_store_dbias<T>(sb, a, blk.b, i0, j0, blk.h0, G::BS);
     }
@@ -555,13 +512,6 @@ __global__ __launch_bounds__(256) void ba_delta_kernel(const T* __restrict__ out
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 template <typename F>
-int with_ba_dtype(int dtype, F&& f) {
-  if (dtype == kF32) return f(float{});
-  if (dtype == kF16) return f(f16_t{});
-  return f(bf16_t{});
-}
-
-template <typename F>
 int with_ba_width(int64_t D, F&& f) {
   if (D <= 32) return f(std::integral_constant<int, 1>{});
   if (D <= 64) return f(std::integral_constant<int, 2>{});
@@ -569,40 +519,55 @@ int with_ba_width(int64_t D, F&& f) {
   return f(std::integral_constant<int, 4>{});
 }
 
-// everything the entry points refuse about the sizes and the rate; fills the geometry of the launch
-int check_ba(const char* who, int dtype, float drop, BaArgs* a, size_t wave_bytes) {
-  if (dtype != kF32 && dtype != kF16 && dtype != kBF16) return fail(who, "operands must be float32, float16 or bfloat16");
-  if (a->B < 0 || a->N < 1 || a->H < 1) return fail(who, "q, k, v must be (B, N, H, D) with N >= 1 and H >= 1");
-  if (a->D < 1 || a->D > kBaMaxDim)
-    return fail(who, "head width " + std::to_string(a->D) + ": the kernels take 1 to " + std::to_string(kBaMaxDim));
-  if (!gat_dropout_params(drop, &a->threshold, &a->keep_scale)) return fail(who, "the dropout probability must lie in [0, 1)");
-  if (a->N > INT32_MAX / 2 || a->H > INT32_MAX / 2) return fail(who, "sizes overflow");
-  int hg = static_cast<int>(kBaLdsBytes / wave_bytes);
-  hg = hg > kBaMaxWaves ? kBaMaxWaves : hg;
-  hg = hg > a->H ? static_cast<int>(a->H) : hg;
-  a->hg = hg;
-  a->tiles = static_cast<int>((a->N + kBaTile - 1) / kBaTile);
-  a->groups = static_cast<int>((a->H + hg - 1) / hg);
-  if (a->B > 0 && a->B > INT32_MAX / a->tiles / a->groups) return fail(who, "more workgroups than one launch takes");
-  return 0;
+// BaGeo<T, NB>::kWaveBytes of the instance that dtype and D select
+size_t ba_wave_bytes(int dtype, int64_t D) {
+  const size_t item = float_itemsize(dtype), vec = 16 / item, dp = static_cast<size_t>((D + 31) / 32 * 32);
+  return item * (2 * kBaTile * (dp + vec) + kBaTile * (kBaTile + vec));
 }
 
-bool ba_aligned(const void* p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
+// What forward and backward open with: the arguments they share into `a`, everything they refuse about the sizes and
+// the rate, the geometry of the launch.
+int check_ba(const char* who, int dtype, const void* q, const void* k, const void* v, const void* bias, const void* mask, int64_t B,
+             int64_t N, int64_t H, int64_t D, float scale, float drop, uint64_t seed, BaArgs* a) {
+  a->q = q, a->k = k, a->v = v, a->bias = bias, a->mask = static_cast<const uint8_t*>(mask);
+  a->B = B, a->N = N, a->H = H, a->D = D, a->scale = scale, a->seed = seed;
+  if (check_float16(who, dtype, "operands")) return -1;
+  if (B < 0 || N < 1 || H < 1) return fail(who, "q, k, v must be (B, N, H, D) with N >= 1 and H >= 1");
+  if (D < 1 || D > kBaMaxDim)
+    return fail(who, "head width " + std::to_string(D) + ": the kernels take 1 to " + std::to_string(kBaMaxDim));
+  if (!gat_dropout_params(drop, &a->threshold, &a->keep_scale)) return fail(who, "the dropout probability must lie in [0, 1)");
+  if (N > INT32_MAX / 2 || H > INT32_MAX / 2) return fail(who, "sizes overflow");
+  int hg = static_cast<int>(kBaLdsBytes / ba_wave_bytes(dtype, D));
+  hg = hg > kBaMaxWaves ? kBaMaxWaves : hg;
+  hg = hg > H ? static_cast<int>(H) : hg;
+  a->hg = hg;
+  a->tiles = static_cast<int>((N + kBaTile - 1) / kBaTile);
+  a->groups = static_cast<int>((H + hg - 1) / hg);
+  if (B > 0 && B > INT32_MAX / a->tiles / a->groups) return fail(who, "more workgroups than one launch takes");
+  return 0;
+}
 
 template <typename T>
 void ba_vector_flags(BaArgs* a) {
   constexpr int VEC = 16 / sizeof(T);
-  a->vec_ok = a->D % VEC == 0 && ba_aligned(a->q, 16) && ba_aligned(a->k, 16) && ba_aligned(a->v, 16) &&
-              (!a->dout || ba_aligned(a->dout, 16));
+  a->vec_ok = a->D % VEC == 0 && aligned_to(a->q, 16) && aligned_to(a->k, 16) && aligned_to(a->v, 16) &&
+              (!a->dout || aligned_to(a->dout, 16));
   const size_t four = 4 * sizeof(T);
-  a->out_vec_ok = a->D % 4 == 0 && (!a->o || ba_aligned(a->o, four)) && (!a->dq || ba_aligned(a->dq, four)) &&
-                  (!a->dk || ba_aligned(a->dk, four)) && (!a->dv || ba_aligned(a->dv, four));
-  a->bias_vec_ok = a->H % kBaMaxWaves == 0 && (!a->bias || ba_aligned(a->bias, four)) && (!a->dbias || ba_aligned(a->dbias, four));
+  a->out_vec_ok = a->D % 4 == 0 && (!a->o || aligned_to(a->o, four)) && (!a->dq || aligned_to(a->dq, four)) &&
+                  (!a->dk || aligned_to(a->dk, four)) && (!a->dv || aligned_to(a->dv, four));
+  a->bias_vec_ok = a->H % kBaMaxWaves == 0 && (!a->bias || aligned_to(a->bias, four)) && (!a->dbias || aligned_to(a->dbias, four));
 }
 
-size_t ba_wave_bytes(int dtype, int64_t D) {
-  const size_t item = dtype == kF32 ? 4 : 2, vec = 16 / item, dp = static_cast<size_t>((D + 31) / 32 * 32);
-  return item * (2 * kBaTile * (dp + vec) + kBaTile * (kBaTile + vec));
+// The launch of the three tile kernels of a (T, NB) instance: a workgroup per (batch, tile, head group), a wavefront
+// and kWaveBytes of LDS per head of the group.
+struct BaLaunch {
+  dim3 grid, block;
+  size_t lds;
+};
+template <typename T, int NB>
+BaLaunch ba_launch(const BaArgs& a) {
+  return BaLaunch{dim3(static_cast<unsigned>(a.B * a.tiles * a.groups)), dim3(static_cast<unsigned>(64 * a.hg)),
+                  BaGeo<T, NB>::kWaveBytes * a.hg};
 }
 
 }  // namespace
@@ -622,21 +587,19 @@ int dgla_biased_attention_forward(int dtype, const void* q, const void* k, const
                                   float* lse, void* hip_stream) {
   const char* who = "biased_attention";
   BaArgs a{};
-  a.q = q, a.k = k, a.v = v, a.bias = bias, a.mask = static_cast<const uint8_t*>(mask), a.o = out, a.lse = lse;
-  a.B = B, a.N = N, a.H = H, a.D = D, a.scale = scale, a.seed = seed;
-  if (check_ba(who, dtype, drop, &a, ba_wave_bytes(dtype, D > 0 && D <= kBaMaxDim ? D : 1))) return -1;
+  a.o = out, a.lse = lse;
+  if (check_ba(who, dtype, q, k, v, bias, mask, B, N, H, D, scale, drop, seed, &a)) return -1;
   if (B == 0) return 0;
   if (!q || !k || !v || !out || !lse) return fail(who, "q, k, v, out or lse is null");
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
-  return with_ba_dtype(dtype, [&](auto ttag) -> int {
+  return with_float16(dtype, [&](auto ttag) -> int {
     using T = decltype(ttag);
     ba_vector_flags<T>(&a);
     return with_ba_width(D, [&](auto ntag) -> int {
       constexpr int NB = decltype(ntag)::value;
-      const dim3 grid(static_cast<unsigned>(B * a.tiles * a.groups)), block(static_cast<unsigned>(64 * a.hg));
-      const size_t lds = BaGeo<T, NB>::kWaveBytes * a.hg;
-      hipLaunchKernelGGL((ba_query_kernel<T, NB, false>), grid, block, lds, s, a);
+      const BaLaunch l = ba_launch<T, NB>(a);
+      hipLaunchKernelGGL((ba_query_kernel<T, NB, false>), l.grid, l.block, l.lds, s, a);
       DGLA_CHECK_HIP(hipGetLastError());
       return 0;
     });
@@ -649,10 +612,8 @@ int dgla_biased_attention_backward(int dtype, const void* q, const void* k, cons
                                    void* workspace, size_t workspace_bytes, void* hip_stream) {
   const char* who = "biased_attention";
   BaArgs a{};
-  a.q = q, a.k = k, a.v = v, a.bias = bias, a.mask = static_cast<const uint8_t*>(mask), a.out = out, a.dout = dout;
-  a.lse = const_cast<float*>(lse), a.dq = dq, a.dk = dk, a.dv = dv, a.dbias = dbias;
-  a.B = B, a.N = N, a.H = H, a.D = D, a.scale = scale, a.seed = seed;
-  if (check_ba(who, dtype, drop, &a, ba_wave_bytes(dtype, D > 0 && D <= kBaMaxDim ? D : 1))) return -1;
+  a.out = out, a.dout = dout, a.lse = const_cast<float*>(lse), a.dq = dq, a.dk = dk, a.dv = dv, a.dbias = dbias;
+  if (check_ba(who, dtype, q, k, v, bias, mask, B, N, H, D, scale, drop, seed, &a)) return -1;
   if (B == 0) return 0;
   if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv) return fail(who, "an operand or a gradient of q, k, v is null");
   const size_t need = dgla_biased_attention_workspace_bytes(B, N, H);
@@ -662,7 +623,7 @@ int dgla_biased_attention_backward(int dtype, const void* q, const void* k, cons
   Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, need)) return -1;
   a.delta = reinterpret_cast<float*>(scratch.p);
-  return with_ba_dtype(dtype, [&](auto ttag) -> int {
+  return with_float16(dtype, [&](auto ttag) -> int {
     using T = decltype(ttag);
     ba_vector_flags<T>(&a);
     const int64_t rows = B * N * H;
@@ -670,10 +631,9 @@ int dgla_biased_attention_backward(int dtype, const void* q, const void* k, cons
                        static_cast<const T*>(dout), rows, static_cast<int>(N), static_cast<int>(H), static_cast<int>(D), a.delta);
     return with_ba_width(D, [&](auto ntag) -> int {
       constexpr int NB = decltype(ntag)::value;
-      const dim3 grid(static_cast<unsigned>(B * a.tiles * a.groups)), block(static_cast<unsigned>(64 * a.hg));
-      const size_t lds = BaGeo<T, NB>::kWaveBytes * a.hg;
-      hipLaunchKernelGGL((ba_key_kernel<T, NB>), grid, block, lds, s, a);
-      hipLaunchKernelGGL((ba_query_kernel<T, NB, true>), grid, block, lds, s, a);
+      const BaLaunch l = ba_launch<T, NB>(a);
+      hipLaunchKernelGGL((ba_key_kernel<T, NB>), l.grid, l.block, l.lds, s, a);
+      hipLaunchKernelGGL((ba_query_kernel<T, NB, true>), l.grid, l.block, l.lds, s, a);
       DGLA_CHECK_HIP(hipGetLastError());
       return 0;
     });

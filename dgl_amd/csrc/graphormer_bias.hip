@@ -298,14 +298,11 @@ int gb_next_pow2_log(int64_t x) {  // log2 of the smallest power of two >= x
   return lg;
 }
 
-size_t gb_itemsize(int dtype) { return dtype == kF32 ? 4 : 2; }
-
-// f(T{}) with T = float, f16_t or bf16_t: the operand type of a call, checked by the caller
+// f(LMAX): the row gathers the forward holds in registers, 8 or kGbMaxLen
 template <typename F>
-int with_gb_dtype(int dtype, F&& f) {
-  if (dtype == kF32) return f(float{});
-  if (dtype == kF16) return f(f16_t{});
-  return f(bf16_t{});
+int with_gb_lmax(int64_t Lc, F&& f) {
+  if (Lc <= 8) return f(std::integral_constant<int, 8>{});
+  return f(std::integral_constant<int, kGbMaxLen>{});
 }
 
 struct GbShape {
@@ -350,7 +347,7 @@ GbLayout gb_layout(const GbShape& g) {
 // everything the three entry points refuse about the shape
 int check_gb_shape(const char* who, int idtype_bits, int dtype, GbShape* g, int64_t path_len) {
   if (!idbits_ok(idtype_bits)) return fail(who, "idtype must be int32 or int64");
-  if (dtype != kF32 && dtype != kF16 && dtype != kBF16) return fail(who, "operands must be float32, float16 or bfloat16");
+  if (check_float16(who, dtype, "operands")) return -1;
   if (g->P < 0 || path_len < 0 || g->E < 0 || g->srows < 0) return fail(who, "negative size");
   if (g->H < 1 || g->H > kGbMaxHeads)
     return fail(who, std::to_string(g->H) + " heads: the kernels take 1 to " + std::to_string(kGbMaxHeads));
@@ -378,19 +375,16 @@ int gb_forward(const char* who, const GbShape& g, const Idx* dist, const Idx* pa
   waves = waves > kGbBlock / 64 ? kGbBlock / 64 : waves;
   const int64_t blocks = (g.P + static_cast<int64_t>(waves) * ppw - 1) / (static_cast<int64_t>(waves) * ppw);
   if (blocks > INT32_MAX) return fail(who, std::to_string(g.P) + " pairs are more than one launch takes");
-  const auto aligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  const int vec_ok = g.H % VEC == 0 && aligned(table) && aligned(out);
+  const int vec_ok = g.H % VEC == 0 && aligned_to(table, 16) && aligned_to(out, 16);
   const size_t lds = static_cast<size_t>(spatial_bytes) + ids_bytes * static_cast<size_t>(waves);
   const dim3 grid(static_cast<unsigned>(blocks)), block(static_cast<unsigned>(64 * waves));
-  if (g.Lc <= 8)
-    hipLaunchKernelGGL((gb_forward_kernel<T, Idx, 8>), grid, block, lds, s, dist, paths, g.P, g.Lp, static_cast<int>(g.Lc), table,
-                       g.E, g.max_len, static_cast<int>(g.H), spatial, static_cast<int>(g.srows), out, lg, spatial_bytes, vec_ok);
-  else
-    hipLaunchKernelGGL((gb_forward_kernel<T, Idx, kGbMaxLen>), grid, block, lds, s, dist, paths, g.P, g.Lp, static_cast<int>(g.Lc),
-                       table, g.E, g.max_len, static_cast<int>(g.H), spatial, static_cast<int>(g.srows), out, lg, spatial_bytes,
-                       vec_ok);
-  DGLA_CHECK_HIP(hipGetLastError());
-  return 0;
+  return with_gb_lmax(g.Lc, [&](auto ltag) -> int {
+    hipLaunchKernelGGL((gb_forward_kernel<T, Idx, decltype(ltag)::value>), grid, block, lds, s, dist, paths, g.P, g.Lp,
+                       static_cast<int>(g.Lc), table, g.E, g.max_len, static_cast<int>(g.H), spatial, static_cast<int>(g.srows), out, lg,
+                       spatial_bytes, vec_ok);
+    DGLA_CHECK_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 // the inverted index into the workspace, then dT; the flag is read back before dT is trusted
@@ -473,7 +467,7 @@ int dgla_graphormer_bias_forward(int idtype_bits, int dtype, const void* dist, c
   const DeviceGuard dev(s, out);
   return with_idx(idtype_bits, [&](auto itag) -> int {
     using Idx = decltype(itag);
-    return with_gb_dtype(dtype, [&](auto ttag) -> int {
+    return with_float16(dtype, [&](auto ttag) -> int {
       using T = decltype(ttag);
       return gb_forward<T, Idx>(who, g, static_cast<const Idx*>(dist), static_cast<const Idx*>(paths),
                                 static_cast<const T*>(table), static_cast<const T*>(spatial), static_cast<T*>(out), s);
@@ -498,7 +492,7 @@ int dgla_graphormer_bias_backward(int idtype_bits, int dtype, const void* dist, 
   if (optional_workspace(who, workspace, workspace_bytes, L.bytes)) return -1;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, grad_out);
-  const size_t item = gb_itemsize(dtype);
+  const size_t item = float_itemsize(dtype);
   if (g.P == 0) {  // nothing to sum: zeros, without a launch
     if (want_table) DGLA_CHECK_HIP(hipMemsetAsync(grad_table, 0, item * static_cast<size_t>(g.E * g.max_len * g.H), s));
     if (grad_spatial) DGLA_CHECK_HIP(hipMemsetAsync(grad_spatial, 0, item * static_cast<size_t>(g.srows * g.H), s));
@@ -508,7 +502,7 @@ int dgla_graphormer_bias_backward(int idtype_bits, int dtype, const void* dist, 
   if (scratch.take(workspace, workspace_bytes, L.bytes)) return -1;
   return with_idx(idtype_bits, [&](auto itag) -> int {
     using Idx = decltype(itag);
-    return with_gb_dtype(dtype, [&](auto ttag) -> int {
+    return with_float16(dtype, [&](auto ttag) -> int {
       using T = decltype(ttag);
       const Idx* d = static_cast<const Idx*>(dist);
       const T* go = static_cast<const T*>(grad_out);

@@ -2,8 +2,11 @@
 // pinsage, csr_mm, coo2csr, labor, knn, matching, subgraph, exclude, traversal, topk, biased, etype): launch geometry, the
 // structural CSR check and the typed CSR view, the workspace carver and its two bindings, the read-back, the id-width
 // and float-type dispatches, and what the seed-row samplers (topk, biased, etype) share: the refusals of their seeds and
-// outputs, the head of their workspace and the typed view of their arrays.  fail(msg), align256() and gptr<T> live in
-// common.h, which every unit includes.  Nothing here is device code.
+// outputs, the head of their workspace and the typed view of their arrays.  The three dense Graphormer units
+// (graphormer_bias, biased_attention, spatial_encoder3d) take from it the float32 / float16 / bfloat16 dispatch and its
+// refusal, the item size, the pointer alignment test, the workspace carver and the optional-workspace binding; what the
+// two MFMA units share on the device is in mfma_tile.h.  fail(msg), align256() and gptr<T> live in common.h, which
+// every unit includes.  Nothing here is device code.
 #pragma once
 #include <stdint.h>
 
@@ -164,6 +167,27 @@ decltype(auto) with_float(int dtype, F&& f) {
   if (dtype == kF32) return f(float{});
   return f(double{});
 }
+
+// ---- dense units: operands of float32, float16 or bfloat16 -----------------------------------------------------------
+// The refusal of any other dtype: "<who>: <noun> must be float32, float16 or bfloat16".
+inline int check_float16(const char* who, int dtype, const char* noun) {
+  if (dtype != kF32 && dtype != kF16 && dtype != kBF16) return fail(who, std::string(noun) + " must be float32, float16 or bfloat16");
+  return 0;
+}
+
+// f(T{}) with T = float, f16_t or bf16_t: the operand type of a call that passed check_float16
+template <typename F>
+decltype(auto) with_float16(int dtype, F&& f) {
+  if (dtype == kF32) return f(float{});
+  if (dtype == kF16) return f(f16_t{});
+  return f(bf16_t{});
+}
+
+// bytes of an element of such a dtype
+inline size_t float_itemsize(int dtype) { return dtype == kF32 ? 4 : 2; }
+
+// whether a vector access of `bytes` bytes may start at p
+inline bool aligned_to(const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
 
 // f(W{}, weighted): the type of an optional per-edge weight; a call without one runs the uniform form
 template <typename F>

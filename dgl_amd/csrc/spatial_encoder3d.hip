@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "host_util.h"
+#include "mfma_tile.h"
 
 namespace dgla {
 namespace {
@@ -46,44 +47,10 @@ constexpr int kSeFwdGroups = 512;  // persistent workgroups of the forward: two 
 constexpr int kSeBwdGroups = 256;  // of the backward (one per compute unit: its registers leave room for no more)
 constexpr int kSePartPad = kSeTile + 1;  // row of the [wave][head][pair] partial tile
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
-typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
-
-// One MFMA per operand type.  Raw is what a lane hands the instruction for A or B: FE consecutive k elements.
-template <typename T>
-struct SeMma;
-template <>
-struct SeMma<float> {
-  static constexpr int KSTEP = 2, FE = 1;
-  using Raw = float;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ void put(Raw& f, int e, float x) { f = x; }
-};
-template <>
-struct SeMma<f16_t> {
-  static constexpr int KSTEP = 16, FE = 8;
-  using Raw = u16x8;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void put(Raw& f, int e, f16_t x) { f[e] = __builtin_bit_cast(uint16_t, x); }
-};
-template <>
-struct SeMma<bf16_t> {
-  static constexpr int KSTEP = 16, FE = 8;
-  using Raw = u16x8;
-  static __device__ __forceinline__ f32x16 mma(Raw a, Raw b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b16x8, a), __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ void put(Raw& f, int e, bf16_t x) { f[e] = x.bits; }
-};
-
 // Geometry of a (T, NB, HB) instance: K <= 32 NB, H <= 32 HB, LDS rows padded by 16 bytes.
 template <typename T, int NB, int HB>
 struct SeGeo {
-  using M = SeMma<T>;
+  using M = Mma32<T>;
   static constexpr int VEC = 16 / sizeof(T);
   static constexpr int KP = 32 * NB, HP = 32 * HB;
   static constexpr int RS = KP + VEC;  // row of a [pair][K] tile
@@ -102,27 +69,17 @@ struct SeArgs {
   int K, H, out_vec_ok;
 };
 
-__device__ __forceinline__ f32x16 se_zero() {
-  f32x16 c;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) c[r] = 0.f;
-  return c;
-}
-
-// the row of the A operand (of the wave's 32) that register r of a C tile holds
-__device__ __forceinline__ int se_crow(int r, int g) { return 8 * (r >> 2) + 4 * g + (r & 3); }
-
 // A fragment out of an LDS tile whose rows are the operand's rows: elements k0 .. k0 + FE of row `row` (one read)
 template <typename T>
-__device__ __forceinline__ typename SeMma<T>::Raw se_frag_rows(const T* lds, int row, int k0, int rs) {
-  return *reinterpret_cast<const typename SeMma<T>::Raw*>(lds + row * rs + k0);
+__device__ __forceinline__ typename Mma32<T>::Raw se_frag_rows(const T* lds, int row, int k0, int rs) {
+  return *reinterpret_cast<const typename Mma32<T>::Raw*>(lds + row * rs + k0);
 }
 
 // A fragment of the TRANSPOSED tile: the contraction runs down the LDS rows k0 .. k0 + FE, the operand's row is the LDS
 // column `col` (consecutive lanes read consecutive addresses)
 template <typename T>
-__device__ __forceinline__ typename SeMma<T>::Raw se_frag_cols(const T* lds, int col, int k0, int rs) {
-  using M = SeMma<T>;
+__device__ __forceinline__ typename Mma32<T>::Raw se_frag_cols(const T* lds, int col, int k0, int rs) {
+  using M = Mma32<T>;
   typename M::Raw f;
 #pragma unroll
   for (int e = 0; e < M::FE; ++e) M::put(f, e, lds[(k0 + e) * rs + col]);
@@ -132,9 +89,9 @@ __device__ __forceinline__ typename SeMma<T>::Raw se_frag_cols(const T* lds, int
 // A stationary fragment out of global memory, element by element, once per workgroup: row `row` of a (rows x cols)
 // operand whose element (row, k) lies at src[row * row_stride + k * k_stride]; zero outside.
 template <typename T>
-__device__ __forceinline__ typename SeMma<T>::Raw se_frag_global(const T* __restrict__ src, int row, int rows, int k0, int cols,
+__device__ __forceinline__ typename Mma32<T>::Raw se_frag_global(const T* __restrict__ src, int row, int rows, int k0, int cols,
                                                                  int row_stride, int k_stride) {
-  using M = SeMma<T>;
+  using M = Mma32<T>;
   typename M::Raw f;
 #pragma unroll
   for (int e = 0; e < M::FE; ++e) M::put(f, e, row < rows && k0 + e < cols ? src[row * row_stride + (k0 + e) * k_stride] : T{});
@@ -193,13 +150,13 @@ __device__ __forceinline__ void se_features(T* gl, const float* xs, const SeBasi
 }
 
 // z^T[hidden][pair] = W1 g^T of the wave's 32 hidden units, plus b1: the lane's pair is lane % 32, register r holds the
-// hidden unit 32 wave + se_crow(r, lane / 32).
+// hidden unit 32 wave + mfma_c_row(r, lane / 32).
 template <typename T, int NB, int HB>
-__device__ __forceinline__ f32x16 se_layer1(const typename SeMma<T>::Raw (&w1f)[SeGeo<T, NB, HB>::KK], const T* gl, const float (&b1r)[16],
+__device__ __forceinline__ f32x16 se_layer1(const typename Mma32<T>::Raw (&w1f)[SeGeo<T, NB, HB>::KK], const T* gl, const float (&b1r)[16],
                                             int K, int lane) {
   using G = SeGeo<T, NB, HB>;
-  using M = SeMma<T>;
-  f32x16 c = se_zero();
+  using M = Mma32<T>;
+  f32x16 c = mfma_zero();
 #pragma unroll
   for (int kk = 0; kk < G::KK; ++kk)
     if (kk * M::KSTEP < K) c = M::mma(w1f[kk], se_frag_rows<T>(gl, lane & 31, kk * M::KSTEP + (lane >> 5) * M::FE, G::RS), c);
@@ -218,7 +175,7 @@ __device__ __forceinline__ float se_gelu(float z, float* slope) {
 template <typename T, int NB, int HB>
 __global__ __launch_bounds__(64 * NB) void se_forward_kernel(const SeArgs a) {
   using G = SeGeo<T, NB, HB>;
-  using M = SeMma<T>;
+  using M = Mma32<T>;
   __shared__ __attribute__((aligned(16))) T gl[kSeTile * G::RS];
   __shared__ float part[NB * G::HP * kSePartPad];
   __shared__ float xs[kSeTile], b2s[G::HP];
@@ -237,13 +194,13 @@ __global__ __launch_bounds__(64 * NB) void se_forward_kernel(const SeArgs a) {
     for (int st = 0; st < G::MK; ++st)
 #pragma unroll
       for (int e = 0; e < M::FE; ++e) {
-        const int hh = 32 * hb + n, ko = 32 * wave + se_crow(st * M::FE + e, g);
+        const int hh = 32 * hb + n, ko = 32 * wave + mfma_c_row(st * M::FE + e, g);
         M::put(w2f[hb][st], e, hh < H && ko < K ? w2[hh * K + ko] : T{});
       }
   float b1r[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ko = 32 * wave + se_crow(r, g);
+    const int ko = 32 * wave + mfma_c_row(r, g);
     b1r[r] = ko < K ? to_acc<T>(static_cast<const T*>(a.b1)[ko]) : 0.f;
   }
   for (int hh = threadIdx.x; hh < G::HP; hh += G::THREADS) b2s[hh] = hh < H ? to_acc<T>(static_cast<const T*>(a.b2)[hh]) : 0.f;
@@ -268,16 +225,16 @@ __global__ __launch_bounds__(64 * NB) void se_forward_kernel(const SeArgs a) {
     }
 #pragma unroll
     for (int hb = 0; hb < HB; ++hb) {
-      f32x16 o = se_zero();
+      f32x16 o = mfma_zero();
 #pragma unroll
       for (int st = 0; st < G::MK; ++st) {
         typename M::Raw b;
 #pragma unroll
         for (int e = 0; e < M::FE; ++e) M::put(b, e, from_acc<T>(h[st * M::FE + e]));
-        o = M::mma(w2f[hb][st], b, o);  // o[r]: head 32 hb + se_crow(r, g), pair n, the wave's share of the sum
+        o = M::mma(w2f[hb][st], b, o);  // o[r]: head 32 hb + mfma_c_row(r, g), pair n, the wave's share of the sum
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) part[(wave * G::HP + 32 * hb + se_crow(r, g)) * kSePartPad + n] = o[r];
+      for (int r = 0; r < 16; ++r) part[(wave * G::HP + 32 * hb + mfma_c_row(r, g)) * kSePartPad + n] = o[r];
     }
     __syncthreads();
 
@@ -320,7 +277,7 @@ __device__ __forceinline__ float se_sum_pairs(float v) {
 template <typename T, int NB, int HB>
 __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
   using G = SeGeo<T, NB, HB>;
-  using M = SeMma<T>;
+  using M = Mma32<T>;
   __shared__ __attribute__((aligned(16))) T gl[kSeTile * G::RS];   // features  [pair][k]
   __shared__ __attribute__((aligned(16))) T hl[kSeTile * G::RS];   // h         [pair][hidden]
   __shared__ __attribute__((aligned(16))) T zl[kSeTile * G::RS];   // dz        [pair][hidden]
@@ -345,7 +302,7 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
   float b1r[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ko = 32 * wave + se_crow(r, g);
+    const int ko = 32 * wave + mfma_c_row(r, g);
     b1r[r] = ko < K ? to_acc<T>(static_cast<const T*>(a.b1)[ko]) : 0.f;
   }
   const SeBasis bf = se_basis(a, threadIdx.x % G::KP);
@@ -353,9 +310,9 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
 
   f32x16 dw1[NB], dw2[HB];
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) dw1[nb] = se_zero();
+  for (int nb = 0; nb < NB; ++nb) dw1[nb] = mfma_zero();
 #pragma unroll
-  for (int hb = 0; hb < HB; ++hb) dw2[hb] = se_zero();
+  for (int hb = 0; hb < HB; ++hb) dw2[hb] = mfma_zero();
   float db1a[16], dma[16], dsa[16], db2a = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) db1a[r] = 0.f, dma[r] = 0.f, dsa[r] = 0.f;
@@ -383,7 +340,7 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
 
     // the lane's pair n and its 16 hidden units: z, h, gelu'(z); dh = dout W2; dz = dh gelu'(z)
     f32x16 z = se_layer1<T, NB, HB>(w1f, gl, b1r, K, lane);
-    f32x16 dh = se_zero();
+    f32x16 dh = mfma_zero();
 #pragma unroll
     for (int st = 0; st < G::HK; ++st)
       if (st * M::KSTEP < H) dh = M::mma(w2tf[st], se_frag_rows<T>(dol, n, st * M::KSTEP + g * M::FE, G::RO), dh);
@@ -406,7 +363,7 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
     __syncthreads();
 
     // dg^T[k][pair] = W1^T dz^T for the wave's 32 basis functions k; dx of the pair and the terms of dmeans and dstds
-    f32x16 dg = se_zero();
+    f32x16 dg = mfma_zero();
 #pragma unroll
     for (int kk = 0; kk < G::KK; ++kk)
       if (kk * M::KSTEP < K) dg = M::mma(w1tf[kk], se_frag_rows<T>(zl, n, kk * M::KSTEP + g * M::FE, G::RS), dg);
@@ -414,7 +371,7 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
     float dxl = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int k = 32 * wave + se_crow(r, g);
+      const int k = 32 * wave + mfma_c_row(r, g);
       const SeBasis bk = basis[k];
       float t;
       const float u = dg[r] * se_gauss<T>(bk, x, &t) * bk.isd;  // dg g / sd
@@ -451,23 +408,23 @@ __global__ __launch_bounds__(64 * NB) void se_backward_kernel(const SeArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {  // dw1[nb][r]: hidden 32 wave + se_crow(r, g), basis function 32 nb + n
-      const int ko = 32 * wave + se_crow(r, g), k = 32 * nb + n;
+    for (int r = 0; r < 16; ++r) {  // dw1[nb][r]: hidden 32 wave + mfma_c_row(r, g), basis function 32 nb + n
+      const int ko = 32 * wave + mfma_c_row(r, g), k = 32 * nb + n;
       if (ko < K && k < K) part[ko * K + k] = dw1[nb][r];
     }
   part += K * K;
 #pragma unroll
   for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {  // dw2[hb][r]: head 32 hb + se_crow(r, g), hidden 32 wave + n
-      const int hh = 32 * hb + se_crow(r, g), ko = 32 * wave + n;
+    for (int r = 0; r < 16; ++r) {  // dw2[hb][r]: head 32 hb + mfma_c_row(r, g), hidden 32 wave + n
+      const int hh = 32 * hb + mfma_c_row(r, g), ko = 32 * wave + n;
       if (hh < H && ko < K) part[hh * K + ko] = dw2[hb][r];
     }
   part += H * K;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const float s1 = se_sum_pairs(db1a[r]), sm = se_sum_pairs(dma[r]), ss = se_sum_pairs(dsa[r]);
-    const int k = 32 * wave + se_crow(r, g);
+    const int k = 32 * wave + mfma_c_row(r, g);
     if (n == 0 && k < K) part[k] = s1, part[K + k] = sm, part[2 * K + k] = ss;
   }
   if (threadIdx.x < H) part[3 * K + threadIdx.x] = db2a;
@@ -530,7 +487,7 @@ const char* const kSeWho = "spatial_encoder_3d";
 
 // everything the entry points refuse about the sizes; fills the geometry
 int check_se(int dtype, int64_t B, int64_t N, int64_t K, int64_t H, SeArgs* a) {
-  if (dtype != kF32 && dtype != kF16 && dtype != kBF16) return fail(kSeWho, "the weights must be float32, float16 or bfloat16");
+  if (check_float16(kSeWho, dtype, "the weights")) return -1;
   if (B < 0 || N < 0) return fail(kSeWho, "coord must be (B, N, 3) with B >= 0 and N >= 0");
   if (K < 1 || K > kSeMaxK)
     return fail(kSeWho, "num_kernels " + std::to_string(K) + ": the kernels take 1 to " + std::to_string(kSeMaxK));
@@ -540,6 +497,18 @@ int check_se(int dtype, int64_t B, int64_t N, int64_t K, int64_t H, SeArgs* a) {
     return fail(kSeWho, "sizes overflow");
   a->N = N, a->pairs = B * N * N, a->tiles = (a->pairs + kSeTile - 1) / kSeTile;
   a->K = static_cast<int>(K), a->H = static_cast<int>(H);
+  return 0;
+}
+
+// The eleven operands of forward and backward into `a`, after the one refusal of a null among them and `io`, the
+// tensor the direction adds (`io_name`: out or dout).
+int bind_se(SeArgs* a, const float* coord, const float* gamma_src, const float* gamma_tgt, const float* beta_src,
+            const float* beta_tgt, const float* means, const float* stds, const void* w1, const void* b1, const void* w2,
+            const void* b2, const void* io, const char* io_name) {
+  if (!coord || !gamma_src || !gamma_tgt || !beta_src || !beta_tgt || !means || !stds || !w1 || !b1 || !w2 || !b2 || !io)
+    return fail(kSeWho, std::string("an operand or ") + io_name + " is null");
+  a->coord = coord, a->gs = gamma_src, a->gt = gamma_tgt, a->bs = beta_src, a->bt = beta_tgt, a->means = means, a->stds = stds;
+  a->w1 = w1, a->b1 = b1, a->w2 = w2, a->b2 = b2;
   return 0;
 }
 
@@ -560,7 +529,7 @@ SeWorkspace se_workspace(int64_t pairs, int64_t K, int64_t H) {
 
 template <typename F>
 int with_se_instance(int dtype, int64_t K, int64_t H, F&& f) {
-  auto with_shape = [&](auto ttag) -> int {
+  return with_float16(dtype, [&](auto ttag) -> int {
     auto with_h = [&](auto nbtag) -> int {
       if (H <= 32) return f(ttag, nbtag, std::integral_constant<int, 1>{});
       return f(ttag, nbtag, std::integral_constant<int, 2>{});
@@ -568,10 +537,7 @@ int with_se_instance(int dtype, int64_t K, int64_t H, F&& f) {
     if (K <= 32) return with_h(std::integral_constant<int, 1>{});
     if (K <= 64) return with_h(std::integral_constant<int, 2>{});
     return with_h(std::integral_constant<int, 4>{});
-  };
-  if (dtype == kF32) return with_shape(float{});
-  if (dtype == kF16) return with_shape(f16_t{});
-  return with_shape(bf16_t{});
+  });
 }
 
 }  // namespace
@@ -594,11 +560,8 @@ int dgla_spatial_encoder3d_forward(int dtype, const float* coord, const float* g
   SeArgs a{};
   if (check_se(dtype, B, N, K, H, &a)) return -1;
   if (a.pairs == 0) return 0;
-  if (!coord || !gamma_src || !gamma_tgt || !beta_src || !beta_tgt || !means || !stds || !w1 || !b1 || !w2 || !b2 || !out)
-    return fail(kSeWho, "an operand or out is null");
-  a.coord = coord, a.gs = gamma_src, a.gt = gamma_tgt, a.bs = beta_src, a.bt = beta_tgt, a.means = means, a.stds = stds;
-  a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.out = out;
-  a.out_vec_ok = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  if (bind_se(&a, coord, gamma_src, gamma_tgt, beta_src, beta_tgt, means, stds, w1, b1, w2, b2, out, "out")) return -1;
+  a.out = out, a.out_vec_ok = aligned_to(out, 16);
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const DeviceGuard dev(s, out);
   return with_se_instance(dtype, K, H, [&](auto ttag, auto nbtag, auto hbtag) -> int {
@@ -620,8 +583,7 @@ int dgla_spatial_encoder3d_backward(int dtype, const float* coord, const float* 
   SeArgs a{};
   if (check_se(dtype, B, N, K, H, &a)) return -1;
   if (a.pairs == 0) return 0;
-  if (!coord || !gamma_src || !gamma_tgt || !beta_src || !beta_tgt || !means || !stds || !w1 || !b1 || !w2 || !b2 || !dout)
-    return fail(kSeWho, "an operand or dout is null");
+  if (bind_se(&a, coord, gamma_src, gamma_tgt, beta_src, beta_tgt, means, stds, w1, b1, w2, b2, dout, "dout")) return -1;
   if (!dw1 || !db1 || !dw2 || !db2 || !dmeans || !dstds || !dgamma_src || !dgamma_tgt || !dbeta_src || !dbeta_tgt)
     return fail(kSeWho, "a gradient is null");
   const SeWorkspace w = se_workspace(a.pairs, K, H);
@@ -630,9 +592,7 @@ int dgla_spatial_encoder3d_backward(int dtype, const float* coord, const float* 
   const DeviceGuard dev(s, dw1);
   Scratch scratch(s);
   if (scratch.take(workspace, workspace_bytes, w.bytes)) return -1;
-  a.coord = coord, a.gs = gamma_src, a.gt = gamma_tgt, a.bs = beta_src, a.bt = beta_tgt, a.means = means, a.stds = stds;
-  a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.dout = dout;
-  a.dx = reinterpret_cast<float*>(scratch.p + w.dx), a.part = reinterpret_cast<float*>(scratch.p + w.part);
+  a.dout = dout, a.dx = reinterpret_cast<float*>(scratch.p + w.dx), a.part = reinterpret_cast<float*>(scratch.p + w.part);
   return with_se_instance(dtype, K, H, [&](auto ttag, auto nbtag, auto hbtag) -> int {
     using T = decltype(ttag);
     constexpr int NB = decltype(nbtag)::value, HB = decltype(hbtag)::value;
